@@ -9,6 +9,7 @@ and outputs resident in HBM.  value = uncompressed bytes through both
 directions / time, whole job, GiB/s.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--gib G]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Multi-GPU: streams are independent, so each rank compresses its own shard;
@@ -82,6 +83,63 @@ def source_sha16():
             h.update(str(f.relative_to(ROOT)).encode())
             h.update(f.read_bytes())
     return h.hexdigest()[:16]
+
+
+DUMP_MAX_STREAMS = 1 << 16   # per-stream lengths / errors kept in a dump
+
+
+def dump_outputs(out_dir, comp, comp_lens, comp_errs, back, back_lens,
+                 back_errs, n_files):
+    """--dump-outputs: what the last timed step handed back to its caller,
+    as .npy files (float32 / float64) under `out_dir`, so that two builds
+    can be compared output for output.  Per stream: the compressed and the
+    decompressed length and both error records (kind, a, b, c) - for every
+    stream, or a seeded sample of DUMP_MAX_STREAMS of them in larger
+    batches.  Bytes: the compressed and the decompressed bytes of one stream
+    per bench input, each from a seeded choice of round, back to back
+    (about 18 MB as float32).  The seeds are fixed, so the same arguments
+    dump the same streams."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n = len(comp.lens)
+    rng = np.random.default_rng(20240601)
+    if n <= DUMP_MAX_STREAMS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(rng.choice(n, DUMP_MAX_STREAMS, replace=False))
+    cl = comp_lens.cpu().numpy()
+    bl = back_lens.cpu().numpy()
+
+    def records(errs):
+        rec = np.frombuffer(errs.cpu().numpy().tobytes(), dtype=np.dtype(
+            [("kind", "<i4"), ("r", "<u4"), ("a", "<u8"), ("b", "<u8"),
+             ("c", "<u8")]))[idx]
+        return np.stack([rec[f].astype(np.float64)
+                         for f in ("kind", "a", "b", "c")], axis=1)
+
+    rounds = n // n_files
+    picks = (rng.integers(0, rounds, n_files) * n_files
+             + np.arange(n_files)).astype(np.int64)
+    arrays = {
+        "stream_index": idx.astype(np.float64),
+        "compressed_len": cl[idx].astype(np.float64),
+        "decompressed_len": bl[idx].astype(np.float64),
+        "compress_error": records(comp_errs),
+        "decompress_error": records(back_errs),
+        "bytes_stream_index": picks.astype(np.float64),
+        "compressed_bytes": np.frombuffer(b"".join(
+            comp.stream_bytes(i, cl[i]) for i in picks),
+            dtype=np.uint8).astype(np.float32),
+        "decompressed_bytes": np.frombuffer(b"".join(
+            back.stream_bytes(i, bl[i]) for i in picks),
+            dtype=np.uint8).astype(np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes over 64 MiB"
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {"bytes": total, "streams": int(idx.size),
+            "byte_streams": int(picks.size)}
 
 
 def usable_cores():
@@ -495,7 +553,14 @@ def main():
     ap.add_argument("--plumbing-check", action="store_true",
                     help="no GPU work: only the --gpus N launch plumbing over "
                          "gloo (what tests/test_bench_spawn_cpu.py runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "computed (lengths, error records, a seeded sample "
+                         "of the compressed and decompressed bytes) as "
+                         "DIR/<name>.npy, 64 MiB at most (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     spawned = maybe_spawn(args)
     if spawned is not None:
@@ -719,6 +784,12 @@ def main():
                 assert bool((per[r, o:o + m] == d_round[o:o + m]).all()), \
                     f"after the timed steps: round trip of stream {j}"
         verified_after = True
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, comp, comp_lens, comp_errs,
+                              back, back_lens, back_errs, len(rnd))
+        log(f"[bench] outputs of the last timed step in "
+            f"{args.dump_outputs}: {dumped}")
     context_holds = None
     if rank == 0:
         placement_log = ctx.table_probe_log()
@@ -924,6 +995,8 @@ def main():
         line["ranks_seen"] = sorted(ranks_seen)
         line["devices_seen"] = len(set(devices_seen))
         line["verified_after_timed_steps"] = verified_after
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if coll_error is not None:
             line["error"] = coll_error
         if extras is not None:

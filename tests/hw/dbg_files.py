@@ -1,5 +1,7 @@
+import os
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sys, json, traceback
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, 'tests'))
 import torch, numpy as np
 import bench_configs as B
 import oracle_lib as O

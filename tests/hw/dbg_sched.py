@@ -1,7 +1,9 @@
 """The window kernel with its scheduler forced (span_schedule 2) on a small and
 a mid-size batch, against the oracle; prints as it goes (a hang shows where)."""
+import os
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sys, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, 'tests'))
 import torch, numpy as np
 import oracle_lib as O
 from rust_snappy_amd import raw, batch

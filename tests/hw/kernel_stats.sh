@@ -3,7 +3,7 @@
 # rocprofv3 --kernel-trace --stats of one extras config; the per-kernel table
 # goes to gpurun_out/<tag>_kernel_stats.md (profiles/db_stats.py)
 tag=$1; plan=$2
-R=/root/repo
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 out=$R/gpurun_out/prof_$tag
 rm -rf $out

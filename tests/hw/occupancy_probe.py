@@ -1,7 +1,9 @@
 """Experiment: how many k_compress_blocks workgroups (32 KiB LDS each) are
 resident per CU?  Identical blocks; time vs grid size shows the step."""
+import os
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, 'tests'))
 import oracle_lib as O
 import rust_snappy_amd as R
 from rust_snappy_amd import batch

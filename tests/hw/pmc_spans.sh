@@ -1,11 +1,11 @@
 #!/bin/bash
 # SQ counters of k_compress_spans on alice29.txt tiled to 0.25 GiB (4096
 # blocks of ~1148 steps): one rocprofv3 --pmc pass per group, per-kernel sums
-R=$PWD
+export R=$PWD
 cd /tmp && export TMPDIR=/tmp
 cat > /tmp/spans_one.py <<'PY'
-import sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys
+sys.path.insert(0, os.environ["R"]); sys.path.insert(0, os.path.join(os.environ["R"], "tests"))
 import torch
 import bench_configs as B, oracle_lib as O
 from rust_snappy_amd import raw

@@ -1,7 +1,8 @@
 """Experiment: per-phase cycle split of k_decompress_streams (profile build)."""
 import ctypes as C, os, sys
-os.environ["SNAPMI_LIB"] = "/root/repo/rust-snappy_amd/libsnapmi_profile.so"
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ["SNAPMI_LIB"] = os.path.join(_R, "rust-snappy_amd", "libsnapmi_profile.so")
+sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, 'tests'))
 import numpy as np, torch
 import oracle_lib as O
 import rust_snappy_amd as R

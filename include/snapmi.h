@@ -154,13 +154,6 @@ SNAPMI_API const char *snapmi_version(void);
  *                          lane-per-block kernel on large batches (default)
  *                          [2, both at once, is a cross-check of the test
  *                          build: snapmi_test.h]
- *   "window_tokens"        1: a batch of more than two blocks per CU and
- *                          fewer than lane_min_blocks runs the window kernel
- *                          as a match finder and encodes with a wide kernel
- *                          of its own (128 KiB of token scratch per block of
- *                          the batch, at most 1 GiB); 0 (default): the window
- *                          kernel encodes while it matches (no scratch but
- *                          the block slots) - the two measure within 3 %
  *   "small_table_kernel"   1 (default): blocks of at most 8 KiB - pages,
  *                          short frame chunks, tails - are matched by a
  *                          window kernel with the 16 KiB table the reference

@@ -15,7 +15,7 @@
  * Environment: a process that sets SNAPMI_TESTING=1 may also steer a new
  * context with SNAPMI_LANE_WAVES, SNAPMI_LANE_SEGMENT_BLOCKS,
  * SNAPMI_LANE_TABLE_SPREAD, SNAPMI_LANE_MIN_BLOCKS, SNAPMI_FRAME_CRC_SIDE,
- * SNAPMI_LANE_UNCACHED, SNAPMI_LANE_DIRECT, SNAPMI_HOST_COPY_KERNEL,
+ * SNAPMI_LANE_UNCACHED, SNAPMI_HOST_COPY_KERNEL,
  * SNAPMI_HOST_ENCODE_SLICE, SNAPMI_HOST_DECODE_CHUNKS, SNAPMI_DECODE_KERNEL,
  * SNAPMI_COMPRESS (the experiment scripts under tests/hw/ do).  Without
  * SNAPMI_TESTING they are ignored.
@@ -35,9 +35,6 @@ extern "C" {
  *                          a small batch puts several blocks on one lane
  *   "lane_tables_uncached" 1: the lane tables come from an uncached
  *                          allocation (measured: no gain; default 0)
- *   "lane_direct_encode"   1 (default): the lane kernel's encoder writes every
- *                          block at its final position; 0: scratch slot per
- *                          block + a compaction pass
  *   "lane_overlap_encode"  0 (default) never; 1: a lane-kernel segment with
  *                          at least 1.4 blocks per lane is matched in two
  *                          halves, the first half's tokens encoded on a side

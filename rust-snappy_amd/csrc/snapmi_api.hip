@@ -25,6 +25,7 @@
 #include "snapmi_test.h"
 #include "snapmi_ctx.hpp"
 #include "snapmi_pool.hpp"
+#include "snapmi_route.hpp"
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
 
@@ -166,8 +167,6 @@ int snapmi_ctx_create(int device, void *hip_stream, snapmi_ctx **out)
             ctx->frame_crc_side_stream = atoi(e) != 0;
         if (const char *e = getenv("SNAPMI_LANE_UNCACHED"))
             ctx->lane_tables_uncached = atoi(e) != 0;
-        if (const char *e = getenv("SNAPMI_LANE_DIRECT"))
-            ctx->lane_direct_encode = atoi(e) != 0;
         if (const char *e = getenv("SNAPMI_HOST_COPY_KERNEL"))
             ctx->host_copy_kernel = atoi(e) & 3;
         if (const char *e = getenv("SNAPMI_HOST_ENCODE_SLICE"))
@@ -344,8 +343,6 @@ int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
     else if (strcmp(name, "lane_table_budget_pct") == 0 && value >= 1 &&
              value <= 90)
         ctx->lane_table_budget_pct = (uint32_t)value;
-    else if (strcmp(name, "window_tokens") == 0 && value >= 0 && value <= 1)
-        ctx->window_tokens = (int)value;
     else if (strcmp(name, "token_pool_pct") == 0 && value >= 1 &&
              value <= 100) {
         ctx->token_pool_pct = (uint32_t)value;
@@ -430,9 +427,6 @@ int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
     else if (strcmp(name, "lane_tables_uncached") == 0 && value >= 0 &&
              value <= 1)
         ctx->lane_tables_uncached = (int)value;
-    else if (strcmp(name, "lane_direct_encode") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->lane_direct_encode = (int)value;
     else if (strcmp(name, "lane_overlap_encode") == 0 && value >= 0 &&
              value <= 2)
         ctx->lane_overlap_encode = (int)value;
@@ -660,19 +654,41 @@ int snapmi_decompress_len(const uint8_t *input, size_t input_len,
 
 } // extern "C"
 namespace snapmi {
-// streams shorter than this are compressed by the lane-per-stream kernels
-// (k_compress_tiny under 256 bytes, k_compress_small under 1 KiB - under
-// 2 KiB with small_stream_kernel = 2) and get no blocks; 0: every stream goes
-// through the block kernels
 int prepare_lane_tables(snapmi_ctx *ctx, uint64_t blocks, bool top);
-static uint64_t small_stream_limit(const snapmi_ctx *ctx)
+static_assert(kRouteCompressWaves == kCompressWaves &&
+                  kRouteSmallTableWaves == kSmallTableWaves &&
+                  kRouteBothWaves == kBothWaves &&
+                  kRouteBothLaneWaves == kBothLaneWaves &&
+                  kRouteTinyCompress == kTinyCompress &&
+                  kRouteSmallCompress == kSmallCompress,
+              "snapmi_route.hpp and snapmi_kernels.hpp disagree");
+
+// (snapmi_route.hpp: the options it reads)
+static RouteOptions route_options(const snapmi_ctx *ctx)
 {
-    if (!ctx->tiny_stream_kernel)
-        return 0;
-    return ctx->small_stream_kernel == 2
-               ? kSmallCompress
-               : (ctx->small_stream_kernel ? kSmallCompress / 2
-                                           : kTinyCompress);
+    RouteOptions o;
+    o.compress_mode = ctx->compress_mode;
+    o.lds_order_ok = ctx->lds_order_ok;
+    o.num_cus = (uint32_t)ctx->num_cus;
+    o.lane_min_blocks = ctx->lane_min_blocks;
+    o.lane_segment_blocks = ctx->lane_segment_blocks;
+    o.lane_waves_per_cu = ctx->lane_waves_per_cu;
+    o.lane_max_waves = ctx->lane_max_waves;
+    o.lane_coresident = ctx->lane_coresident;
+    o.lane_coresident_min_blocks = ctx->lane_coresident_min_blocks;
+    o.small_table_kernel = ctx->small_table_kernel;
+    o.small_table_min_blocks = ctx->small_table_min_blocks;
+    o.small_batch_kernel = ctx->small_batch_kernel;
+    o.span_kernel = ctx->span_kernel;
+    o.span_schedule = ctx->span_schedule;
+    o.both_wave_cus = ctx->both_wave_cus;
+    o.match_kernel = ctx->match_kernel;
+    o.lane_speculate = ctx->lane_speculate;
+    o.lane_speculate_max_blocks = ctx->lane_speculate_max_blocks;
+    o.lane_overlap_encode = ctx->lane_overlap_encode;
+    o.tiny_stream_kernel = ctx->tiny_stream_kernel;
+    o.small_stream_kernel = ctx->small_stream_kernel;
+    return o;
 }
 } // namespace snapmi
 extern "C" {
@@ -706,7 +722,7 @@ int snapmi_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     }
     uint64_t blocks = 0, slots = 0, cnt8 = 0, block_bytes = 0;
     // streams under this length are the lane-per-stream kernels': no block
-    const uint64_t small = small_stream_limit(ctx);
+    const uint64_t small = small_stream_limit(route_options(ctx));
     uint32_t classes = 0; // which of those kernels have anything to do
     for (size_t i = 0; i < n; i++) {
         const uint64_t len = h_in_lens[i];
@@ -824,34 +840,11 @@ constexpr size_t kPlanOneWg = 16384;
 // call, ten times over - 72 s for a context's first 4 GiB batch,
 // profiles/r6_sweep_repro_head.txt).  That is why it is a call of its own.
 // ---------------------------------------------------------------------
-// (snapmi_pool.hpp: equal launches of at most lane_segment_blocks blocks)
-static uint64_t segment_blocks(const snapmi_ctx *ctx, uint64_t blocks)
-{
-    return snapmi::segment_blocks(blocks, ctx->lane_segment_blocks);
-}
 static_assert(snapmi::kPoolTokPage == kTokPage &&
                   snapmi::kPoolExcPage == kExcPage &&
                   snapmi::kPoolPagesPerBlock ==
                       kTokPagesPerBlock + kExcPagesPerBlock,
               "snapmi_pool.hpp and snapmi_kernels.hpp disagree");
-
-static uint32_t lane_count(const snapmi_ctx *ctx, uint64_t seg_blocks,
-                           bool both_cores)
-{
-    // waves of the lane-per-block match finder: a few per CU saturate the
-    // random-access rate of HBM; never more lanes than blocks
-    uint64_t waves = (uint64_t)ctx->num_cus * ctx->lane_waves_per_cu;
-    const uint64_t need = (seg_blocks + 63) / 64;
-    if (waves > need)
-        waves = need ? need : 1;
-    if (ctx->lane_max_waves && waves > ctx->lane_max_waves)
-        waves = ctx->lane_max_waves;
-    // k_match_both: its lane wavefronts on every CU, beside two of the
-    // window kernel
-    if (both_cores)
-        waves = (uint64_t)ctx->num_cus * kBothLaneWaves;
-    return (uint32_t)waves * 64;
-}
 
 static int place_lane_tables(snapmi_ctx *ctx, uint32_t lanes,
                              bool top_of_memory)
@@ -1165,19 +1158,15 @@ static int place_lane_tables(snapmi_ctx *ctx, uint32_t lanes,
 
 
 // snapmi_ctx_prepare: the tables a batch of `blocks` blocks would make the
-// first compress call allocate, now (the same lane count launch_compress
-// derives); nothing when such a batch does not run the lane kernel or the
-// context already has that many tables - unless the far end of the memory is
-// asked for and the tables are not there yet.
+// first compress call allocate, now (prepare_lanes, snapmi_route.hpp);
+// nothing when such a batch does not run the lane kernel or the context
+// already has that many tables - unless the far end of the memory is asked
+// for and the tables are not there yet.
 int prepare_lane_tables(snapmi_ctx *ctx, uint64_t blocks, bool top)
 {
-    if (ctx->compress_mode == 0 || blocks < ctx->lane_min_blocks)
+    const uint32_t lanes = prepare_lanes(route_options(ctx), blocks);
+    if (!lanes)
         return SNAPMI_OK;
-    const uint64_t seg_blocks = segment_blocks(ctx, blocks);
-    const bool both = ctx->compress_mode == 1 && ctx->lds_order_ok &&
-                      ctx->lane_coresident &&
-                      blocks >= ctx->lane_coresident_min_blocks;
-    const uint32_t lanes = lane_count(ctx, seg_blocks, both);
     if (lanes <= ctx->n_lanes && !(top && !ctx->lane_tables_top))
         return SNAPMI_OK;
     const int rc = place_lane_tables(ctx, lanes > ctx->n_lanes ? lanes
@@ -1206,6 +1195,74 @@ static void launch_scan_sizes(const CompressArgs &a, hipStream_t s)
     }
 }
 
+// match_kernel 2's hint: the latest batch that has finished (a slot reads 0
+// in word 4 while a kernel is writing it) compressed to no less than
+// match_spans_ratio_pct of its input
+static bool spans_hint(const snapmi_ctx *ctx)
+{
+    if (ctx->match_kernel != 2 || !ctx->h_ratio)
+        return false;
+    const volatile uint32_t *r = ctx->h_ratio;
+    const uint32_t s0 = r[4], s1 = r[12];
+    const volatile uint32_t *slot = s1 > s0 ? r + 8 : r;
+    const uint32_t seq = slot[4];
+    const uint64_t c = ((uint64_t)slot[1] << 32) | slot[0];
+    const uint64_t u = ((uint64_t)slot[3] << 32) | slot[2];
+    return seq && slot[4] == seq && u &&
+           c * 100 >= u * ctx->match_spans_ratio_pct;
+}
+
+// the route's window kernel over the whole batch, on stream ws
+static void launch_window(const CompressRoute &route, const CompressArgs &a,
+                          hipStream_t ws)
+{
+    const dim3 grid(route.window_grid);
+    switch (route.window) {
+    case WindowKernel::spans:
+        hipLaunchKernelGGL(k_compress_spans, grid, dim3(kCompressWaves * 64),
+                           0, ws, a);
+        break;
+    case WindowKernel::span_lds:
+        hipLaunchKernelGGL(k_compress_span_lds, grid, dim3(64), 0, ws, a);
+        break;
+#ifdef SNAPMI_TESTING // (span_kernel 0: the product refuses it)
+    case WindowKernel::blocks:
+        hipLaunchKernelGGL(k_compress_blocks, grid, dim3(kCompressWaves * 64),
+                           0, ws, a);
+        break;
+    case WindowKernel::block_lds:
+        hipLaunchKernelGGL(k_compress_block_lds, grid, dim3(64), 0, ws, a);
+        break;
+#endif
+    default:
+        break;
+    }
+}
+
+// the route's match finder over the blocks [a.blk_lo, a.blk_hi) of segment g
+static void launch_match(const RouteOptions &o, const CompressRoute &route,
+                         const Segment &g, CompressArgs a, hipStream_t s)
+{
+    const dim3 grid(match_grid(o, route, a.blk_hi - a.blk_lo));
+    switch (route.match) {
+    case MatchKernel::spans:
+        hipLaunchKernelGGL(k_match_spans, grid, dim3(kCompressWaves * 64), 0,
+                           s, a);
+        break;
+    case MatchKernel::both:
+        a.tok_stage_wave0 = kBothLaneWaves;
+        hipLaunchKernelGGL(k_match_both, grid, dim3(kBothWaves * 64), 0, s,
+                           a);
+        break;
+    case MatchKernel::blocks:
+        hipLaunchKernelGGL(g.spec ? k_match_blocks_spec : k_match_blocks, grid,
+                           dim3(64), 0, s, a);
+        break;
+    case MatchKernel::none:
+        break;
+    }
+}
+
 int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                     const uint64_t *d_in_lens, void *const *d_out_ptrs,
                     const uint64_t *d_out_caps, uint64_t *d_out_lens,
@@ -1228,6 +1285,10 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                       ((n > blocks ? n : blocks) / 1024 + 4) * 16)) ||
         (rc = reserve(ctx, ctx->ticket, 64)))
         return rc;
+
+    // which kernels the batch runs (snapmi_route.hpp)
+    const RouteOptions o = route_options(ctx);
+    const CompressRoute route = compress_route(o, blocks, cnt8, spans_hint(ctx));
 
     CompressArgs a;
     a.in_ptrs = d_in_ptrs;
@@ -1263,97 +1324,23 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     a.lane_per_chunk = 0;
     a.n_lanes = 0;
     a.tok_base = 0;
-    a.small_limit = (uint32_t)small_stream_limit(ctx);
+    a.small_limit = (uint32_t)small_stream_limit(o);
     a.cls_lo = 0;
     a.cls_hi = kMaxBlock;
-    // Small batches are latency-bound: the wavefront kernel finishes a block
-    // in ~2 ms, a lane needs tens of ms.  Large batches are throughput-bound
-    // and go to the lane-per-block kernel.
-    // Blocks of at most 8 KiB (cnt8 of them: the caller counted one-block
-    // streams and tails): a window kernel with the table the reference gives
-    // such blocks, ten per CU instead of five (k_match_spans_8k), whatever
-    // the size of the batch - every probe of the lane kernel into a block's
-    // fresh table is an HBM transaction, and the 64 KiB window kernel keeps a
-    // CU's issue slots four fifths idle.  (Twenty tables of 8 KiB per CU for
-    // blocks of at most 4 KiB were built too and measured the same: at ten
-    // wavefronts the CU's one scalar unit is 70 % busy.)
-    const uint64_t nb_small = cnt8 < blocks ? cnt8 : blocks;
-    const bool use_small = blocks > 0 && ctx->lds_order_ok &&
-                           ctx->compress_mode == 1 &&
-                           ctx->small_table_kernel &&
-                           nb_small >= ctx->small_table_min_blocks;
-    const uint64_t nb_big = use_small ? blocks - nb_small : blocks;
-    const bool big = nb_big >= ctx->lane_min_blocks;
-    // (a device that failed the LDS order self-check only has the lane kernel)
-    // The token path with the WINDOW kernel as its match finder
-    // (k_match_spans): every block at its final position, no slots, no
-    // k_compact, the encoder a wide kernel of its own.  What the small-block
-    // kernel runs on, and - option window_tokens - a mid-size batch (more
-    // than two blocks per CU, fewer than lane_min_blocks).
-    const bool win_tok =
-        blocks > 0 && ctx->lds_order_ok && ctx->compress_mode == 1 && !big &&
-        (use_small ||
-         (ctx->window_tokens &&
-          !(ctx->small_batch_kernel == 2 ||
-            (ctx->small_batch_kernel == 1 &&
-             blocks <= 2 * (uint64_t)ctx->num_cus))));
-    const bool lanes_mode =
-        blocks > 0 &&
-        (!ctx->lds_order_ok || (ctx->compress_mode != 0 && big) || win_tok);
-    // (segment_blocks: equal launches that bound the token scratch; "both at
-    // once" needs the whole list in one segment)
-    const uint64_t seg_blocks = segment_blocks(ctx, blocks);
-    const bool waves_mode =
-        blocks > 0 && ctx->lds_order_ok &&
-        (!lanes_mode || ctx->compress_mode == 0 ||
-         (ctx->compress_mode == 2 && seg_blocks == blocks));
-    // The lane kernel knows every block's encoded size before a byte of it
-    // is written, so its encoder puts the blocks where they belong; only the
-    // wavefront kernel (which encodes while it matches) needs a scratch slot
-    // per block and the k_compact pass.
-    const bool direct = lanes_mode && !waves_mode && ctx->lane_direct_encode &&
-                        ctx->lane_overlap_encode == 0;
-    a.direct = direct ? 1 : 0;
-    if (!direct &&
+    a.direct = route.direct ? 1 : 0;
+    if (!route.direct &&
         (rc = reserve(ctx, ctx->slots, (slots + 1) * (size_t)kSlotBytes)))
         return rc;
     a.scratch = (uint8_t *)ctx->slots.p;
     a.blk_lo = 0;
     a.blk_hi = (uint32_t)blocks;
-    // The token path's match finder: the lane kernel, or - option
-    // match_kernel - the window kernel (k_match_spans: table in LDS, no
-    // tables in HBM).  By default the context's last batch decides: data that
-    // does not compress costs a lane three HBM transactions per probe for
-    // nothing (cfg5: 12 ms of lane kernel for 32 GiB against ~4 of windows).
-    bool span_match = false;
-    if (lanes_mode && !waves_mode && ctx->lds_order_ok) {
-        if (ctx->match_kernel == 1 || win_tok) {
-            span_match = true;
-        } else if (ctx->match_kernel == 2 && ctx->h_ratio) {
-            // the slot of the latest batch that has finished (a slot reads
-            // 0 in word 4 while a kernel is writing it)
-            const volatile uint32_t *r = ctx->h_ratio;
-            const uint32_t s0 = r[4], s1 = r[12];
-            const volatile uint32_t *slot = s1 > s0 ? r + 8 : r;
-            const uint32_t seq = slot[4];
-            const uint64_t c = ((uint64_t)slot[1] << 32) | slot[0];
-            const uint64_t u = ((uint64_t)slot[3] << 32) | slot[2];
-            span_match = seq && slot[4] == seq && u &&
-                         c * 100 >= u * ctx->match_spans_ratio_pct;
-        }
-    }
-    // both match finders on every CU (k_match_both): launches that fill the
-    // chip with lanes anyway
-    const bool both_cores = lanes_mode && !waves_mode && !span_match &&
-                            ctx->lds_order_ok && ctx->lane_coresident &&
-                            nb_big >= ctx->lane_coresident_min_blocks;
     // The token pool (CompressArgs::tok_pool): pages of 2 KiB for the tokens
     // of a launch's blocks - token_pool_pct per cent of what the worst case
     // of every block would take, and what the launch keeps in hand on top;
     // never fewer than 32 768 pages (64 MiB: a small batch does not spill);
     // grown for the batch behind one of which more than a hundredth spilled
     // - by half, or by a sixth when it was less than a tenth (k_redo_spilled
-    // posts the counts; read without waiting, like the ratio above).
+    // posts the counts; read without waiting, like the ratio hint).
     if (ctx->h_tokstat) {
         const volatile uint32_t *t = ctx->h_tokstat;
         const uint32_t seq = t[3];
@@ -1372,47 +1359,25 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         ctx->token_pool_now = ctx->token_pool_pct;
     // (snapmi_pool.hpp: the share of the worst case, what the launch keeps in
     // hand, the floor, and "100 means never")
-    const uint32_t pool_lanes =
-        lanes_mode && !span_match ? lane_count(ctx, seg_blocks, both_cores)
-                                  : 0;
     const uint64_t pool_pages =
-        snapmi::pool_pages(block_bytes, blocks, seg_blocks, pool_lanes,
+        snapmi::pool_pages(block_bytes, blocks, route.seg_blocks, route.lanes,
                            ctx->token_pool_now, ctx->token_pool_min_pages);
     // (+ the dump page of the lanes)
     const size_t pool_bytes = (size_t)(pool_pages + 1) * kTokPage * 4;
-    // the window wavefronts' staging arrays (TokenWriter): one per wavefront
-    // of the largest workgroup this call launches
-    const uint32_t stage_waves =
-        use_small ? kSmallTableWaves
-                  : both_cores ? kBothWaves - kBothLaneWaves
-                               : span_match ? kCompressWaves : 0;
     const size_t stage_bytes =
-        (size_t)ctx->num_cus * stage_waves * kTokStageWords * 4;
-    a.tok_stage_waves = stage_waves;
+        (size_t)ctx->num_cus * route.stage_waves * kTokStageWords * 4;
+    a.tok_stage_waves = route.stage_waves;
     a.tok_stage_wave0 = 0;
     // ... and behind its control words and the list of the spilled blocks,
     // the blocks' page tables
     const size_t tab_off =
-        ((size_t)(kTokCtlList + seg_blocks) * 4 + 255) & ~(size_t)255;
+        ((size_t)(kTokCtlList + route.seg_blocks) * 4 + 255) & ~(size_t)255;
     const size_t tab_bytes =
-        tab_off + (size_t)seg_blocks * kPageTabStride * 4;
-    if (lanes_mode && span_match) {
-        if ((rc = reserve(ctx, ctx->tokens, pool_bytes, /*slack=*/false)) ||
-            (rc = reserve(ctx, ctx->tok_pages, tab_bytes)) ||
-            (rc = reserve(ctx, ctx->tok_stage, stage_bytes + 256)) ||
-            (rc = reserve(ctx, ctx->ntok, (size_t)blocks * sizeof(uint32_t))))
-            return rc;
-        a.tok_pool = (uint32_t *)ctx->tokens.p;
-        a.tok_ctl = (uint32_t *)ctx->tok_pages.p;
-        a.tok_pages = (uint32_t *)((uint8_t *)ctx->tok_pages.p + tab_off);
-        a.tok_pool_pages = (uint32_t)pool_pages;
-        a.tok_stage = (uint32_t *)ctx->tok_stage.p;
-        ctx->tok_pool_pages_last = (uint32_t)pool_pages;
-        a.ntok = (uint32_t *)ctx->ntok.p;
-    } else if (lanes_mode) {
-        const uint32_t lanes = lane_count(ctx, seg_blocks, both_cores);
-        if (lanes > ctx->n_lanes) {
-            if ((rc = place_lane_tables(ctx, lanes, /*top_of_memory=*/false)))
+        tab_off + (size_t)route.seg_blocks * kPageTabStride * 4;
+    if (route.tokens) {
+        if (route.lanes > ctx->n_lanes) {
+            if ((rc = place_lane_tables(ctx, route.lanes,
+                                        /*top_of_memory=*/false)))
                 return rc;
             ctx->lane_tables_top = false;
         }
@@ -1421,7 +1386,8 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
             (rc = reserve(ctx, ctx->tok_stage, stage_bytes + 256)) ||
             (rc = reserve(ctx, ctx->ntok, (size_t)blocks * sizeof(uint32_t))))
             return rc;
-        if (ctx->lane_epoch_preset >= 0) { // test knob, see snapmi_ctx.hpp
+        // test knob, see snapmi_ctx.hpp
+        if (route.lanes && ctx->lane_epoch_preset >= 0) {
             HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->lane_epochs.p,
                                            (int)ctx->lane_epoch_preset,
                                            ctx->n_lanes, ctx->stream));
@@ -1434,12 +1400,14 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         a.tok_stage = (uint32_t *)ctx->tok_stage.p;
         ctx->tok_pool_pages_last = (uint32_t)pool_pages;
         a.ntok = (uint32_t *)ctx->ntok.p;
-        a.lane_tables = (unsigned long long *)ctx->lane_tables.p;
-        a.lane_epochs = (uint32_t *)ctx->lane_epochs.p;
-        a.lane_stride = ctx->lane_stride;
-        a.lane_chunks = ctx->lane_chunk_count;
-        a.lane_per_chunk = ctx->lane_per_chunk;
-        a.n_lanes = lanes;
+        if (route.lanes) {
+            a.lane_tables = (unsigned long long *)ctx->lane_tables.p;
+            a.lane_epochs = (uint32_t *)ctx->lane_epochs.p;
+            a.lane_stride = ctx->lane_stride;
+            a.lane_chunks = ctx->lane_chunk_count;
+            a.lane_per_chunk = ctx->lane_per_chunk;
+            a.n_lanes = route.lanes;
+        }
     }
     a.prof = nullptr;
     PROF(
@@ -1484,231 +1452,110 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                                    a);
         }
     }
-    if (blocks) {
-        hipStream_t ws = s; // stream of the wavefront kernel
-        if (waves_mode) {
-            HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
-            if (lanes_mode) {
+    if (route.window != WindowKernel::none) {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
+        hipStream_t ws = s; // stream of the window kernel
+        if (route.window_beside) {
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+            ws = ctx->stream2;
+        }
+        if (route.sched) {
+            const size_t head = (size_t)(16 + n) * 4;
+            const size_t lists = (size_t)2 * (slots + 1) * 4;
+            if ((rc = reserve(ctx, ctx->sched, head + lists)))
+                return rc;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->sched.p, 0, head, ws));
+            HIP_TRY(ctx, hipMemsetAsync((uint8_t *)ctx->sched.p + head, 0xFF,
+                                        lists, ws));
+            a.sched = (uint32_t *)ctx->sched.p;
+        }
+        launch_window(route, a, ws);
+        a.sched = nullptr;
+    }
+    if (route.tokens) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev[4], s));
+        for (uint64_t lo = 0; lo < blocks; lo += route.seg_blocks) {
+            const uint64_t hi = lo + route.seg_blocks < blocks
+                                    ? lo + route.seg_blocks
+                                    : blocks;
+            const Segment g = segment(o, route, lo, hi);
+            a.tok_base = (uint32_t)lo;
+            a.blk_lo = (uint32_t)lo;
+            a.blk_hi = (uint32_t)g.mid;
+            // the pool is the segment's: no page handed out, no block
+            // spilled, k_redo_spilled's ticket at 0
+            HIP_TRY(ctx, hipMemsetAsync(ctx->tok_pages.p, 0,
+                                        kTokCtlList * 4, s));
+            if (route.window == WindowKernel::none) // (else shared with it)
+                HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
+            // (with the small-block kernels on, this launch's class is the
+            // blocks of more than 8 KiB - if the batch has any)
+            a.cls_lo = route.small_grid ? 8192 : 0;
+            launch_match(o, route, g, a, s);
+            if (route.small_grid) {
+                HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
+                a.cls_lo = 0;
+                a.cls_hi = 8192;
+                hipLaunchKernelGGL(k_match_spans_8k, dim3(route.small_grid),
+                                   dim3(kSmallTableWaves * 64), 0, s, a);
+            }
+            a.cls_lo = 0;
+            a.cls_hi = kMaxBlock;
+            if (g.mid < hi) {
                 HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
                 HIP_TRY(ctx,
                         hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                ws = ctx->stream2;
-            }
-            // persistent: one 5-wave workgroup per CU (all of its LDS), each
-            // wavefront pulls blocks from the back of the ticket
-            // the smallest batches (no more than two blocks per CU: scalar
-            // calls, short frames) run one block per CU with the input block
-            // in LDS too - half the time per block, a fifth of the blocks in
-            // flight; five tables per CU from there
-            const bool lds_input =
-                ctx->small_batch_kernel == 2 ||
-                (ctx->small_batch_kernel == 1 &&
-                 blocks <= 2 * (uint64_t)ctx->num_cus);
-            if (lds_input) {
-                const uint32_t wgs = (uint32_t)(
-                    blocks < (uint64_t)ctx->num_cus ? blocks : ctx->num_cus);
-#ifdef SNAPMI_TESTING
-                hipLaunchKernelGGL(ctx->span_kernel ? k_compress_span_lds
-                                                    : k_compress_block_lds,
-                                   dim3(wgs), dim3(64), 0, ws, a);
-#else
-                hipLaunchKernelGGL(k_compress_span_lds, dim3(wgs), dim3(64),
-                                   0, ws, a);
-#endif
-            } else {
-                const uint64_t want =
-                    (blocks + kCompressWaves - 1) / kCompressWaves;
-                // (beside the lane kernel it takes a share of the CUs only:
-                // a persistent workgroup owns its CU's whole LDS)
-                const uint64_t cus =
-                    lanes_mode ? (ctx->both_wave_cus ? ctx->both_wave_cus
-                                                     : ctx->num_cus / 2)
-                               : (uint64_t)ctx->num_cus;
-                const uint32_t wgs = (uint32_t)(want < cus ? want : cus);
-                // several blocks per wavefront, the window kernel alone:
-                // the order of the blocks is chosen as the launch goes
-                // (SpanSched, snapmi_compress.hip: heavy streams first,
-                // light ones last - a launch ends with its small jobs)
-                bool sched = !lanes_mode && ctx->span_kernel &&
-                             (ctx->span_schedule == 2 ||
-                              (ctx->span_schedule == 1 &&
-                               blocks > (uint64_t)wgs * kCompressWaves));
-                if (sched) {
-                    const size_t head = (size_t)(16 + n) * 4;
-                    const size_t lists = (size_t)2 * (slots + 1) * 4;
-                    if ((rc = reserve(ctx, ctx->sched, head + lists)))
-                        return rc;
-                    HIP_TRY(ctx, hipMemsetAsync(ctx->sched.p, 0, head, ws));
-                    HIP_TRY(ctx, hipMemsetAsync((uint8_t *)ctx->sched.p + head,
-                                                0xFF, lists, ws));
-                    a.sched = (uint32_t *)ctx->sched.p;
-                }
-#ifdef SNAPMI_TESTING
-                hipLaunchKernelGGL(ctx->span_kernel ? k_compress_spans
-                                                    : k_compress_blocks,
-                                   dim3(wgs), dim3(kCompressWaves * 64), 0, ws,
-                                   a);
-#else
-                hipLaunchKernelGGL(k_compress_spans, dim3(wgs),
-                                   dim3(kCompressWaves * 64), 0, ws, a);
-#endif
-                a.sched = nullptr;
-            }
-        }
-        if (lanes_mode) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev[4], s));
-            for (uint64_t lo = 0; lo < blocks; lo += seg_blocks) {
-                const uint64_t hi =
-                    lo + seg_blocks < blocks ? lo + seg_blocks : blocks;
-                // Option lane_overlap_encode (off by default): the segment is
-                // matched in two halves and the first half's tokens are
-                // encoded on the side stream while the second half is
-                // matched.  Two halves alone cost the match finder nothing
-                // (114.2 vs 115 ms), but the encoder's streaming traffic under
-                // it does: 121.6 -> 135 ms at cfg2.  Kept as a measured dead
-                // end that the encoder tests still run through.
-                uint64_t mid = hi;
-                if (!waves_mode && !use_small &&
-                    (ctx->lane_overlap_encode == 2
-                         ? hi - lo >= 2
-                         : (ctx->lane_overlap_encode == 1 &&
-                            (hi - lo) * 10 >= (uint64_t)a.n_lanes * 14)))
-                    mid = lo + (hi - lo) / 2;
-                a.tok_base = (uint32_t)lo;
-                a.blk_lo = (uint32_t)lo;
-                a.blk_hi = (uint32_t)mid;
-                // the pool is the segment's: no page handed out, no block
-                // spilled, k_redo_spilled's ticket at 0
-                HIP_TRY(ctx, hipMemsetAsync(ctx->tok_pages.p, 0,
-                                            kTokCtlList * 4, s));
-                if (!waves_mode) // (shared with the wavefront kernel if on)
-                    HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
-                // A launch of few blocks waits for the latency of its
-                // rounds with the memory system idle: the kernel that also
-                // fetches the next probe's entry (k_match_blocks_spec) takes
-                // 10-15 % off 2 048 .. 16 384 blocks of text.  From 32 768
-                // blocks on the launch is at the random-access rate of HBM
-                // even with one block per lane (1.6e10 rounds a second, as at
-                // 146 700 blocks) and the extra reads buy nothing
-                // (profiles/r3_lane_speculation.txt).
-                const bool spec = ctx->lane_speculate &&
-                                  hi - lo <= a.n_lanes &&
-                                  hi - lo <= ctx->lane_speculate_max_blocks;
-                // (with the small-block kernels on, this launch's class is
-                // the blocks of more than 8 KiB - if the batch has any)
-                a.cls_lo = use_small ? 8192 : 0;
-                if (use_small && nb_big == 0) {
-                } else if (span_match) {
-                    const uint64_t mine =
-                        use_small && nb_big < mid - lo ? nb_big : mid - lo;
-                    const uint64_t want =
-                        (mine + kCompressWaves - 1) / kCompressWaves;
-                    hipLaunchKernelGGL(
-                        k_match_spans,
-                        dim3((uint32_t)(want < (uint64_t)ctx->num_cus
-                                            ? want : ctx->num_cus)),
-                        dim3(kCompressWaves * 64), 0, s, a);
-                } else if (both_cores) {
-                    a.tok_stage_wave0 = kBothLaneWaves;
-                    hipLaunchKernelGGL(k_match_both, dim3(ctx->num_cus),
-                                       dim3(kBothWaves * 64), 0, s, a);
-                    a.tok_stage_wave0 = 0;
-                } else
-                hipLaunchKernelGGL(spec ? k_match_blocks_spec : k_match_blocks,
-                                   dim3(a.n_lanes / 64), dim3(64), 0, s, a);
-                if (use_small) {
-                    // one 640-thread workgroup per CU: ten 16 KiB tables
-                    HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
-                    a.cls_lo = 0;
-                    a.cls_hi = 8192;
-                    const uint64_t want =
-                        (nb_small + kSmallTableWaves - 1) / kSmallTableWaves;
-                    const uint64_t room = ctx->num_cus;
-                    hipLaunchKernelGGL(
-                        k_match_spans_8k,
-                        dim3((uint32_t)(want < room ? want : room)),
-                        dim3(kSmallTableWaves * 64), 0, s, a);
-                }
-                a.cls_lo = 0;
-                a.cls_hi = kMaxBlock;
-                if (mid < hi) {
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
-                    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2,
-                                                    ctx->ev_fork, 0));
-                    hipLaunchKernelGGL(k_encode_tokens,
-                                       dim3((uint32_t)(mid - lo)), dim3(64),
-                                       0, ctx->stream2, a);
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-                    a.blk_lo = (uint32_t)mid;
-                    a.blk_hi = (uint32_t)hi;
-                    HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
-                    if (span_match) {
-                        const uint64_t want =
-                            (hi - mid + kCompressWaves - 1) / kCompressWaves;
-                        hipLaunchKernelGGL(
-                            k_match_spans,
-                            dim3((uint32_t)(want < (uint64_t)ctx->num_cus
-                                                ? want : ctx->num_cus)),
-                            dim3(kCompressWaves * 64), 0, s, a);
-                    } else if (both_cores) {
-                        a.tok_stage_wave0 = kBothLaneWaves;
-                        hipLaunchKernelGGL(k_match_both, dim3(ctx->num_cus),
-                                           dim3(kBothWaves * 64), 0, s, a);
-                        a.tok_stage_wave0 = 0;
-                    } else
-                    hipLaunchKernelGGL(
-                        spec ? k_match_blocks_spec : k_match_blocks,
-                        dim3(a.n_lanes / 64), dim3(64), 0, s, a);
-                }
-                if (hi == blocks) // dominant_ms: first match start .. last end
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev[5], s));
-                if (waves_mode) {
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-                    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-                }
-                if (direct)
-                    launch_scan_sizes(a, s);
                 hipLaunchKernelGGL(k_encode_tokens,
-                                   dim3((uint32_t)(hi - a.blk_lo)), dim3(64),
-                                   0, s, a);
-                if (mid < hi) // the side stream's half is done as well
-                    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-                {
-                    // the blocks whose tokens found no page: once more, by
-                    // the window kernel, to where the encoder would have put
-                    // them (CompressArgs::tok_pool)
-                    if (!ctx->h_tokstat) {
-                        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_tokstat,
-                                                   64, hipHostMallocDefault));
-                        memset((void *)ctx->h_tokstat, 0, 64);
-                    }
-                    CompressArgs r = a;
-                    r.blk_lo = (uint32_t)lo;
-                    r.blk_hi = (uint32_t)hi;
-                    r.cls_lo = 0;
-                    r.cls_hi = kMaxBlock;
-                    const uint64_t want =
-                        (hi - lo + kCompressWaves - 1) / kCompressWaves;
-                    hipLaunchKernelGGL(
-                        k_redo_spilled,
-                        dim3((uint32_t)(want < (uint64_t)ctx->num_cus
-                                            ? want : ctx->num_cus)),
-                        dim3(kCompressWaves * 64), 0, s, r,
-                        (uint32_t *)ctx->h_tokstat, ++ctx->tokstat_seq);
-                }
+                                   dim3((uint32_t)(g.mid - lo)), dim3(64), 0,
+                                   ctx->stream2, a);
+                HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+                a.blk_lo = (uint32_t)g.mid;
+                a.blk_hi = (uint32_t)hi;
+                HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
+                launch_match(o, route, g, a, s);
             }
-            a.blk_lo = 0;
-            a.tok_base = 0;
-            a.blk_hi = (uint32_t)blocks;
+            if (hi == blocks) // dominant_ms: first match start .. last end
+                HIP_TRY(ctx, hipEventRecord(ctx->ev[5], s));
+            if (route.window_beside) {
+                HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+                HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+            }
+            if (route.direct)
+                launch_scan_sizes(a, s);
+            hipLaunchKernelGGL(k_encode_tokens,
+                               dim3((uint32_t)(hi - a.blk_lo)), dim3(64), 0, s,
+                               a);
+            if (g.mid < hi) // the side stream's half is done as well
+                HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+            // the blocks whose tokens found no page: once more, by the window
+            // kernel, to where the encoder would have put them
+            // (CompressArgs::tok_pool)
+            if (!ctx->h_tokstat) {
+                HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_tokstat, 64,
+                                           hipHostMallocDefault));
+                memset((void *)ctx->h_tokstat, 0, 64);
+            }
+            CompressArgs r = a;
+            r.blk_lo = (uint32_t)lo;
+            r.blk_hi = (uint32_t)hi;
+            r.cls_lo = 0;
+            r.cls_hi = kMaxBlock;
+            hipLaunchKernelGGL(k_redo_spilled, dim3(g.redo_grid),
+                               dim3(kCompressWaves * 64), 0, s, r,
+                               (uint32_t *)ctx->h_tokstat, ++ctx->tokstat_seq);
         }
+        a.blk_lo = 0;
+        a.tok_base = 0;
+        a.blk_hi = (uint32_t)blocks;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], s));
-    if (blocks && direct) {
+    if (route.direct) {
         hipLaunchKernelGGL(k_stream_lens, dim3((uint32_t)((n + 255) / 256)),
                            dim3(256), 0, s, a);
         // what this batch compressed to, for the next batch's choice of
         // match finder (read without waiting: a hint)
-        if (ctx->match_kernel == 2 && blocks >= 2 * ctx->lane_min_blocks) {
+        if (route.post_ratio) {
             if (!ctx->h_ratio) {
                 HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_ratio, 64,
                                            hipHostMallocDefault));
@@ -1728,13 +1575,8 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     HIP_TRY(ctx, hipGetLastError());
     ctx->timing_valid = true;
     ctx->timing_is_compress = true;
-    ctx->last_kernel =
-        !blocks ? "k_compress_tiny"
-        : !lanes_mode ? "k_compress_spans"
-        : span_match ? (use_small && nb_big == 0 ? "k_match_spans_8k"
-                                                 : "k_match_spans")
-        : both_cores ? "k_match_both" : "k_match_blocks";
-    ctx->dominant_split = lanes_mode;
+    ctx->last_kernel = route.last_kernel;
+    ctx->dominant_split = route.tokens;
     ctx->codec_launches = blocks ? 1 : 0;
     return SNAPMI_OK;
 }

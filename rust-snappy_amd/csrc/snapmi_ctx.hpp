@@ -67,12 +67,6 @@ struct snapmi_ctx {
     // two-ended ticket (no faster: the wavefront kernel takes whole CUs' LDS
     // away from the lanes' input windows; kept as a cross-check)
     int compress_mode = 1;
-    // 1: batches between two blocks per CU and lane_min_blocks run the window
-    // kernel as a match finder (k_match_spans) in front of k_encode_tokens;
-    // 0 (default): k_compress_spans, which encodes while it matches (no token
-    // scratch).  Measured equal within 3 % either way on 64 MiB .. 1 GiB
-    // (profiles/r5_span_sweep.txt), so the path without scratch is the default
-    int window_tokens = 0;
     // k_compress_spans on more blocks than it has wavefronts: 1 (default) the
     // order of the blocks is chosen as the launch goes (SpanSched,
     // snapmi_compress.hip), 0 ticket order, 2 scheduled whatever the count
@@ -168,9 +162,6 @@ struct snapmi_ctx {
     // the match finder costs its random accesses far more than the 3.3 ms
     // it hides), 2 = whenever the segment has two blocks (tests)
     int lane_overlap_encode = 0;
-    // 1: the lane kernel's encoder writes every block at its final position
-    // (sizes are known after matching); 0: scratch slots + k_compact
-    int lane_direct_encode = 1;
     // 1: the lane tables come from hipExtMallocWithFlags(hipDeviceMallocUncached)
     int lane_tables_uncached = 0;
     // 3: k_decompress_streams3 (element per lane, 128-byte windows; default);

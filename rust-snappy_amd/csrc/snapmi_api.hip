@@ -1715,51 +1715,16 @@ static size_t long_stream_min()
 
 constexpr size_t kBatchLongMaxN = 16384;
 constexpr uint32_t kBatchLongMaxL = 4096;
+static_assert(sizeof(snapmi_error) == kStreamErrBytes,
+              "snapmi_streamplan.hpp sizes the piece descriptors with it");
 
-#define BL_CHECK(name)                                                        \
+#define LAUNCH_CHECK(name)                                                    \
     do {                                                                      \
         hipError_t _e = hipGetLastError();                                    \
         if (_e != hipSuccess)                                                 \
             return fail_ctx(ctx, SNAPMI_E_DEVICE, "launch of " #name ": %s",  \
                             hipGetErrorString(_e));                           \
     } while (0)
-
-// Segment size of the scan of long streams (k_stream_scan and the levels
-// above it): 4 KiB when there is enough of them to fill the chip with walks
-// (one 2 GiB stream: 2.0 ms of scan at 280 GiB/s), 1 KiB below that - the
-// scan of a few hundred KiB is then a wait for the longest walk of ONE
-// wavefront, ~1 200 hops of ~630 cycles in a 4 KiB segment (0.5 ms whatever
-// the size), and a quarter of that with four times the lanes.
-static uint32_t stream_seg_log2(const snapmi_ctx *ctx, uint64_t long_bytes)
-{
-    if (ctx->stream_seg_log2)
-        return ctx->stream_seg_log2;
-    return long_bytes < ((uint64_t)256 << 20) ? 10u : 12u;
-}
-
-// Segments per wavefront of k_stream_scan (StreamArgs::scan_segs) for a call
-// whose long streams hold `nseg` segments together: the kernel's full group of
-// 64 when that still makes kScanFill wavefronts, else halved until it does
-// (not below 8).  A scan wavefront of 64 segments of 1 KiB hands its 64 lanes
-// eight rounds of entry walks and then trunks of which the longest is three
-// to four times the average - ~1 100 hops of ~630 cycles, 280 us, whoever
-// else is on the chip - and 32 MiB of long streams are 506 such wavefronts,
-// two per CU.  Measured (profiles/r5_scan_groups.txt): 64 MiB of the corpus
-// round 1.359 -> 1.301 ms per call with 16 (8: 1.357 - the groups are a
-// second wave of workgroups then), one 126 MB stream as a batch of one 1.690
-// -> 1.585 with 32, Decoder::decompress of lcet10.txt 1.076 -> 0.993 with 8,
-// 256 MiB 1.622 with 64 and 1.702 with 32: hence 1 024.  (The cuts kernel's
-// 512 segments per wavefront were measured the same way: 64 .. 512 are equal,
-// its time is the one walk every lane has.)
-static uint32_t stream_scan_segs(const snapmi_ctx *ctx, uint64_t nseg)
-{
-    if (ctx->stream_scan_segs)
-        return ctx->stream_scan_segs;
-    uint32_t segs = kScanSegs;
-    while (segs > 8 && nseg / segs < kScanFill)
-        segs /= 2;
-    return segs;
-}
 
 // pinned host staging of a context (grow-only): pageable copies go through
 // the runtime's own staging buffer one at a time, process-wide - eight
@@ -1780,6 +1745,81 @@ static int pin_reserve(snapmi_ctx *ctx, void **p, size_t *cap, size_t bytes)
     return SNAPMI_OK;
 }
 
+// The geometry of stream `g` of plan `p` and where its tables and piece
+// descriptors lie in sd_tables / sd_desc (reserved for the plan); the caller
+// sets the stream's own fields (in, out, out_len, err, fb_mode).
+static void stream_pointers(snapmi_ctx *ctx, const StreamPlan &p,
+                            const StreamSlot &g, StreamArgs &a)
+{
+    uint8_t *const t = (uint8_t *)ctx->sd_tables.p;
+    uint8_t *const d = (uint8_t *)ctx->sd_desc.p;
+    a.nseg = g.nseg;
+    a.nsuper = g.nsuper;
+    a.nsuper3 = g.nsuper3;
+    a.kmax = g.kmax;
+    a.seg_log2 = p.seg_log2;
+    a.scan_segs = p.scan_segs;
+    a.meta = (unsigned long long *)(t + g.meta);
+    a.s1 = (unsigned long long *)(t + g.s1);
+    a.s2 = (unsigned long long *)(t + g.s2);
+    a.s3 = (unsigned long long *)(t + g.s3);
+    a.e1 = (unsigned long long *)(t + g.e1);
+    a.e2 = (unsigned long long *)(t + g.e2);
+    a.e3 = (unsigned long long *)(t + g.e3);
+    a.cuts = (unsigned long long *)(t + g.cuts);
+    a.c_in = (const void **)(d + p.c_in) + g.entry;
+    a.c_inlen = (unsigned long long *)(d + p.c_inlen) + g.entry;
+    a.c_out = (void **)(d + p.c_out) + g.entry;
+    a.c_cap = (unsigned long long *)(d + p.c_cap) + g.entry;
+    a.c_outlen = (unsigned long long *)(d + p.c_outlen) + g.entry;
+    a.c_err = (snapmi_error *)(d + p.c_err) + g.entry;
+    a.c_mode = (uint8_t *)(d + p.c_mode) + g.entry;
+}
+
+// The streams of plan `p`, whose descriptor block (descriptors, then the
+// workgroup prefixes) the device holds at `dev`, from their headers to their
+// piece descriptors: head, scan, the levels, chain, cuts, pieces.
+static int launch_stream_chain(snapmi_ctx *ctx, const StreamPlan &p,
+                               const void *dev)
+{
+    hipStream_t s = ctx->stream;
+    const uint32_t L = p.n;
+    const uint32_t *pre = (const uint32_t *)((const uint8_t *)dev + p.pre_off);
+    auto B = [&](int k) {
+        BatchStreams b;
+        b.descs = (const StreamArgs *)dev;
+        b.pre = k < 0 ? nullptr : pre + (size_t)k * (L + 1);
+        b.n = L;
+        return b;
+    };
+    hipLaunchKernelGGL(k_bstream_head, dim3(L), dim3(1), 0, s, B(-1));
+    LAUNCH_CHECK(k_bstream_head);
+    hipLaunchKernelGGL(k_bstream_scan, dim3(p.grid[kPScan]), dim3(64), 0, s,
+                       B(kPScan));
+    LAUNCH_CHECK(k_bstream_scan);
+    hipLaunchKernelGGL(k_bstream_super, dim3(p.grid[kPSuper]), dim3(kEntry), 0,
+                       s, B(kPSuper));
+    LAUNCH_CHECK(k_bstream_super);
+    hipLaunchKernelGGL(k_bstream_super3, dim3(p.grid[kPSuper3]), dim3(kEntry),
+                       0, s, B(kPSuper3));
+    LAUNCH_CHECK(k_bstream_super3);
+    hipLaunchKernelGGL(k_bstream_chain, dim3(L), dim3(1), 0, s, B(-1));
+    LAUNCH_CHECK(k_bstream_chain);
+    hipLaunchKernelGGL(k_bstream_spread3, dim3(p.grid[kPSpread3]), dim3(64), 0,
+                       s, B(kPSpread3));
+    LAUNCH_CHECK(k_bstream_spread3);
+    hipLaunchKernelGGL(k_bstream_spread2, dim3(p.grid[kPSpread2]), dim3(64), 0,
+                       s, B(kPSpread2));
+    LAUNCH_CHECK(k_bstream_spread2);
+    hipLaunchKernelGGL(k_bstream_cuts, dim3(p.grid[kPCuts]), dim3(64), 0, s,
+                       B(kPCuts));
+    LAUNCH_CHECK(k_bstream_cuts);
+    hipLaunchKernelGGL(k_bstream_pieces, dim3(p.grid[kPPieces]), dim3(256), 0,
+                       s, B(kPPieces));
+    LAUNCH_CHECK(k_bstream_pieces);
+    return SNAPMI_OK;
+}
+
 static int decompress_batch_long(snapmi_ctx *ctx,
                                  const void *const *d_in_ptrs,
                                  const uint64_t *d_in_lens,
@@ -1794,19 +1834,9 @@ static int decompress_batch_long(snapmi_ctx *ctx,
     int rc;
     const size_t list_bytes = 16 + (size_t)kBatchLongMaxL * sizeof(LongItem);
     if ((rc = reserve(ctx, ctx->bl_modes, 2 * n + 64)) ||
-        (rc = reserve(ctx, ctx->bl_list, list_bytes)))
+        (rc = reserve(ctx, ctx->bl_list, list_bytes)) ||
+        (rc = pin_reserve(ctx, &ctx->pin_bl, &ctx->pin_bl_cap, list_bytes)))
         return rc;
-    if (ctx->pin_bl_cap < list_bytes) {
-        if (ctx->pin_bl) {
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-            HIP_TRY(ctx, hipHostFree(ctx->pin_bl));
-            ctx->pin_bl = nullptr;
-            ctx->pin_bl_cap = 0;
-        }
-        HIP_TRY(ctx, hipHostMalloc(&ctx->pin_bl, list_bytes,
-                                   hipHostMallocDefault));
-        ctx->pin_bl_cap = list_bytes;
-    }
     uint8_t *modes = (uint8_t *)ctx->bl_modes.p, *modes2 = modes + n;
     uint32_t *d_count = (uint32_t *)ctx->bl_list.p;
     LongItem *d_list = (LongItem *)((uint8_t *)ctx->bl_list.p + 16);
@@ -1816,7 +1846,7 @@ static int decompress_batch_long(snapmi_ctx *ctx,
                        (uint64_t)long_stream_min(), modes, d_list,
                        kBatchLongMaxL,
                        d_count);
-    BL_CHECK(k_long_plan);
+    LAUNCH_CHECK(k_long_plan);
     HIP_TRY(ctx, hipMemcpyAsync(ctx->pin_bl, ctx->bl_list.p, list_bytes,
                                 hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1831,32 +1861,29 @@ static int decompress_batch_long(snapmi_ctx *ctx,
     const uint32_t L = found;
     const LongItem *items = (const LongItem *)((const uint8_t *)ctx->pin_bl + 16);
 
-    // ---- geometry, scratch, descriptors ----------------------------------
-    // first workgroup of every stream, per kernel: scan, super, super3,
-    // spread3, spread2, cuts, pieces
-    enum { kPScan, kPSuper, kPSuper3, kPSpread3, kPSpread2, kPCuts, kPPieces, kPre };
+    // ---- plan, scratch, descriptors --------------------------------------
     // (descriptors and prefixes are written into pinned memory of the
     // context: their copy to the device needs no wait - the next call's
     // synchronisation behind k_long_plan comes before they are written again)
-    const size_t desc_bytes0 = (size_t)L * sizeof(StreamArgs);
-    const size_t pre_count = (size_t)kPre * (L + 1);
     if ((rc = pin_reserve(ctx, &ctx->pin_bl2, &ctx->pin_bl2_cap,
-                          desc_bytes0 + pre_count * sizeof(uint32_t) + 64)))
+                          (size_t)L * sizeof(StreamArgs) +
+                              (size_t)kPre * (L + 1) * sizeof(uint32_t) + 64)))
         return rc;
     StreamArgs *const descs = (StreamArgs *)ctx->pin_bl2;
-    uint32_t *const pre = (uint32_t *)((uint8_t *)ctx->pin_bl2 + desc_bytes0);
-    size_t rows = 0, blocks = 0, cuts = 0, pieces = 0;
-    uint64_t long_bytes = 0;
-    for (uint32_t j = 0; j < L; j++)
-        long_bytes += items[j].in_len;
-    const uint32_t seg_log2 = stream_seg_log2(ctx, long_bytes);
-    const uint64_t seg = 1ull << seg_log2;
-    const uint32_t scan_segs = stream_scan_segs(ctx, long_bytes / seg + L);
+    std::vector<StreamSlot> slot(L);
+    for (uint32_t j = 0; j < L; j++) {
+        slot[j].in_len = items[j].in_len;
+        slot[j].bound = items[j].dlen;
+    }
+    const StreamPlan p = plan_streams(
+        slot.data(), L, false, ctx->stream_seg_log2, ctx->stream_scan_segs,
+        sizeof(StreamArgs), (uint32_t *)(descs + L));
+    if ((rc = reserve(ctx, ctx->sd_tables, p.t_bytes)) ||
+        (rc = reserve(ctx, ctx->sd_desc, p.d_bytes)) ||
+        (rc = reserve(ctx, ctx->bl_descs, p.desc_bytes + 64)))
+        return rc;
     for (uint32_t j = 0; j < L; j++) {
         StreamArgs &a = descs[j];
-        memset(&a, 0, sizeof a);
-        a.seg_log2 = seg_log2;
-        a.scan_segs = scan_segs;
         a.in = (const uint8_t *)items[j].in;
         a.in_len = items[j].in_len;
         a.out = (uint8_t *)items[j].out;
@@ -1864,179 +1891,60 @@ static int decompress_batch_long(snapmi_ctx *ctx,
         a.out_len = (unsigned long long *)(d_out_lens + items[j].idx);
         a.err = d_errs ? d_errs + items[j].idx : nullptr;
         a.fb_mode = modes2 + items[j].idx;
-        a.nseg = (uint32_t)((a.in_len + seg - 1) / seg + 1);
-        a.nsuper = (a.nseg + kSegPerSuper - 1) / kSegPerSuper;
-        a.nsuper3 = (a.nsuper + kSegPerSuper - 1) / kSegPerSuper;
-        a.kmax = (uint32_t)(items[j].dlen / kStreamChunk + 2);
-        uint32_t *pj = &pre[j];
-        const size_t st = L + 1;
-        pj[kPScan * st] = (a.nseg + scan_segs - 1) / scan_segs;
-        pj[kPSuper * st] = a.nsuper;
-        pj[kPSuper3 * st] = a.nsuper3;
-        pj[kPSpread3 * st] = (a.nsuper3 + 63) / 64;
-        pj[kPSpread2 * st] = (a.nsuper + 63) / 64;
-        pj[kPCuts * st] = (a.nseg + kCutSegs - 1) / kCutSegs;
-        pj[kPPieces * st] = (a.kmax + 255) / 256;
-        rows += (size_t)a.nseg + ((size_t)a.nsuper + a.nsuper3) * kSegPerSuper;
-        blocks += (size_t)a.nseg + a.nsuper + a.nsuper3;
-        cuts += (size_t)a.kmax + 1;
-        pieces += a.kmax;
+        stream_pointers(ctx, p, slot[j], a);
     }
-    uint32_t grid[kPre];
-    for (int k = 0; k < kPre; k++) { // counts -> exclusive prefix, total last
-        uint32_t *pk = &pre[(size_t)k * (L + 1)];
-        uint32_t acc = 0;
-        for (uint32_t j = 0; j < L; j++) {
-            const uint32_t c = pk[j];
-            pk[j] = acc;
-            acc += c;
-        }
-        pk[L] = acc;
-        grid[k] = acc;
-    }
-    const size_t t_bytes = 64 + (size_t)L * 64 + rows * kEntry * 16 +
-                           blocks * 16 + cuts * 16;
-    const size_t d_stride = 8 + 8 + 8 + 8 + 8 + sizeof(snapmi_error) + 1;
-    const size_t d_bytes = pieces * d_stride + 64;
-    const size_t desc_bytes = desc_bytes0;
-    const size_t pre_bytes = pre_count * sizeof(uint32_t);
-    if ((rc = reserve(ctx, ctx->sd_tables, t_bytes)) ||
-        (rc = reserve(ctx, ctx->sd_desc, d_bytes)) ||
-        (rc = reserve(ctx, ctx->bl_descs, desc_bytes + pre_bytes + 64)))
-        return rc;
-    {
-        unsigned long long *t = (unsigned long long *)ctx->sd_tables.p;
-        unsigned long long *meta = t;
-        t += (size_t)L * 8;
-        unsigned long long *e_all = t; // the e-tables of all streams: one fill
-        unsigned long long *e = e_all;
-        t += blocks * 2;
-        uint8_t *q = (uint8_t *)ctx->sd_desc.p;
-        const void **c_in = (const void **)q;
-        q += pieces * 8;
-        unsigned long long *c_inlen = (unsigned long long *)q;
-        q += pieces * 8;
-        void **c_out = (void **)q;
-        q += pieces * 8;
-        unsigned long long *c_cap = (unsigned long long *)q;
-        q += pieces * 8;
-        unsigned long long *c_outlen = (unsigned long long *)q;
-        q += pieces * 8;
-        snapmi_error *c_err = (snapmi_error *)q;
-        q += pieces * sizeof(snapmi_error);
-        uint8_t *c_mode = q;
-        size_t k0 = 0;
-        for (uint32_t j = 0; j < L; j++) {
-            StreamArgs &a = descs[j];
-            a.meta = meta + (size_t)j * 8;
-            a.e1 = e;
-            e += (size_t)a.nseg * 2;
-            a.e2 = e;
-            e += (size_t)a.nsuper * 2;
-            a.e3 = e;
-            e += (size_t)a.nsuper3 * 2;
-            a.s1 = t;
-            t += (size_t)a.nseg * kEntry * 2;
-            a.s2 = t;
-            t += (size_t)a.nsuper * kSegPerSuper * kEntry * 2;
-            a.s3 = t;
-            t += (size_t)a.nsuper3 * kSegPerSuper * kEntry * 2;
-            a.cuts = t;
-            t += ((size_t)a.kmax + 1) * 2;
-            a.c_in = c_in + k0;
-            a.c_inlen = c_inlen + k0;
-            a.c_out = c_out + k0;
-            a.c_cap = c_cap + k0;
-            a.c_outlen = c_outlen + k0;
-            a.c_err = c_err + k0;
-            a.c_mode = c_mode + k0;
-            k0 += a.kmax;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->bl_descs.p, descs,
-                                    desc_bytes + pre_bytes,
-                                    hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemsetAsync(e_all, 0xFF, blocks * 16, s));
-        HIP_TRY(ctx, hipMemsetAsync(modes2, 3, n, s));
-        const StreamArgs *dd = (const StreamArgs *)ctx->bl_descs.p;
-        const uint32_t *dp =
-            (const uint32_t *)((uint8_t *)ctx->bl_descs.p + desc_bytes);
-        auto B = [&](int k) {
-            BatchStreams b;
-            b.descs = dd;
-            b.pre = k < 0 ? nullptr : dp + (size_t)k * (L + 1);
-            b.n = L;
-            return b;
-        };
-        // the batch's other streams beside all this, on the second stream
-        // (their longest is 0.6-0.8 ms of one wavefront on the corpus)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        // from here on every way out joins the side stream again: whatever
-        // it was given still writes the caller's arrays and reads bl_modes /
-        // bl_order, which the next call reuses
-        struct SideJoin {
-            snapmi_ctx *c;
-            hipStream_t s;
-            bool joined = false;
-            void join()
-            {
-                if (joined)
-                    return;
-                joined = true;
-                if (hipEventRecord(c->ev_join, c->stream2) != hipSuccess ||
-                    hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    (void)hipStreamSynchronize(c->stream2);
-                }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bl_descs.p, descs, p.desc_bytes,
+                                hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync((uint8_t *)ctx->sd_tables.p + p.e_off, 0xFF,
+                                p.e_bytes, s));
+    HIP_TRY(ctx, hipMemsetAsync(modes2, 3, n, s));
+    // the batch's other streams beside all this, on the second stream
+    // (their longest is 0.6-0.8 ms of one wavefront on the corpus)
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+    // from here on every way out joins the side stream again: whatever
+    // it was given still writes the caller's arrays and reads bl_modes /
+    // bl_order, which the next call reuses
+    struct SideJoin {
+        snapmi_ctx *c;
+        hipStream_t s;
+        bool joined = false;
+        void join()
+        {
+            if (joined)
+                return;
+            joined = true;
+            if (hipEventRecord(c->ev_join, c->stream2) != hipSuccess ||
+                hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(c->stream2);
             }
-            ~SideJoin() { join(); }
-        } side{ctx, s};
-        if ((rc = launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs,
-                                    d_out_caps, d_out_lens, d_errs, modes, n,
-                                    nullptr, 0, ctx->stream2,
-                                    &ctx->bl_order)))
-            return rc;
-        hipLaunchKernelGGL(k_bstream_head, dim3(L), dim3(1), 0, s, B(-1));
-        BL_CHECK(k_bstream_head);
-        hipLaunchKernelGGL(k_bstream_scan, dim3(grid[kPScan]), dim3(64), 0, s,
-                           B(kPScan));
-        BL_CHECK(k_bstream_scan);
-        hipLaunchKernelGGL(k_bstream_super, dim3(grid[kPSuper]), dim3(kEntry),
-                           0, s, B(kPSuper));
-        BL_CHECK(k_bstream_super);
-        hipLaunchKernelGGL(k_bstream_super3, dim3(grid[kPSuper3]),
-                           dim3(kEntry), 0, s, B(kPSuper3));
-        BL_CHECK(k_bstream_super3);
-        hipLaunchKernelGGL(k_bstream_chain, dim3(L), dim3(1), 0, s, B(-1));
-        BL_CHECK(k_bstream_chain);
-        hipLaunchKernelGGL(k_bstream_spread3, dim3(grid[kPSpread3]), dim3(64),
-                           0, s, B(kPSpread3));
-        BL_CHECK(k_bstream_spread3);
-        hipLaunchKernelGGL(k_bstream_spread2, dim3(grid[kPSpread2]), dim3(64),
-                           0, s, B(kPSpread2));
-        BL_CHECK(k_bstream_spread2);
-        hipLaunchKernelGGL(k_bstream_cuts, dim3(grid[kPCuts]), dim3(64), 0, s,
-                           B(kPCuts));
-        BL_CHECK(k_bstream_cuts);
-        hipLaunchKernelGGL(k_bstream_pieces, dim3(grid[kPPieces]), dim3(256),
-                           0, s, B(kPPieces));
-        BL_CHECK(k_bstream_pieces);
-        // the pieces of the long streams; which of the long ones were
-        // irregular; those, by the wavefront decoder
-        if ((rc = launch_decompress(ctx, c_in, (const uint64_t *)c_inlen,
-                                    c_out, (const uint64_t *)c_cap,
-                                    (uint64_t *)c_outlen, c_err, c_mode,
-                                    pieces)))
-            return rc;
-        hipLaunchKernelGGL(k_bstream_finish, dim3(L), dim3(1024), 0, s, B(-1));
-        BL_CHECK(k_bstream_finish);
-        side.join();
-        // (without timing events: snapmi_last_timing reports the pieces)
-        if ((rc = launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs,
-                                    d_out_caps, d_out_lens, d_errs, modes2,
-                                    n, nullptr, 0, s, nullptr)))
-            return rc;
-    }
+        }
+        ~SideJoin() { join(); }
+    } side{ctx, s};
+    if ((rc = launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs,
+                                d_out_caps, d_out_lens, d_errs, modes, n,
+                                nullptr, 0, ctx->stream2, &ctx->bl_order)) ||
+        (rc = launch_stream_chain(ctx, p, ctx->bl_descs.p)))
+        return rc;
+    // the pieces of the long streams; which of the long ones were
+    // irregular; those, by the wavefront decoder
+    const StreamArgs &a = descs[0]; // (its arrays hold all streams' pieces)
+    if ((rc = launch_decompress(ctx, a.c_in, (const uint64_t *)a.c_inlen,
+                                a.c_out, (const uint64_t *)a.c_cap,
+                                (uint64_t *)a.c_outlen, a.c_err, a.c_mode,
+                                p.pieces)))
+        return rc;
+    hipLaunchKernelGGL(k_bstream_finish, dim3(L), dim3(1024), 0, s,
+                       BatchStreams{(const StreamArgs *)ctx->bl_descs.p,
+                                    nullptr, L});
+    LAUNCH_CHECK(k_bstream_finish);
+    side.join();
+    // (without timing events: snapmi_last_timing reports the pieces)
+    if ((rc = launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs,
+                                d_out_caps, d_out_lens, d_errs, modes2, n,
+                                nullptr, 0, s, nullptr)))
+        return rc;
     *done = true;
     return SNAPMI_OK;
 }
@@ -2079,14 +1987,10 @@ int snapmi_decompress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                              d_out_lens, d_errs, nullptr, n);
 }
 
-#define STREAM_CHECK(name)                                                    \
-    do {                                                                      \
-        hipError_t _e = hipGetLastError();                                    \
-        if (_e != hipSuccess)                                                 \
-            return fail_ctx(ctx, SNAPMI_E_DEVICE, "launch of " #name ": %s",  \
-                            hipGetErrorString(_e));                           \
-    } while (0)
-
+// One stream as a batch of one, enqueue-only (the scalar entry points wait
+// for nothing else).  Its descriptor, the prefixes of its launches and the
+// whole stream for the sequential decoder reach the device in one copy from
+// this frame: the runtime stages a pageable copy before the call returns.
 int snapmi_decompress_stream(snapmi_ctx *ctx, const void *d_in,
                              uint64_t in_len, void *d_out, uint64_t out_cap,
                              uint64_t *d_out_len, snapmi_error *d_err)
@@ -2096,132 +2000,64 @@ int snapmi_decompress_stream(snapmi_ctx *ctx, const void *d_in,
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "decompress_stream: bad args");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // pieces: one per 64 KiB of output; the output cannot exceed out_cap nor
-    // ~21.4x the input (a 3-byte copy element yields at most 64 bytes)
-    uint64_t bound = out_cap;
-    if (in_len < (1ull << 40) && in_len * 22 < bound)
-        bound = in_len * 22;
-    const uint64_t kmax64 = bound / kStreamChunk + 2;
-    const uint32_t seg_log2 = stream_seg_log2(ctx, in_len);
-    const uint64_t seg = 1ull << seg_log2;
-    const uint64_t nseg64 = (in_len + seg - 1) / seg + 1;
-    if (kmax64 > 0x3FFFFFFFu || nseg64 > 0x3FFFFFFFu)
+    struct Lone {
+        StreamArgs a;
+        uint32_t pre[kPre * 2];
+        // the whole stream, mode 0 (decode it), for the sequential decoder
+        const void *in;
+        uint64_t in_len;
+        void *out;
+        uint64_t cap;
+        uint8_t mode;
+    } h = {};
+    static_assert(offsetof(Lone, pre) == sizeof(StreamArgs),
+                  "the descriptor block of plan_streams");
+    StreamSlot slot;
+    slot.in_len = in_len;
+    slot.bound = lone_stream_bound(in_len, out_cap);
+    const StreamPlan p =
+        plan_streams(&slot, 1, true, ctx->stream_seg_log2,
+                     ctx->stream_scan_segs, sizeof(StreamArgs), h.pre);
+    if (!p.fits)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "decompress_stream: too long");
-    StreamArgs a;
+    int rc;
+    if ((rc = reserve(ctx, ctx->sd_tables, p.t_bytes)) ||
+        (rc = reserve(ctx, ctx->sd_desc, p.d_bytes)) ||
+        (rc = reserve(ctx, ctx->bl_descs, sizeof h)))
+        return rc;
+    StreamArgs &a = h.a;
     a.in = (const uint8_t *)d_in;
     a.in_len = in_len;
     a.out = (uint8_t *)d_out;
     a.out_cap = out_cap;
     a.out_len = (unsigned long long *)d_out_len;
     a.err = d_err;
-    a.nseg = (uint32_t)nseg64;
-    a.seg_log2 = seg_log2;
-    a.scan_segs = stream_scan_segs(ctx, a.nseg);
-    a.nsuper = (a.nseg + kSegPerSuper - 1) / kSegPerSuper;
-    a.nsuper3 = (a.nsuper + kSegPerSuper - 1) / kSegPerSuper;
-    a.kmax = (uint32_t)kmax64;
     a.fb_mode = nullptr;
-    const size_t blocks = (size_t)a.nseg + a.nsuper + a.nsuper3;
-    const size_t rows = (size_t)a.nseg +
-                        ((size_t)a.nsuper + a.nsuper3) * kSegPerSuper;
-    const size_t t_bytes = 64 + rows * kEntry * 16 + blocks * 16 +
-                           ((size_t)a.kmax + 1) * 16;
-    // descriptors: the pieces, then the whole stream as batch entry [kmax]
-    const size_t d_stride = 8 + 8 + 8 + 8 + 8 + sizeof(snapmi_error);
-    const size_t d_bytes = ((size_t)a.kmax + 1) * (d_stride + 1) + 64;
-    int rc;
-    if ((rc = reserve(ctx, ctx->sd_tables, t_bytes)) ||
-        (rc = reserve(ctx, ctx->sd_desc, d_bytes)))
+    stream_pointers(ctx, p, slot, a);
+    h.in = d_in;
+    h.in_len = in_len;
+    h.out = d_out;
+    h.cap = out_cap;
+    const Lone *dh = (const Lone *)ctx->bl_descs.p;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bl_descs.p, &h, sizeof h,
+                                hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync((uint8_t *)ctx->sd_tables.p + p.e_off, 0xFF,
+                                p.e_bytes, s));
+    if ((rc = launch_stream_chain(ctx, p, dh)))
         return rc;
-    unsigned long long *t = (unsigned long long *)ctx->sd_tables.p;
-    a.meta = t;
-    t += 8;
-    a.s1 = t;
-    t += (size_t)a.nseg * kEntry * 2;
-    a.s2 = t;
-    t += (size_t)a.nsuper * kSegPerSuper * kEntry * 2;
-    a.s3 = t;
-    t += (size_t)a.nsuper3 * kSegPerSuper * kEntry * 2;
-    a.e1 = t; // e1, e2, e3 contiguous: one memset
-    t += (size_t)a.nseg * 2;
-    a.e2 = t;
-    t += (size_t)a.nsuper * 2;
-    a.e3 = t;
-    t += (size_t)a.nsuper3 * 2;
-    a.cuts = t;
-    const size_t m = (size_t)a.kmax + 1;
-    uint8_t *q = (uint8_t *)ctx->sd_desc.p;
-    a.c_in = (const void **)q;
-    q += m * 8;
-    a.c_inlen = (unsigned long long *)q;
-    q += m * 8;
-    a.c_out = (void **)q;
-    q += m * 8;
-    a.c_cap = (unsigned long long *)q;
-    q += m * 8;
-    a.c_outlen = (unsigned long long *)q;
-    q += m * 8;
-    a.c_err = (snapmi_error *)q;
-    q += m * sizeof(snapmi_error);
-    a.c_mode = q;
-
-    // entry [kmax]: the stream itself, for the sequential decoder
-    struct {
-        const void *in;
-        uint64_t in_len;
-        void *out;
-        uint64_t cap;
-    } whole = {d_in, in_len, d_out, out_cap};
-    HIP_TRY(ctx, hipMemcpyAsync((void *)&a.c_in[a.kmax], &whole.in, 8,
-                                hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(&a.c_inlen[a.kmax], &whole.in_len, 8,
-                                hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(&a.c_out[a.kmax], &whole.out, 8,
-                                hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(&a.c_cap[a.kmax], &whole.cap, 8,
-                                hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(&a.c_mode[a.kmax], 0, 1, s));
-    HIP_TRY(ctx, hipMemsetAsync(a.e1, 0xFF, blocks * 16, s));
-
-    hipLaunchKernelGGL(k_stream_head, dim3(1), dim3(1), 0, s, a);
-    STREAM_CHECK(k_stream_head);
-    hipLaunchKernelGGL(k_stream_scan,
-                       dim3((a.nseg + a.scan_segs - 1) / a.scan_segs),
-                       dim3(64), 0, s, a);
-    STREAM_CHECK(k_stream_scan);
-    hipLaunchKernelGGL(k_stream_super, dim3(a.nsuper), dim3(kEntry), 0, s, a);
-    STREAM_CHECK(k_stream_super);
-    hipLaunchKernelGGL(k_stream_super3, dim3(a.nsuper3), dim3(kEntry), 0, s,
-                       a);
-    STREAM_CHECK(k_stream_super3);
-    hipLaunchKernelGGL(k_stream_chain, dim3(1), dim3(1), 0, s, a);
-    STREAM_CHECK(k_stream_chain);
-    hipLaunchKernelGGL(k_stream_spread3, dim3((a.nsuper3 + 63) / 64),
-                       dim3(64), 0, s, a);
-    STREAM_CHECK(k_stream_spread3);
-    hipLaunchKernelGGL(k_stream_spread2, dim3((a.nsuper + 63) / 64), dim3(64),
-                       0, s, a);
-    STREAM_CHECK(k_stream_spread2);
-    hipLaunchKernelGGL(k_stream_cuts, dim3((a.nseg + kCutSegs - 1) / kCutSegs),
-                       dim3(64), 0, s, a);
-    STREAM_CHECK(k_stream_cuts);
-    hipLaunchKernelGGL(k_stream_pieces, dim3((a.kmax + 255) / 256), dim3(256),
-                       0, s, a);
-    STREAM_CHECK(k_stream_pieces);
     // the pieces, unless the scan gave up (meta[2] == 1) ...
-    rc = launch_decompress(ctx, a.c_in, (const uint64_t *)a.c_inlen, a.c_out,
-                           (const uint64_t *)a.c_cap, (uint64_t *)a.c_outlen,
-                           a.c_err, a.c_mode, a.kmax, a.meta + 2, 0);
-    if (rc)
+    if ((rc = launch_decompress(ctx, a.c_in, (const uint64_t *)a.c_inlen,
+                                a.c_out, (const uint64_t *)a.c_cap,
+                                (uint64_t *)a.c_outlen, a.c_err, a.c_mode,
+                                a.kmax, a.meta + 2, 0)))
         return rc;
-    hipLaunchKernelGGL(k_stream_finish, dim3(1), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(k_bstream_finish, dim3(1), dim3(1024), 0, s,
+                       BatchStreams{&dh->a, nullptr, 1});
+    LAUNCH_CHECK(k_bstream_finish);
     // ... and the sequential decoder over the whole stream if anything was
     // irregular: it owns the error report
-    return launch_decompress(ctx, a.c_in + a.kmax,
-                             (const uint64_t *)a.c_inlen + a.kmax,
-                             a.c_out + a.kmax,
-                             (const uint64_t *)a.c_cap + a.kmax, d_out_len,
-                             d_err, a.c_mode + a.kmax, 1, a.meta + 2, 1);
+    return launch_decompress(ctx, &dh->in, &dh->in_len, &dh->out, &dh->cap,
+                             d_out_len, d_err, &dh->mode, 1, a.meta + 2, 1);
 }
 
 int snapmi_stream_decode_path(snapmi_ctx *ctx)

@@ -174,12 +174,15 @@ struct snapmi_ctx {
     bool frame_crc_side_stream = true;
     // staging for the host-pointer (scalar) entry points
     snapmi::DevBuf st_in, st_out, st_desc, st_prof, ticket, order;
-    // long-stream decode scratch (snapmi_decompress_stream)
+    // long-stream decode scratch of snapmi_decompress_stream and of the long
+    // streams of a batch (snapmi_streamplan.hpp lays them out): tables,
+    // piece descriptors
     snapmi::DevBuf sd_tables, sd_desc;
     // the long streams of a small batch get their pieces
     // (snapmi_decompress_batch, option batch_long_streams): modes of the
-    // batch's own launch and of the one behind, what k_long_plan found, the
-    // streams' descriptors and workgroup prefixes; pinned staging of both
+    // batch's own launch and of the one behind, what k_long_plan found; the
+    // streams' descriptors and workgroup prefixes (a lone stream's too); pinned
+    // staging of the list and of the batch's descriptors
     int batch_long_streams = 1;
     snapmi::DevBuf bl_modes, bl_list, bl_descs, bl_order;
     void *pin_bl = nullptr;

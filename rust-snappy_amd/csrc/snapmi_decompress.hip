@@ -29,12 +29,12 @@
 //       what names every error (any failed check of the wide paths hands the
 //       stream over), and the fallback of a device that fails the LDS
 //       store-order self-check.
-//   k_stream_* / k_long_plan + k_bstream_*   ONE long stream on many
-//       wavefronts: (exit, produced) per segment and entry offset by walks
-//       that hop through LDS (scan), two levels above, one short sequential
-//       pass, the element boundaries at every 64 KiB of output (cuts), and
-//       the pieces between them through k_decompress_streams3; the same for
-//       the long streams of a small batch.
+//   k_long_plan + k_bstream_*   ONE long stream on many wavefronts:
+//       (exit, produced) per segment and entry offset by walks that hop
+//       through LDS (scan), two levels above, one short sequential pass, the
+//       element boundaries at every 64 KiB of output (cuts), and the pieces
+//       between them through k_decompress_streams3; all long streams of a
+//       small batch in the same launches, a lone stream as a batch of one.
 //
 // DESIGN.md section 4.2 has the history (byte-per-lane kernel of round 1,
 // gone; 354 -> 16 ms at cfg2) and what bounds each of them.
@@ -1819,7 +1819,8 @@ __global__ __launch_bounds__(64) void k_decompress_small(DecompressArgs a)
 }
 
 // ---------------------------------------------------------------------
-// One long raw stream on many wavefronts (snapmi_decompress_stream).
+// One long raw stream on many wavefronts (snapmi_decompress_stream, and the
+// long streams of a small batch).
 //
 // A raw stream has no index and its elements form a chain, but where the
 // chain goes is cheap to tabulate: a lane that starts at byte o of a 4 KiB
@@ -1837,7 +1838,7 @@ __global__ __launch_bounds__(64) void k_decompress_small(DecompressArgs a)
 // ---------------------------------------------------------------------
 namespace {
 constexpr unsigned long long kNone = ~0ull;
-// k_stream_scan follows a chain at most this many elements behind its
+// k_bstream_scan follows a chain at most this many elements behind its
 // segment's end.  Compressible data lands on a tabulated offset (within
 // kEntry = 8 bytes of a 4 KiB boundary) at the next boundary unless an
 // element of 9+ encoded bytes jumps over it, which costs a segment of small
@@ -2048,7 +2049,7 @@ __device__ __forceinline__ void stream_head(const StreamArgs &a, const uint32_t 
 }
 
 // ---------------------------------------------------------------------
-// k_stream_scan: the level-1 table, (exit, produced) for the kEntry entry
+// k_bstream_scan: the level-1 table, (exit, produced) for the kEntry entry
 // offsets of every 4 KiB segment.
 //
 // Rounds 1-3 gave every (segment, entry) its own lane and let it hop through
@@ -2111,7 +2112,7 @@ struct Hopper {
     uint32_t over;     // elements hopped behind the segment's end
     uint32_t endR;     // the segment's end (or the stream's)
     uint32_t stopR;    // phase A pauses at the first element start here
-    uint32_t stopOut;  // k_stream_cuts: ... at the first one that has produced this
+    uint32_t stopOut;  // k_bstream_cuts: ... at the first one that has produced this
     bool run;          // hopping
     bool slow;         // stands in front of a literal with length bytes
     bool fail;         // the chain cannot be followed
@@ -2524,7 +2525,7 @@ __device__ __forceinline__ void stream_chain(const StreamArgs &a, const uint32_t
 // The element boundary at (or first behind) every 64 KiB of output: the
 // segments whose stretch of the chain holds such a boundary are collected -
 // kCutSegs segments per wavefront, one in eight on text - and walked from
-// where the chain enters them by the pool of k_stream_scan (windows in LDS),
+// where the chain enters them by the pool of k_bstream_scan (windows in LDS),
 // a lane per segment, standing at every boundary on the way.  (Rounds 1-3:
 // one lane per segment hopping through HBM, the wavefront as slow as its
 // slowest lane: 1.7 ms of a 2 GiB stream.)
@@ -2671,10 +2672,10 @@ __device__ __forceinline__ void stream_finish(const StreamArgs &a, const uint32_
 }
 
 // ---------------------------------------------------------------------
-// The kernels: for ONE stream (snapmi_decompress_stream), and for the long
-// streams of a batch (snapmi_decompress_batch, few streams: every long stream
-// gets its pieces instead of one wavefront) - the same bodies, a workgroup of
-// the batched launch first finds its stream.
+// The kernels, for the long streams of a batch (snapmi_decompress_batch, few
+// streams: every long stream gets its pieces instead of one wavefront) and
+// for ONE stream as a batch of one (snapmi_decompress_stream): a workgroup
+// first finds its stream and its place in that stream's workgroups.
 // ---------------------------------------------------------------------
 // b.pre[s] = first workgroup of stream s in this launch, pre[L] = all of them;
 // pre == nullptr: one workgroup per stream
@@ -2702,11 +2703,6 @@ __device__ __forceinline__ bool batch_find(const BatchStreams &b, uint32_t &s,
     return true;
 }
 #define SNAPMI_STREAM_KERNEL(name, bounds, call)                              \
-    __global__ __launch_bounds__(bounds) void k_stream_##name(StreamArgs a)   \
-    {                                                                         \
-        const uint32_t wg = blockIdx.x;                                       \
-        call;                                                                 \
-    }                                                                         \
     __global__ __launch_bounds__(bounds) void k_bstream_##name(BatchStreams b) \
     {                                                                         \
         uint32_t s_, wg;                                                      \

@@ -8,6 +8,7 @@
 #include "snapmi.h"
 #include "snapmi_tiny.hpp"
 #include "snapmi_profile.hpp"
+#include "snapmi_streamplan.hpp"
 
 namespace snapmi {
 
@@ -160,10 +161,10 @@ struct DecompressArgs {
     uint64_t *out_lens;
     snapmi_error *errs; // [n] or nullptr
     // optional [n]: 1 = stored chunk (frame type 0x01): plain copy of the
-    // input; 2 = headerless piece of a long stream (k_stream_*): elements only,
-    // out_caps[i] is the exact output length; 3 = not this launch's (a long
-    // stream of a batch, decoded through its pieces): nothing is read, nothing
-    // written
+    // input; 2 = headerless piece of a long stream (k_bstream_pieces):
+    // elements only, out_caps[i] is the exact output length; 3 = not this
+    // launch's (a long stream of a batch, decoded through its pieces):
+    // nothing is read, nothing written
     const uint8_t *modes;
     // optional: the launch does nothing unless *gate == gate_value
     const unsigned long long *gate;
@@ -216,29 +217,9 @@ __global__ void k_scan_sizes(CompressArgs a);
 __global__ void k_compact(CompressArgs a);
 __global__ void k_stream_lens(CompressArgs a);
 
-// One long raw stream decoded by many wavefronts (snapmi_decompress_stream).
-// The element chain is sequential, so it is resolved hierarchically first:
-// per 4 KiB segment and per 256 KiB super-segment, "if an element starts at
-// offset o (< kEntry) of this piece, where does the chain leave it and how many
-// bytes has it produced".
-constexpr uint32_t kSeg = 4096;           // bytes of compressed input
-// Entry offsets tabulated per segment / child: a chain is followed from the
-// first kEntry bytes behind a boundary.  8 instead of a full wavefront of 64:
-// the 64 chains of a segment merge within a few elements, so most of the
-// scan's hops were duplicates; a wavefront now scans eight segments (one raw
-// stream of 3 GiB: 52 -> 119 GiB/s; 16 entries gave 103, 4 gave 123 within
-// noise of 8).  A literal of 9-60 bytes that straddles a boundary jumps over
-// the landing zone and costs one more segment of hops: rare next to the 8x.
-constexpr uint32_t kEntry = 8;
-constexpr uint32_t kSegPerSuper = 64;
-constexpr uint32_t kCutSegs = 512;       // segments per wavefront of k_stream_cuts
-constexpr uint32_t kScanSegs = 64;       // segments per wavefront of k_stream_scan, at most
-// wavefronts a scan launch should have before its wavefronts own that many
-// segments each (StreamArgs::scan_segs)
-constexpr uint32_t kScanFill = 1024;
-constexpr uint32_t kStreamChunk = 65536;  // output bytes per piece: the
-                                          // encoders' block size, so pieces
-                                          // of their streams are independent
+// One long raw stream decoded by many wavefronts (snapmi_decompress_stream,
+// and the long streams of a small batch): the constants and the plan of the
+// launches are snapmi_streamplan.hpp's.
 struct StreamArgs {
     const uint8_t *in;
     unsigned long long in_len;
@@ -262,11 +243,11 @@ struct StreamArgs {
     // are short enough for the scan to be a wait for its longest walk: a
     // quarter of the hops per lane, four times the lanes - round 5)
     uint32_t seg_log2;
-    // segments a wavefront of k_stream_scan owns: kScanSegs when that still
+    // segments a wavefront of k_bstream_scan owns: kScanSegs when that still
     // makes kScanFill wavefronts, fewer (a power of two from 8) when it does
     // not - a scan wavefront is as slow as the chain of walks its lanes are
     // handed, ~630 cycles a hop whoever else is on the chip
-    // (stream_scan_segs in snapmi_api.hip)
+    // (stream_scan_segs in snapmi_streamplan.hpp)
     uint32_t scan_segs;
     // piece descriptors for k_decompress_streams
     const void **c_in;
@@ -276,12 +257,13 @@ struct StreamArgs {
     unsigned long long *c_outlen;
     snapmi_error *c_err;
     uint8_t *c_mode;
-    // a long stream of a batch: where k_stream_finish says whether the
+    // a long stream of a batch: where k_bstream_finish says whether the
     // launch behind it must decode the stream (0) or not (3); else nullptr
     uint8_t *fb_mode;
 };
-// the long streams of a batch: their descriptors and, per kernel, the first
-// workgroup of every stream (nullptr: one workgroup each)
+// the long streams of a batch (a lone stream is a batch of one): their
+// descriptors and, per kernel, the first workgroup of every stream (nullptr:
+// one workgroup each)
 struct BatchStreams {
     const StreamArgs *descs;
     const uint32_t *pre; // [n + 1]
@@ -308,7 +290,6 @@ struct LongItem { // what k_long_plan hands to the host
     unsigned long long out_cap;
 };
 #define SNAPMI_STREAM_KERNEL_DECL(name)                                       \
-    __global__ void k_stream_##name(StreamArgs a);                            \
     __global__ void k_bstream_##name(BatchStreams b);
 SNAPMI_STREAM_KERNEL_DECL(head)
 SNAPMI_STREAM_KERNEL_DECL(scan)

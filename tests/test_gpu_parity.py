@@ -527,7 +527,7 @@ def test_long_stream_parallel_decode(ctx, geom):
 
 @pytest.mark.parametrize("geom", SCAN_GEOMETRIES)
 def test_long_stream_scan_shapes(ctx, geom):
-    """The structure k_stream_scan / k_stream_cuts work in (8 .. 64 segments
+    """The structure k_bstream_scan / k_bstream_cuts work in (8 .. 64 segments
     of 1 or 4 KiB per scan wavefront, 512 per cuts wavefront, walks handed out from a
     pool, chains that join the next segment's trunk): streams whose segment
     count sits at and around those boundaries, streams where chains run

@@ -9,18 +9,27 @@ and outputs resident in HBM.  value = uncompressed bytes through both
 directions / time, whole job, GiB/s.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--gib G]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline needs and nothing else: it sets up (the
+first compress and decompress call of the context, untimed), warms up, times
+the K steps, writes the outputs of the last step if asked and prints the
+line.  `--full` adds everything else the benchmark measures or checks: the
+parity gate against the oracle's bytes before and after the timed steps,
+roofline.traffic from two PMC child runs, the `extras` and the CPU baseline
+(each of them can be left out again with --no-verify / --no-pmc /
+--no-extras / --no-cpu).
 
 Multi-GPU: streams are independent, so each rank compresses its own shard;
 no data-path collective (scaling = weak: G GiB per GPU).  `--gpus N` without
 a torch.distributed environment re-executes itself under
 torch.distributed.run with N ranks (one per GPU, 127.0.0.1 rendezvous); it
 fails loudly when fewer than N devices are visible or when WORLD_SIZE
-disagrees with N.  After the timed region the line gets `extras`: BASELINE
-configs 3 and 5 at full size and the per-file rates (N = 1), and config 4 -
-the framed stream sharded by chunk range over the ranks with the RCCL gather
-of the framed parts (any N).
+disagrees with N.  With --full, after the timed region the line gets
+`extras`: BASELINE configs 3 and 5 at full size and the per-file rates
+(N = 1), and config 4 - the framed stream sharded by chunk range over the
+ranks with the RCCL gather of the framed parts (any N).
 """
 import argparse
 import hashlib
@@ -311,8 +320,7 @@ def measure_traffic(args, kernels):
             cmd = [rp, "--kernel-trace", "--pmc", counter, "--output-format",
                    "csv", "-d", out, "-o", "p", "--", sys.executable,
                    str(Path(__file__).resolve()), "--steps", "1", "--warmup",
-                   "0", "--no-cpu", "--no-extras", "--no-pmc", "--gib",
-                   f"{args.gib:g}"]
+                   "0", "--gib", f"{args.gib:g}"]
             env = dict(os.environ, TMPDIR="/tmp")
             p = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True,
                                text=True, timeout=240)
@@ -531,21 +539,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--gib", type=float, default=8.0,
                     help="uncompressed GiB per GPU (BASELINE cfg2: 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate, "
+                         "roofline.traffic from PMC child runs, the extra "
+                         "configs and the CPU baseline (a plain run does "
+                         "none of them)")
     ap.add_argument("--no-cpu", action="store_true",
-                    help="skip the cpu_baseline leg")
+                    help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-verify", action="store_true",
-                    help="experiment builds only: skip the parity gate "
-                         "(the JSON line is then marked invalid)")
+                    help="experiment builds only: skip the parity gate of "
+                         "--full (the JSON line is then marked invalid)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra configs (cfg3/cfg4/cfg5/per-file)")
+                    help="with --full: skip the extra configs "
+                         "(cfg3/cfg4/cfg5/per-file)")
     ap.add_argument("--extras-gib", type=float, default=None,
                     help="size of the cfg3 / cfg5 extras (default: BASELINE's "
                          "64 and 32 GiB)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not measure roofline.traffic (two child runs of "
-                         "one step each under rocprofv3 --pmc FETCH_SIZE / "
-                         "WRITE_SIZE); the committed profile is quoted "
-                         "instead and the line says traffic_measured: false")
+                    help="with --full: do not measure roofline.traffic (two "
+                         "child runs of one step each under rocprofv3 --pmc "
+                         "FETCH_SIZE / WRITE_SIZE); the committed profile is "
+                         "quoted instead, as in a plain run, and the line "
+                         "says traffic_measured: false")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="proof run of the N > 1 code on ONE GPU: all ranks "
                          "drive cuda:0, collectives over gloo; the JSON line "
@@ -679,7 +694,7 @@ def main():
                              back.d_lens, back_lens, back_errs)
         return ctx.last_timing()
 
-    # ---- parity gate before any number is reported ----------------------
+    # ---- the first call of the context, untimed -------------------------
     # (the first compress call of the context on its own: it allocates the
     # scratch and places the lane tables - the line carries what it took and
     # the device's free memory around it, so that a record explains itself)
@@ -693,36 +708,40 @@ def main():
     do_decompress()
     ctx.synchronize()
     cl = comp_lens.cpu().numpy()
-    if args.no_verify:
-        shas, rounds_checked = [], 0
+    c_stride = int(comp.offsets[12]) if rounds > 1 else 0
+    per = back.data[:rounds * round_stride].view(rounds, round_stride)
+    gate = args.full and not args.no_verify
+
     def kinds(t):
         return np.frombuffer(t.cpu().numpy().tobytes(),
                              dtype="<i4").reshape(n, 8)[:, 0]
-    assert (kinds(comp_errs) == 0).all(), "compress reported errors"
-    assert args.no_verify or (kinds(back_errs) == 0).all(), \
-        "decompress reported errors"
-    for j in range(12 if not args.no_verify else 0):  # round 0 vs sha256
-        got = comp.stream_bytes(j, cl[j])
-        n_in, n_out, sha = shas[j]
-        assert len(got) == n_out and hashlib.sha256(got).hexdigest() == sha, \
-            f"compressed bytes of stream {j} differ from the oracle's"
-    assert args.no_verify or (cl.reshape(rounds, 12) == cl[:12][None, :]).all()
-    c_stride = int(comp.offsets[12]) if rounds > 1 else 0
-    if rounds > 1 and not args.no_verify:  # every round equals round 0
-        per = comp.data[:rounds * c_stride].view(rounds, c_stride)
-        for j in range(12):
-            o, m = int(comp.offsets[j]), int(cl[j])
-            assert bool((per[:, o:o + m] == per[0:1, o:o + m]).all()), j
-    per = back.data[:rounds * round_stride].view(rounds, round_stride)
-    for j in range(12 if not args.no_verify else 0):  # round trip == input
-        o, m = int(r_offs[j]), int(r_lens[j])
-        assert bool((per[:, o:o + m] == d_round[None, o:o + m]).all()), \
-            f"round trip of stream {j} differs from the input"
+
+    # ---- --full: parity gate before any number is reported --------------
+    if args.full:
+        assert (kinds(comp_errs) == 0).all(), "compress reported errors"
+    if gate:
+        assert (kinds(back_errs) == 0).all(), "decompress reported errors"
+        for j in range(12):  # round 0 vs sha256
+            got = comp.stream_bytes(j, cl[j])
+            n_in, n_out, sha = shas[j]
+            assert len(got) == n_out and \
+                hashlib.sha256(got).hexdigest() == sha, \
+                f"compressed bytes of stream {j} differ from the oracle's"
+        assert (cl.reshape(rounds, 12) == cl[:12][None, :]).all()
+        if rounds > 1:  # every round equals round 0
+            perc = comp.data[:rounds * c_stride].view(rounds, c_stride)
+            for j in range(12):
+                o, m = int(comp.offsets[j]), int(cl[j])
+                assert bool((perc[:, o:o + m] == perc[0:1, o:o + m]).all()), j
+        for j in range(12):  # round trip == input
+            o, m = int(r_offs[j]), int(r_lens[j])
+            assert bool((per[:, o:o + m] == d_round[None, o:o + m]).all()), \
+                f"round trip of stream {j} differs from the input"
     cbytes = int(cl.sum())
     ratio = cbytes / ubytes
     if rank == 0:
-        log(f"[bench] parity ok; compressed {cbytes / GIB:.3f} GiB "
-            f"(ratio {ratio:.4f})")
+        log(f"[bench] {'parity ok; ' if gate else ''}compressed "
+            f"{cbytes / GIB:.3f} GiB (ratio {ratio:.4f})")
 
     # ---- timed region ----------------------------------------------------
     def barrier():
@@ -764,7 +783,7 @@ def main():
     # `comp` and `back` is still the oracle's bytes and the input
     verified_after = False
     placement_log = None
-    if not args.no_verify:
+    if gate:
         cl2 = comp_lens.cpu().numpy()
         assert (cl2 == cl).all(), "compressed lengths changed during the run"
         assert (kinds(comp_errs) == 0).all() and (kinds(back_errs) == 0).all()
@@ -846,7 +865,7 @@ def main():
 
     # ---- extra configs (never part of `value`) ---------------------------
     extras = None
-    if not args.no_extras and not args.no_verify:
+    if gate and not args.no_extras:
         # the extras need the memory (cfg3: 64 GiB in, 64 GiB framed, 64 GiB
         # decoded): drop the headline buffers and the context's scratch
         # (87 GB of lane tables); the extras run on a context of their own
@@ -884,7 +903,7 @@ def main():
         # profile of the same workload and labelled as such
         traffic = traffic_d = None
         traffic_measured, traffic_note = False, None
-        if world == 1 and not args.no_pmc and not args.no_verify:
+        if gate and world == 1 and not args.no_pmc:
             try:
                 # (the headline context's 87 GB of tables are still held:
                 # the child runs need that memory)
@@ -1007,7 +1026,7 @@ def main():
             line["INVALID"] = (f"oversubscribed: {world} ranks on one GPU over "
                                "gloo - a proof of the N > 1 code, not a "
                                "measurement")
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(rnd)
         print(json.dumps(line), flush=True)
     if world > 1:

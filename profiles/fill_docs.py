@@ -50,7 +50,7 @@ def sizes(key, n=1):
 
 
 txt = [F[k] for k in ("6_txt1", "7_txt2", "8_txt3", "9_txt4")]
-design = f"""**Results** (1× MI355X, one box, one `python bench.py` of the final sources:
+design = f"""**Results** (1× MI355X, one box, one `python bench.py --full` of the final sources:
 `profiles/r6_final_bench.json`, `source_sha16` {d['source_sha16']}; the GPU suite ran green in the same
 session, `r6_final_gpu_suite.txt`: {passed} passed, and `smoke()` behind it; `r6_final_kernel_stats.md` /
 `r6_final_bench_under_rocprof.json`: `k_match_both` {ks['k_match_both']:.3f} ms by rocprof against {rp['kernel_ms']['compress_dominant']:.3f} by the HIP
@@ -79,7 +79,7 @@ earlier sources: 123.1, 124.3, 125.65 (`r6_v1_*`) - the box decides ±1 %.  This
 | `extras.budget`: 75 / 33 / 15 % budgets, then `snapmi_ctx_prepare(TOP_OF_MEMORY)` as the FOURTH context of a process that has allocated and freed hundreds of GB | | {g(B['pct75']['compress_gibs'])} / {g(B['pct33']['compress_gibs'])} / {g(B['pct15']['compress_gibs'])}, {g(B['prepared_top_of_memory']['compress_gibs'])} | the chunks hold their rate wherever they are asked (63.6-71.7 over the round's runs at 15 %, where the budget has no room for chunks); the far end of the memory is the far end only in a process that asks first (56.5-71.8 here; `r6_budget_chunks.txt`: 71.6-71.8 in a fresh process) - which is what the call is documented for |
 """
 
-readme = f"""## Results (1× MI355X, device resident; ONE box, one `python bench.py` of the round's last sources: `profiles/r6_final_bench.json`, `DESIGN.md` §6)
+readme = f"""## Results (1× MI355X, device resident; ONE box, one `python bench.py --full` of the round's last sources: `profiles/r6_final_bench.json`, `DESIGN.md` §6)
 
 | workload | compress | decompress |
 |---|---|---|

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""After `tests/hw/final_profile.sh r6_final` on the GPU box (gpurun merges
-gpurun_out/ back): copy the set into profiles/r6_final_*, rewrite
+"""After `tests/hw/final_profile.sh r6_final` on the GPU box (its profile_out/
+copied back here): copy the set into profiles/r6_final_*, rewrite
 r6_pmc_traffic.json from the line's own roofline.traffic, and print the
 figures the documents quote.
 
@@ -13,7 +13,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 tag = sys.argv[1] if len(sys.argv) > 1 else "r6_final"
-G, P = ROOT / "gpurun_out", ROOT / "profiles"
+G, P = ROOT / "profile_out", ROOT / "profiles"
 pairs = {f"bench_{tag}.json": f"{tag}_bench.json",
          f"kernel_stats_{tag}.md": f"{tag}_kernel_stats.md",
          f"prof_{tag}_bench.json": f"{tag}_bench_under_rocprof.json",

@@ -68,7 +68,7 @@ def test_more_gpus_than_devices_is_refused():
 def test_committed_final_bench_line_is_of_this_tree():
     """Round 5 landed placement code after its last full bench run, and the
     driver's record then held a row nobody had seen.  The final line of a
-    round (profiles/r6_final_bench.json: one default `python bench.py` on one
+    round (profiles/r6_final_bench.json: one `python bench.py --full` on one
     box) says which sources it measured - `source_sha16`, sha256 over the
     kernels, the C ABI, the Python mirror, bench.py and bench_configs.py - and
     this test compares it with the tree: code that lands behind the last full

@@ -36,14 +36,15 @@ def test_gatherv_over_the_c_abi_world_1(ctx):
 
 
 def test_two_ranks_oversubscribed_on_one_gpu():
-    """`python bench.py --gpus 2 --oversubscribe`: the N > 1 branches of
-    bench.py and of bench_configs.py::cfg4 (spawn, process group, barriers,
-    MAX over ranks, per-rank gather, the sharded frame encode and its gather,
-    the children's process group of their own), with real kernels."""
+    """`python bench.py --gpus 2 --oversubscribe --full`: the N > 1 branches
+    of bench.py and of bench_configs.py::cfg4 (spawn, process group,
+    barriers, MAX over ranks, per-rank gather, the sharded frame encode and
+    its gather, the children's process group of their own), with real
+    kernels."""
     p = subprocess.run(
         [sys.executable, str(ROOT / "bench.py"), "--gpus", "2",
          "--oversubscribe", "--gib", "0.5", "--steps", "2", "--warmup", "1",
-         "--no-cpu"], capture_output=True, text=True, timeout=600)
+         "--full", "--no-cpu"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]     # one line, from rank 0

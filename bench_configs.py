@@ -985,6 +985,134 @@ def cfg4(args, ctx, dev):
     return res
 
 
+def frames_batch(args, ctx, dev):
+    """Many framed streams per call (frame.compress_many_ptrs /
+    decompress_many_ptrs: snapmi_frame_compress_batch / _decompress_batch)
+    against a loop of one-stream calls over the same streams
+    (snapmi_frame_compress / snapmi_frame_decompress) and against the raw
+    batch calls over the same inputs (the floor: no headers, no CRC, no
+    walk).  Two sets: 4 096 streams of 16 KiB of corpus text, and 512 streams
+    of 100 B .. 1 MiB (log-uniform) of the same text.  All three are timed in
+    this process on the same context."""
+    import random
+    import oracle_lib as O
+    from rust_snappy_amd import _lib, batch, frame, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+
+    def piece(n):
+        o = rng.randrange(len(text) - n)
+        return text[o:o + n]
+    sets = {"text_4096x16k": [piece(16384) for _ in range(4096)],
+            "mixed_512_100b_1m": [piece(int(100 * (10486 ** rng.random())))
+                                  for _ in range(512)]}
+    L = _lib.of(ctx)
+    res = {"config": "frames_batch: n framed streams per call vs n one-stream "
+                     "calls vs the raw batch floor",
+           "steps": args.steps}
+    for key, datas in sets.items():
+        n = len(datas)
+        nbytes = sum(len(d) for d in datas)
+        src = batch.StreamBatch.from_bytes(datas, dev)
+        fout = batch.StreamBatch.empty(
+            [frame.frame_max_len(len(d)) for d in datas], dev)
+        flens = torch.zeros(n, dtype=torch.int64, device=dev)
+        ferrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+
+        def f_enc():
+            frame.compress_many_ptrs(ctx, src.d_ptrs, src.d_lens, fout.d_ptrs,
+                                     fout.d_lens, flens, ferrs,
+                                     host_in_lens=src.h_lens)
+        f_enc()
+        ctx.synchronize()
+        fl = flens.cpu().numpy()
+        assert all(e[0] == 0 for e in batch.read_errors(ferrs))
+        for i in (0, n // 2, n - 1):
+            assert fout.stream_bytes(i, fl[i]) == O.frame_compress(datas[i])
+        framed = batch.StreamBatch(fout.data, fout.offsets, fl)
+        back = batch.StreamBatch.empty([len(d) for d in datas], dev)
+        blens = torch.zeros(n, dtype=torch.int64, device=dev)
+        berrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+
+        def f_dec():
+            frame.decompress_many_ptrs(ctx, framed.d_ptrs, framed.d_lens,
+                                       back.d_ptrs, back.d_lens, blens, berrs)
+        f_dec()
+        ctx.synchronize()
+        assert all(e[0] == 0 for e in batch.read_errors(berrs))
+        for i in (0, n // 2, n - 1):
+            assert back.stream_bytes(i, blens[i]) == datas[i]
+        # the loop of one-stream calls (addresses prepared beforehand)
+        in_a = [src.data.data_ptr() + int(o) for o in src.offsets]
+        fo_a = [fout.data.data_ptr() + int(o) for o in fout.offsets]
+        bo_a = [back.data.data_ptr() + int(o) for o in back.offsets]
+        lens_in = [len(d) for d in datas]
+        caps = [int(c) for c in fout.lens]
+        flen_l = [int(x) for x in fl]
+        one_len = torch.zeros(n, dtype=torch.int64, device=dev)
+        one_err = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+        la, ea = one_len.data_ptr(), one_err.data_ptr()
+        s_out = batch.StreamBatch.empty(caps, dev)
+        so_a = [s_out.data.data_ptr() + int(o) for o in s_out.offsets]
+
+        def s_enc():
+            for i in range(n):
+                L.snapmi_frame_compress(ctx._h, in_a[i], lens_in[i], so_a[i],
+                                        caps[i], la + 8 * i, None)
+
+        def s_dec():
+            for i in range(n):
+                L.snapmi_frame_decompress(ctx._h, fo_a[i], flen_l[i], bo_a[i],
+                                          lens_in[i], la + 8 * i,
+                                          ea + 32 * i, None, 0)
+        s_enc()
+        ctx.synchronize()
+        assert s_out.stream_bytes(n - 1, int(one_len[n - 1])) == \
+            fout.stream_bytes(n - 1, fl[n - 1])
+        # the raw floor
+        rout = batch.StreamBatch.empty(
+            [raw.max_compress_len(len(d)) for d in datas], dev)
+        rlens = torch.zeros(n, dtype=torch.int64, device=dev)
+        rback = batch.StreamBatch.empty(lens_in, dev)
+        rblens = torch.zeros(n, dtype=torch.int64, device=dev)
+
+        def r_enc():
+            raw.compress_batch(ctx, src.d_ptrs, src.d_lens, rout.d_ptrs,
+                               rout.d_lens, rlens, None,
+                               host_in_lens=src.h_lens)
+
+        def r_dec():
+            raw.decompress_batch(ctx, rout.d_ptrs, rlens, rback.d_ptrs,
+                                 rback.d_lens, rblens, None)
+        r_enc()
+        ctx.synchronize()
+        t = {}
+        for name, fn in (("batch_enc", f_enc), ("batch_dec", f_dec),
+                         ("single_enc", s_enc), ("single_dec", s_dec),
+                         ("raw_enc", r_enc), ("raw_dec", r_dec)):
+            t[name] = time_it(fn, args.steps, ctx)
+        assert back.stream_bytes(n - 1, blens[n - 1]) == datas[n - 1]
+        assert rback.stream_bytes(n - 1) == datas[n - 1]
+        res[key] = {
+            "streams": n, "bytes": nbytes,
+            "ms": {k: round(v * 1e3, 3) for k, v in t.items()},
+            "batch_gibs": {"compress": round(nbytes / GIB / t["batch_enc"], 2),
+                           "decompress": round(nbytes / GIB / t["batch_dec"],
+                                               2)},
+            "batch_over_single_loop_speedup": {
+                "compress": round(t["single_enc"] / t["batch_enc"], 1),
+                "decompress": round(t["single_dec"] / t["batch_dec"], 1)},
+            "batch_over_raw_floor": {
+                "compress": round(t["batch_enc"] / t["raw_enc"], 2),
+                "decompress": round(t["batch_dec"] / t["raw_dec"], 2)},
+            "single_call_us": {
+                "compress": round(t["single_enc"] / n * 1e6, 1),
+                "decompress": round(t["single_dec"] / n * 1e6, 1)}}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=8.0)
@@ -1016,7 +1144,8 @@ def main():
         ctx.set_option(name, int(value))
     table = {"cfg3": cfg3, "cfg5": cfg5, "files": files, "pcie": pcie,
              "adapters": adapters, "stream": stream, "cfg4": cfg4,
-             "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam}
+             "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
+             "frames_batch": frames_batch}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1034,9 +1163,11 @@ def main():
         return
     for name, fn in (("cfg3", cfg3), ("cfg5", cfg5), ("files", files),
                      ("pcie", pcie), ("adapters", adapters),
-                     ("stream", stream), ("cfg4", cfg4)):
-        if args.only != name and (args.only or name == "cfg4"):
-            continue  # cfg4 only on request (it is the multi-rank config)
+                     ("stream", stream), ("cfg4", cfg4),
+                     ("frames_batch", frames_batch)):
+        if args.only != name and (args.only or name in ("cfg4",
+                                                         "frames_batch")):
+            continue  # cfg4 (the multi-rank config), frames_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:
             print(json.dumps(res), flush=True)

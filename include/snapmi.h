@@ -433,8 +433,9 @@ SNAPMI_API int snapmi_last_timing(snapmi_ctx *ctx, snapmi_timing *out);
 /* ------------------------------------------------------------------ */
 /* 4. Snappy frame format on the device (reference src/frame.rs,        */
 /*    src/crc32.rs, src/write.rs, src/read.rs).  One framed stream per  */
-/*    call; every <=64 KiB chunk is an independent raw stream, so the   */
-/*    chunk is the parallel unit.  All d_* pointers are device memory.  */
+/*    call, or many independent ones per call (the *_batch calls);      */
+/*    every <=64 KiB chunk is an independent raw stream, so the chunk   */
+/*    is the parallel unit.  All d_* pointers are device memory.        */
 /*    Asynchronous like the batch calls.                                */
 /* ------------------------------------------------------------------ */
 
@@ -474,6 +475,64 @@ SNAPMI_API int snapmi_frame_decompress(snapmi_ctx *ctx, const void *d_in,
                             uint64_t *d_out_len, snapmi_error *d_err,
                             const uint64_t *d_chunk_offsets,
                             uint64_t n_chunks);
+
+/*
+ * n independent framed streams per call, in the shape of the raw batch calls
+ * of section 3.  Stream i's result is exactly what the one-stream call gives
+ * for stream i alone; the batch adds nothing and no stream affects another.
+ * The chunks of all streams are compressed / decoded as one list.
+ *
+ * snapmi_frame_compress_batch: stream i == snapmi_frame_compress(
+ * d_in_ptrs[i], d_in_lens[i]), i.e. one write::FrameEncoder::write_all(input)
+ * followed by into_inner() (reference src/write.rs:123-192, src/frame.rs:62-104).
+ *   h_in_lens      host copy of d_in_lens (sizes the launches); NULL = fetched
+ *                  with a blocking D2H
+ *   d_out_caps     NULL = not checked; else cap_i < snapmi_frame_max_len(len_i)
+ *                  (len_i > 0) makes stream i fail with SNAPMI_BUFFER_TOO_SMALL
+ *                  {a = cap_i, b = snapmi_frame_max_len(len_i)}, d_out_lens[i]
+ *                  = 0 and nothing written to d_out_ptrs[i]
+ *   d_out_lens[i]  framed length (0 for an empty input: the identifier is
+ *                  written lazily, src/write.rs:154-170)
+ *   d_errs         per-stream snapmi_error; may be NULL
+ * Asynchronous (enqueue-only) like snapmi_compress_batch, except for the
+ * blocking D2H of a NULL h_in_lens.
+ *
+ * snapmi_frame_decompress_batch: for every i, d_out_lens[i], d_errs[i] and
+ * the bytes d_out_ptrs[i][0, d_out_lens[i]) equal what
+ * snapmi_frame_decompress(stream i, d_out_ptrs[i], d_out_caps[i], no index)
+ * gives, i.e. one read::FrameDecoder over the stream (reference
+ * src/read.rs:105-238): the first error in stream order, the bytes in front
+ * of the failing chunk, BufferTooSmall {cap, total} when the output does not
+ * fit (then nothing is decoded).  Every stream starts a fresh reader.
+ *   d_out_ptrs     NULL = lengths only (d_out == NULL of the one-stream
+ *                  call); d_out_caps may then be NULL
+ *   d_errs         may be NULL
+ * Waits once for the context's stream (the count of data chunks sizes the
+ * decode), so it is not enqueue-only and cannot be captured into a hipGraph.
+ * The chunk headers of a stream are walked by one thread (~0.7 us per
+ * chunk): a stream of many thousands of chunks is better decoded on its own
+ * with snapmi_frame_decompress, whose walk is parallel.
+ *
+ * Both: n and the total number of chunks below 2^31 (else SNAPMI_E_ARGUMENT
+ * and snapmi_last_error); n == 0 enqueues nothing.  snapmi_last_kernel and
+ * snapmi_last_timing describe the raw codec launch over the chunk list, as
+ * for the one-stream frame calls.
+ */
+SNAPMI_API int snapmi_frame_compress_batch(snapmi_ctx *ctx,
+                                const void *const *d_in_ptrs,
+                                const uint64_t *d_in_lens,
+                                const uint64_t *h_in_lens,
+                                void *const *d_out_ptrs,
+                                const uint64_t *d_out_caps,
+                                uint64_t *d_out_lens, snapmi_error *d_errs,
+                                size_t n);
+SNAPMI_API int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
+                                  const void *const *d_in_ptrs,
+                                  const uint64_t *d_in_lens,
+                                  void *const *d_out_ptrs,
+                                  const uint64_t *d_out_caps,
+                                  uint64_t *d_out_lens, snapmi_error *d_errs,
+                                  size_t n);
 
 /* flags of the frame entry points below */
 #define SNAPMI_FRAME_NO_IDENT 1u     /* compress: do not emit the identifier */

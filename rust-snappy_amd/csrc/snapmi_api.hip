@@ -285,7 +285,7 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
                       &ctx->st_desc, &ctx->st_prof, &ctx->ticket,
                       &ctx->order, &ctx->fr_tables, &ctx->fr_desc,
                       &ctx->fr_meta, &ctx->fr_scan, &ctx->fr_slots,
-                      &ctx->fr_chunk_off,
+                      &ctx->fr_chunk_off, &ctx->fb_streams, &ctx->fb_chunks,
                       &ctx->tokens, &ctx->tok_pages, &ctx->tok_stage,
                       &ctx->ntok, &ctx->sched,
                       &ctx->lane_epochs, &ctx->sd_tables, &ctx->sd_desc,
@@ -770,6 +770,7 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
               &ctx->st_out, &ctx->st_desc, &ctx->st_prof, &ctx->ticket,
               &ctx->order, &ctx->fr_tables, &ctx->fr_desc, &ctx->fr_meta,
               &ctx->fr_scan, &ctx->fr_slots, &ctx->fr_chunk_off,
+              &ctx->fb_streams, &ctx->fb_chunks,
               &ctx->tokens, &ctx->tok_pages, &ctx->tok_stage, &ctx->ntok,
               &ctx->sched,
               &ctx->lane_epochs, &ctx->sd_tables, &ctx->sd_desc,

@@ -195,6 +195,8 @@ struct snapmi_ctx {
     size_t pin_bl2_cap = 0;
     // frame layer scratch (snapmi_frame.hip)
     snapmi::DevBuf fr_tables, fr_desc, fr_meta, fr_scan, fr_slots, fr_chunk_off;
+    // snapmi_frame_decompress_batch: per-stream and per-chunk scratch
+    snapmi::DevBuf fb_streams, fb_chunks;
     bool fr_tables_ready = false;
     // framed streams of at least this many bytes without a side index get
     // their chunk headers found in parallel (k_fw_*); shorter ones are walked

@@ -223,6 +223,30 @@ __global__ __launch_bounds__(1024) void k_scan_u64(const uint64_t *in,
         out[n] = carry;
 }
 
+// one chunk at o: header (src/frame.rs:91-93) by thread 0, then the payload
+// from `from` by the whole workgroup
+__device__ inline void frame_put_chunk(gptr o, bool stored, uint64_t payload,
+                                       uint32_t crc, gcptr from)
+{
+    if (threadIdx.x == 0) {
+        const uint32_t cl = 4 + (uint32_t)payload;
+        o[0] = stored ? 0x01 : 0x00;
+        o[1] = (uint8_t)cl;
+        o[2] = (uint8_t)(cl >> 8);
+        o[3] = (uint8_t)(cl >> 16);
+        o[4] = (uint8_t)crc;
+        o[5] = (uint8_t)(crc >> 8);
+        o[6] = (uint8_t)(crc >> 16);
+        o[7] = (uint8_t)(crc >> 24);
+    }
+    gptr to = o + 8;
+    for (uint64_t k = 4 * threadIdx.x; k + 4 <= payload; k += 4 * blockDim.x)
+        st32u(to + k, ld32u(from + k));
+    const uint64_t t = payload & ~3ull;
+    if (threadIdx.x < (payload & 3))
+        to[t + threadIdx.x] = from[t + threadIdx.x];
+}
+
 // one workgroup per chunk: header (src/frame.rs:91-93) + payload
 __global__ __launch_bounds__(256) void k_frame_emit(FrameCompressArgs a)
 {
@@ -239,17 +263,10 @@ __global__ __launch_bounds__(256) void k_frame_emit(FrameCompressArgs a)
                                    'N',  'a',  'P',  'p',  'Y'};
         ((gptr)a.out)[threadIdx.x] = ident[threadIdx.x];
     }
+    frame_put_chunk(o, stored, payload, a.crcs[i],
+                    stored ? (gcptr)a.in_ptrs[i]
+                           : (gcptr)(a.slots + (uint64_t)i * kFrameSlot));
     if (threadIdx.x == 0) {
-        const uint32_t cl = 4 + (uint32_t)payload;
-        const uint32_t crc = a.crcs[i];
-        o[0] = stored ? 0x01 : 0x00;
-        o[1] = (uint8_t)cl;
-        o[2] = (uint8_t)(cl >> 8);
-        o[3] = (uint8_t)(cl >> 16);
-        o[4] = (uint8_t)crc;
-        o[5] = (uint8_t)(crc >> 8);
-        o[6] = (uint8_t)(crc >> 16);
-        o[7] = (uint8_t)(crc >> 24);
         const uint64_t end = a.ident + a.base[0] + a.offs[a.cnt];
         if (a.chunk_offsets) {
             a.chunk_offsets[gi] = at;
@@ -259,14 +276,6 @@ __global__ __launch_bounds__(256) void k_frame_emit(FrameCompressArgs a)
         if (gi + 1 == a.n)
             a.out_len[0] = end;
     }
-    gcptr from = stored ? (gcptr)a.in_ptrs[i]
-                        : (gcptr)(a.slots + (uint64_t)i * kFrameSlot);
-    gptr to = o + 8;
-    for (uint64_t k = 4 * threadIdx.x; k + 4 <= payload; k += 4 * blockDim.x)
-        st32u(to + k, ld32u(from + k));
-    const uint64_t t = payload & ~3ull;
-    if (threadIdx.x < (payload & 3))
-        to[t + threadIdx.x] = from[t + threadIdx.x];
 }
 
 // after a segment's emit: carry its bytes into the next segment's offsets
@@ -320,16 +329,15 @@ struct FrameDecodeArgs {
     unsigned long long fw_seg; // segment bytes (32 MiB; smaller in tests)
 };
 
-__device__ inline void walk_fail(const FrameDecodeArgs &a, uint32_t n_data,
-                                 int kind, uint64_t fa, uint64_t fb)
+__device__ inline snapmi_error frame_err(int kind, uint64_t fa, uint64_t fb)
 {
-    a.serr[0].kind = kind;
-    a.serr[0].reserved = 0;
-    a.serr[0].a = fa;
-    a.serr[0].b = fb;
-    a.serr[0].c = 0;
-    a.meta[0] = n_data;
-    a.meta[2] = n_data;
+    snapmi_error e;
+    e.kind = kind;
+    e.reserved = 0;
+    e.a = fa;
+    e.b = fb;
+    e.c = 0;
+    return e;
 }
 
 // A compressed chunk whose payload is shorter than 10 bytes and holds no
@@ -343,14 +351,15 @@ __device__ inline void walk_fail(const FrameDecodeArgs &a, uint32_t n_data,
 // length is acceptable - whatever Decoder::decompress says about the real
 // payload: Empty or Header (src/decompress.rs:80-83).  Rare and always an
 // error, so the model of src[0..10) is rebuilt here by walking the stream
-// again from its start up to `stop` (the offset of this chunk's header).
-__device__ inline void frame_short_varint(const FrameDecodeArgs &a,
-                                          uint64_t stop, uint32_t n_data)
+// `in` again from its start up to `stop` (the offset of this chunk's header);
+// `stale` is src[0..10) when the walk started.
+__device__ inline snapmi_error frame_short_varint(gcptr in,
+                                                  const uint8_t *stale,
+                                                  uint64_t stop)
 {
-    gcptr in = (gcptr)a.in;
     uint8_t m[10];
     for (int k = 0; k < 10; k++)
-        m[k] = a.stale[k];
+        m[k] = stale[k];
     uint64_t r = 0;
     for (;;) { // every chunk before `stop` was accepted by the walk
         const uint32_t hd = ld32u(in + r);
@@ -387,13 +396,13 @@ __device__ inline void frame_short_varint(const FrameDecodeArgs &a,
     }
     const uint64_t sn = (ld32u(in + stop) >> 8) - 4;
     if (!ok)
-        walk_fail(a, n_data, SNAPMI_HEADER, 0, 0);
-    else if (v > kMaxInput)
-        walk_fail(a, n_data, SNAPMI_TOO_BIG, v, kMaxInput);
-    else if (v > kMaxBlock) // read.rs:217-222
-        walk_fail(a, n_data, SNAPMI_UNSUPPORTED_CHUNK_LENGTH, v, 0);
-    else // Decoder::decompress(&src[0..sn]), src/decompress.rs:80-83
-        walk_fail(a, n_data, sn == 0 ? SNAPMI_EMPTY : SNAPMI_HEADER, 0, 0);
+        return frame_err(SNAPMI_HEADER, 0, 0);
+    if (v > kMaxInput)
+        return frame_err(SNAPMI_TOO_BIG, v, kMaxInput);
+    if (v > kMaxBlock) // read.rs:217-222
+        return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, v, 0);
+    // Decoder::decompress(&src[0..sn]), src/decompress.rs:80-83
+    return frame_err(sn == 0 ? SNAPMI_EMPTY : SNAPMI_HEADER, 0, 0);
 }
 
 // true when the payload [p, p + pl) needs frame_short_varint
@@ -565,62 +574,50 @@ __global__ void k_fw_emit(FrameDecodeArgs a)
     }
 }
 
-// Sequential walk over the chunk headers: reference FrameDecoder::read,
-// src/read.rs:111-236 (checks in the reference's order).  One thread: every
-// hop depends on the previous header.
-__global__ void k_frame_walk(FrameDecodeArgs a)
+// Sequential walk over the chunk headers of one framed stream
+// in[0, in_len): reference FrameDecoder::read, src/read.rs:111-236 (checks
+// in the reference's order; `flags` and `stale` as in
+// snapmi_frame_decompress_ex).  Every hop depends on the previous header, so
+// a stream is walked by one thread.  on_data(k, chunk) is called for data
+// chunk k (0, 1, ...) in front of the first structural error; returns that
+// error (kind SNAPMI_OK at a clean end) and *nd = the data chunks in front
+// of it.
+template <class OnData>
+__device__ inline snapmi_error frame_walk(gcptr in, uint64_t in_len,
+                                          uint32_t flags,
+                                          const uint8_t *stale, uint32_t &nd,
+                                          OnData on_data)
 {
-    if (blockIdx.x || threadIdx.x)
-        return;
-    gcptr in = (gcptr)a.in;
     uint64_t r = 0;
-    uint32_t nd = 0;
-    bool seen_ident = (a.flags & SNAPMI_FRAME_CONTINUATION) != 0;
-    a.meta[1] = 0;
-    a.meta[2] = 0xFFFFFFFFu;
-    a.meta[3] = 0;
-    a.serr[0].kind = SNAPMI_OK;
+    nd = 0;
+    bool seen_ident = (flags & SNAPMI_FRAME_CONTINUATION) != 0;
     for (;;) {
-        if (r == a.in_len)
-            break; // clean EOF, :119-121
-        if (a.in_len - r < 4) {
-            walk_fail(a, nd, SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-            return;
-        }
+        if (r == in_len)
+            return frame_err(SNAPMI_OK, 0, 0); // clean EOF, :119-121
+        if (in_len - r < 4)
+            return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
         const uint32_t hd = ld32u(in + r);
         r += 4;
         const uint32_t ty = hd & 0xFF;
         const uint64_t len = hd >> 8;
         if (!seen_ident) { // :123-128
-            if (ty != 0xFF) {
-                walk_fail(a, nd, SNAPMI_STREAM_HEADER, ty, 0);
-                return;
-            }
+            if (ty != 0xFF)
+                return frame_err(SNAPMI_STREAM_HEADER, ty, 0);
             seen_ident = true;
         }
-        if (len > kMaxChunk) { // :129-135
-            walk_fail(a, nd, SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 0);
-            return;
-        }
-        if (ty >= 0x02 && ty <= 0x7F) { // :138-142
-            walk_fail(a, nd, SNAPMI_UNSUPPORTED_CHUNK_TYPE, ty, 0);
-            return;
-        }
+        if (len > kMaxChunk) // :129-135
+            return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 0);
+        if (ty >= 0x02 && ty <= 0x7F) // :138-142
+            return frame_err(SNAPMI_UNSUPPORTED_CHUNK_TYPE, ty, 0);
         if ((ty >= 0x80 && ty <= 0xFD) || ty == 0xFE) { // skippable, padding
-            if (a.in_len - r < len) {
-                walk_fail(a, nd, SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-                return;
-            }
+            if (in_len - r < len)
+                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
             r += len;
         } else if (ty == 0xFF) { // :159-172
-            if (len != 6) {
-                walk_fail(a, nd, SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 1);
-                return;
-            }
-            if (a.in_len - r < 6) {
-                walk_fail(a, nd, SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-                return;
-            }
+            if (len != 6)
+                return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 1);
+            if (in_len - r < 6)
+                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
             const uint8_t body[6] = {'s', 'N', 'a', 'P', 'p', 'Y'};
             uint64_t got = 0;
             bool same = true;
@@ -629,51 +626,57 @@ __global__ void k_frame_walk(FrameDecodeArgs a)
                 got |= (uint64_t)b << (8 * k);
                 same = same && b == body[k];
             }
-            if (!same) {
-                walk_fail(a, nd, SNAPMI_STREAM_HEADER_MISMATCH, got, 0);
-                return;
-            }
+            if (!same)
+                return frame_err(SNAPMI_STREAM_HEADER_MISMATCH, got, 0);
             r += 6;
         } else { // 0x00 compressed / 0x01 stored: :173-235
-            if (len < 4) {
-                walk_fail(a, nd, SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 0);
-                return;
-            }
-            if (a.in_len - r < 4) {
-                walk_fail(a, nd, SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-                return;
-            }
+            if (len < 4)
+                return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 0);
+            if (in_len - r < 4)
+                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
             const uint32_t crc = ld32u(in + r);
             r += 4;
             const uint64_t pl = len - 4;
-            if (ty == 0x01 && pl > kMaxBlock) { // :182-187
-                walk_fail(a, nd, SNAPMI_UNSUPPORTED_CHUNK_LENGTH, pl, 0);
-                return;
-            }
-            if (a.in_len - r < pl) {
-                walk_fail(a, nd, SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-                return;
-            }
-            if (ty == 0x00 && short_varint(in + r, pl)) { // read.rs:216
-                frame_short_varint(a, r - 8, nd);
-                return;
-            }
-            if (nd < a.cap_chunks) {
-                FrameChunk c;
-                c.payload_off = r;
-                c.payload_len = (uint32_t)pl;
-                c.crc = crc;
-                c.type = ty;
-                c.pad = 0;
-                a.chunks[nd] = c;
-            } else {
-                a.meta[1] = 1; // overflow: caller reruns with more room
-            }
+            if (ty == 0x01 && pl > kMaxBlock) // :182-187
+                return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, pl, 0);
+            if (in_len - r < pl)
+                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
+            if (ty == 0x00 && short_varint(in + r, pl)) // read.rs:216
+                return frame_short_varint(in, stale, r - 8);
+            FrameChunk c;
+            c.payload_off = r;
+            c.payload_len = (uint32_t)pl;
+            c.crc = crc;
+            c.type = ty;
+            c.pad = 0;
+            on_data(nd, c);
             nd++;
             r += pl;
         }
     }
+}
+
+// the walk of the one stream of snapmi_frame_decompress[_ex]
+__global__ void k_frame_walk(FrameDecodeArgs a)
+{
+    if (blockIdx.x || threadIdx.x)
+        return;
+    a.meta[1] = 0;
+    a.meta[2] = 0xFFFFFFFFu;
+    a.meta[3] = 0;
+    uint32_t nd;
+    const snapmi_error e = frame_walk(
+        (gcptr)a.in, a.in_len, a.flags, a.stale, nd,
+        [&](uint32_t k, const FrameChunk &c) {
+            if (k < a.cap_chunks)
+                a.chunks[k] = c;
+            else
+                a.meta[1] = 1; // overflow: caller reruns with more room
+        });
+    a.serr[0] = e;
     a.meta[0] = nd;
+    if (e.kind != SNAPMI_OK)
+        a.meta[2] = nd;
 }
 
 // With a side index: chunk i's header is at index[i]; all chunks must be
@@ -736,8 +739,54 @@ __global__ void k_frame_index(FrameDecodeArgs a)
     a.chunks[i] = c;
 }
 
-// decompressed length of every data chunk: reference src/read.rs:181-187
-// (stored) and :215-222 (compressed: decompress_len, then dn <= 65536)
+// decompressed length of data chunk c, whose payload starts at p: reference
+// src/read.rs:181-187 (stored) and :215-222 (compressed: decompress_len, then
+// dn <= 65536); 0 and *e on an error
+__device__ inline uint64_t frame_chunk_len(gcptr p, const FrameChunk &c,
+                                           snapmi_error &e)
+{
+    e = frame_err(SNAPMI_OK, 0, 0);
+    if (c.type > 1) { // only reachable through a bad side index
+        e.kind = SNAPMI_UNSUPPORTED_CHUNK_TYPE;
+        e.a = c.pad;
+        return 0;
+    }
+    if (c.type == 1)
+        return c.payload_len;
+    uint64_t acc = 0;
+    uint32_t shift = 0;
+    bool ok = false;
+    for (uint32_t k = 0; k < c.payload_len; k++) {
+        const uint32_t b = p[k];
+        if (shift >= 64)
+            break;
+        if (b < 0x80) {
+            acc |= (uint64_t)b << shift;
+            ok = true;
+            break;
+        }
+        acc |= (uint64_t)(b & 0x7F) << shift;
+        shift += 7;
+    }
+    if (c.payload_len == 0) {
+        // reference: decompress_len of the scratch reads a stale byte;
+        // the decode of the empty payload then fails with Empty
+        e.kind = SNAPMI_EMPTY;
+    } else if (!ok) {
+        e.kind = SNAPMI_HEADER;
+    } else if (acc > kMaxInput) {
+        e.kind = SNAPMI_TOO_BIG;
+        e.a = acc;
+        e.b = kMaxInput;
+    } else if (acc > kMaxBlock) {
+        e.kind = SNAPMI_UNSUPPORTED_CHUNK_LENGTH;
+        e.a = acc;
+    } else {
+        return acc;
+    }
+    return 0;
+}
+
 __global__ void k_frame_lens(FrameDecodeArgs a)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -746,52 +795,7 @@ __global__ void k_frame_lens(FrameDecodeArgs a)
         return;
     const FrameChunk c = a.chunks[i];
     snapmi_error e;
-    e.kind = SNAPMI_OK;
-    e.reserved = 0;
-    e.a = e.b = e.c = 0;
-    uint64_t dn = 0;
-    if (c.type > 1) { // only reachable through a bad side index
-        e.kind = SNAPMI_UNSUPPORTED_CHUNK_TYPE;
-        e.a = c.pad;
-    } else if (c.type == 1) {
-        dn = c.payload_len;
-    } else {
-        gcptr p = (gcptr)a.in + c.payload_off;
-        uint64_t acc = 0;
-        uint32_t shift = 0, used = 0;
-        bool ok = false;
-        for (uint32_t k = 0; k < c.payload_len; k++) {
-            const uint32_t b = p[k];
-            if (shift >= 64)
-                break;
-            if (b < 0x80) {
-                acc |= (uint64_t)b << shift;
-                used = k + 1;
-                ok = true;
-                break;
-            }
-            acc |= (uint64_t)(b & 0x7F) << shift;
-            shift += 7;
-        }
-        (void)used;
-        if (c.payload_len == 0) {
-            // reference: decompress_len of the scratch reads a stale byte;
-            // the decode of the empty payload then fails with Empty
-            e.kind = SNAPMI_EMPTY;
-        } else if (!ok) {
-            e.kind = SNAPMI_HEADER;
-        } else if (acc > kMaxInput) {
-            e.kind = SNAPMI_TOO_BIG;
-            e.a = acc;
-            e.b = kMaxInput;
-        } else if (acc > kMaxBlock) {
-            e.kind = SNAPMI_UNSUPPORTED_CHUNK_LENGTH;
-            e.a = acc;
-        } else {
-            dn = acc;
-        }
-    }
-    a.dlens[i] = e.kind == SNAPMI_OK ? dn : 0;
+    a.dlens[i] = frame_chunk_len((gcptr)a.in + c.payload_off, c, e);
     a.cerrs[i] = e;
 }
 
@@ -815,8 +819,57 @@ __global__ void k_frame_desc(FrameDecodeArgs a)
     a.out_lens[i] = 0;
 }
 
-// Final verdict: first error in stream order (reference processes chunk by
-// chunk: length checks, raw decode, checksum :225-232 / :189-196).
+// Final verdict of one framed stream of n data chunks: its first error in
+// stream order (the reference processes chunk by chunk: length checks, raw
+// decode, checksum :225-232 / :189-196) and the output bytes reported with
+// it.  first_bad: first chunk with an error in cerrs[] (0xFFFFFFFF = none);
+// sidx: the data chunk the walk's structural error serr precedes; offs[0..n]:
+// output offsets of the chunks (offs[0] need not be 0); has_out: not a
+// lengths-only call; cap: the output's capacity.
+__device__ inline void frame_verdict(uint32_t first_bad, uint32_t sidx,
+                                     uint32_t n, const snapmi_error *cerrs,
+                                     const snapmi_error &serr, bool has_out,
+                                     uint64_t cap, const uint64_t *offs,
+                                     snapmi_error &e, uint64_t &out_len)
+{
+    const uint64_t total = offs[n] - offs[0];
+    const bool decoded = has_out && total <= cap;
+    e = frame_err(SNAPMI_OK, 0, 0);
+    if (first_bad != 0xFFFFFFFFu && first_bad < sidx)
+        e = cerrs[first_bad];
+    else if (serr.kind != SNAPMI_OK)
+        e = serr;
+    else if (has_out && total > cap)
+        e = frame_err(SNAPMI_BUFFER_TOO_SMALL, cap, total);
+    // On an error the chunks in front of the failing one are decoded and
+    // checked: the reference's reader has handed them out by then
+    // (src/read.rs:112-118), so their byte count is reported.
+    uint32_t upto = n;
+    if (e.kind != SNAPMI_OK) {
+        upto = first_bad < sidx ? first_bad : (sidx < n ? sidx : n);
+        if (!decoded)
+            upto = 0;
+    }
+    out_len = offs[upto] - offs[0];
+}
+
+// the decode stage's verdict on data chunk i (already decoded, not failed
+// before): raw decoder error, else checksum mismatch; false if it is good
+__device__ inline bool frame_chunk_decode_err(const snapmi_error &derr,
+                                              uint32_t stored_crc,
+                                              uint32_t crc, snapmi_error &e)
+{
+    if (derr.kind != SNAPMI_OK) {
+        e = derr;
+        return true;
+    }
+    if (crc != stored_crc) {
+        e = frame_err(SNAPMI_CHECKSUM, stored_crc, crc);
+        return true;
+    }
+    return false;
+}
+
 __global__ __launch_bounds__(1024) void k_frame_verify(FrameDecodeArgs a,
                                                        const snapmi_error *derrs)
 {
@@ -828,52 +881,310 @@ __global__ __launch_bounds__(1024) void k_frame_verify(FrameDecodeArgs a,
     const bool decoded = a.out != nullptr && a.offs[n] <= a.out_cap;
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
         bool bad = a.cerrs[i].kind != SNAPMI_OK;
-        if (!bad && decoded) {
-            if (derrs[i].kind != SNAPMI_OK) {
-                a.cerrs[i] = derrs[i];
-                bad = true;
-            } else if (a.crcs[i] != a.chunks[i].crc) {
-                snapmi_error e;
-                e.kind = SNAPMI_CHECKSUM;
-                e.reserved = 0;
-                e.a = a.chunks[i].crc;
-                e.b = a.crcs[i];
-                e.c = 0;
-                a.cerrs[i] = e;
-                bad = true;
-            }
-        }
+        if (!bad && decoded)
+            bad = frame_chunk_decode_err(derrs[i], a.chunks[i].crc,
+                                         a.crcs[i], a.cerrs[i]);
         if (bad)
             atomicMin(&first_bad, i);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const uint32_t sidx = a.meta[2]; // structural error before chunk sidx
         snapmi_error e;
-        e.kind = SNAPMI_OK;
-        e.reserved = 0;
-        e.a = e.b = e.c = 0;
-        if (first_bad != 0xFFFFFFFFu && first_bad < sidx)
-            e = a.cerrs[first_bad];
-        else if (a.serr[0].kind != SNAPMI_OK)
-            e = a.serr[0];
-        else if (a.out != nullptr && a.offs[n] > a.out_cap) {
-            e.kind = SNAPMI_BUFFER_TOO_SMALL;
-            e.a = a.out_cap;
-            e.b = a.offs[n];
-        }
+        uint64_t len;
+        frame_verdict(first_bad, a.meta[2], n, a.cerrs, a.serr[0],
+                      a.out != nullptr, a.out_cap, a.offs, e, len);
         a.err[0] = e;
-        // On an error the chunks in front of the failing one are decoded and
-        // checked: the reference's reader has handed them out by then
-        // (src/read.rs:112-118), so their byte count is reported.
-        uint32_t upto = n;
-        if (e.kind != SNAPMI_OK) {
-            upto = first_bad < sidx ? first_bad : (sidx < n ? sidx : n);
-            if (!decoded)
-                upto = 0;
-        }
-        a.out_len[0] = a.offs[upto];
+        a.out_len[0] = len;
     }
+}
+
+// ---------------------------------------------------------------------
+// Many framed streams per call (snapmi_frame_compress_batch /
+// snapmi_frame_decompress_batch).  The chunks of all streams form one list
+// (stream i owns chunks [first[i], first[i+1])), the codec kernels run over
+// that list as above, and the results map back to each stream: a chunk's
+// output position is its offset in the list's output minus the offset of its
+// stream's first chunk.
+// ---------------------------------------------------------------------
+struct FrameBatchCompressArgs {
+    const void *const *in_ptrs;
+    const uint64_t *in_lens;
+    void *const *out_ptrs;
+    const uint64_t *out_caps; // nullptr = not checked
+    uint64_t *out_lens;
+    snapmi_error *errs; // nullptr = not reported
+    uint32_t n, total, seg; // streams, chunks, chunks per segment
+    uint64_t *counts;       // [n] chunks per stream
+    uint64_t *first;        // [n+1] exclusive scan of counts
+    uint8_t *refused;       // [n] stream fails the capacity check
+    uint64_t *sbase;        // [n] list offset of the stream's first chunk
+    const void **c_in;      // [total] chunk input
+    uint64_t *c_len;
+    uint32_t *c_stream;
+    // the segment [lo, lo + cnt) of the list (per-segment scratch below)
+    uint32_t lo, cnt;
+    uint64_t *carry; // [1] list bytes of the segments in front
+    void **slot_ptrs;
+    uint64_t *clens;
+    uint32_t *crcs;
+    uint64_t *sizes; // 8 + payload; 0 for a refused stream's chunks
+    uint64_t *offs;  // [cnt+1] exclusive scan of sizes
+    uint8_t *slots;
+};
+
+__device__ inline uint64_t frame_max_len_dev(uint64_t n)
+{
+    return 10 + n + 8 * ((n + kMaxBlock - 1) / kMaxBlock);
+}
+
+// stream i has no room: cap_i < snapmi_frame_max_len(len_i) (an empty input
+// writes nothing and needs none, as snapmi_frame_compress)
+__device__ inline bool fb_refused(const FrameBatchCompressArgs &a, uint32_t i)
+{
+    const uint64_t len = a.in_lens[i];
+    return a.out_caps && len && a.out_caps[i] < frame_max_len_dev(len);
+}
+
+__global__ void k_fb_counts(FrameBatchCompressArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n)
+        a.counts[i] = (a.in_lens[i] + kMaxBlock - 1) / kMaxBlock;
+}
+
+// the stream owning list entry t: the last i with first[i] <= t
+__device__ inline uint32_t fb_stream_of(const uint64_t *first, uint32_t n,
+                                        uint32_t t)
+{
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (first[mid] <= t)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// thread t: stream t's capacity check and result slots, list entry t's
+// chunk descriptor, segment slot t's pointer
+__global__ void k_fb_chunks(FrameBatchCompressArgs a)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.n) {
+        const bool r = fb_refused(a, t);
+        a.refused[t] = r;
+        a.out_lens[t] = 0;
+        if (a.errs)
+            a.errs[t] = r ? frame_err(SNAPMI_BUFFER_TOO_SMALL, a.out_caps[t],
+                                      frame_max_len_dev(a.in_lens[t]))
+                          : frame_err(SNAPMI_OK, 0, 0);
+    }
+    if (t < a.total) {
+        const uint32_t i = fb_stream_of(a.first, a.n, t);
+        const uint64_t off = (t - a.first[i]) * (uint64_t)kMaxBlock;
+        const uint64_t len = a.in_lens[i] - off;
+        a.c_in[t] = (const uint8_t *)a.in_ptrs[i] + off;
+        a.c_len[t] = len < kMaxBlock ? len : kMaxBlock;
+        a.c_stream[t] = i;
+    }
+    if (t < a.seg)
+        a.slot_ptrs[t] = a.slots + (uint64_t)t * kFrameSlot;
+}
+
+// reference compress_frame, src/frame.rs:83-89; nothing for a refused stream
+__global__ void k_fb_sizes(FrameBatchCompressArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.cnt)
+        return;
+    const uint32_t gi = a.lo + i;
+    const uint64_t len = a.c_len[gi];
+    const uint64_t clen = a.clens[i];
+    const bool stored = clen >= len - len / 8;
+    a.sizes[i] = a.refused[a.c_stream[gi]] ? 0 : 8 + (stored ? len : clen);
+}
+
+// The list offset of every stream whose first chunk lies in this segment,
+// fixed before the segment's emit (which reads it in other workgroups; a
+// stream that started in an earlier segment has it already).
+__global__ void k_fb_base(FrameBatchCompressArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.cnt)
+        return;
+    const uint32_t gi = a.lo + i;
+    const uint32_t s = a.c_stream[gi];
+    if (a.first[s] == gi)
+        a.sbase[s] = a.carry[0] + a.offs[i];
+}
+
+// one workgroup per chunk of the segment: the stream identifier (first
+// chunk), header (src/frame.rs:91-93) and payload at the chunk's offset in
+// its stream; the stream's last chunk writes its length
+__global__ __launch_bounds__(256) void k_fb_emit(FrameBatchCompressArgs a)
+{
+    const uint32_t i = blockIdx.x;
+    const uint32_t gi = a.lo + i;
+    const uint32_t s = a.c_stream[gi];
+    if (a.refused[s])
+        return;
+    const uint64_t len = a.c_len[gi];
+    const uint64_t clen = a.clens[i];
+    const bool stored = clen >= len - len / 8;
+    const uint64_t payload = stored ? len : clen;
+    const uint64_t at = 10 + a.carry[0] + a.offs[i] - a.sbase[s];
+    gptr base = (gptr)a.out_ptrs[s];
+    gptr o = base + at;
+    if (gi == a.first[s] && threadIdx.x < 10) {
+        const uint8_t ident[10] = {0xFF, 0x06, 0x00, 0x00, 's',
+                                   'N',  'a',  'P',  'p',  'Y'};
+        base[threadIdx.x] = ident[threadIdx.x];
+    }
+    frame_put_chunk(o, stored, payload, a.crcs[i],
+                    stored ? (gcptr)a.c_in[gi]
+                           : (gcptr)(a.slots + (uint64_t)i * kFrameSlot));
+    if (threadIdx.x == 0 && gi + 1 == a.first[s + 1])
+        a.out_lens[s] = at + 8 + payload;
+}
+
+__global__ void k_fb_advance(FrameBatchCompressArgs a)
+{
+    a.carry[0] += a.offs[a.cnt];
+}
+
+struct FrameBatchDecodeArgs {
+    const void *const *in_ptrs;
+    const uint64_t *in_lens;
+    void *const *out_ptrs; // nullptr = lengths only
+    const uint64_t *out_caps;
+    uint64_t *out_lens;
+    snapmi_error *errs; // nullptr = not reported
+    uint32_t n, total;  // streams, data chunks of all streams
+    // per stream
+    uint64_t *counts;     // [n] data chunks in front of the walk's error
+    uint64_t *first;      // [n+1] exclusive scan of counts
+    snapmi_error *serr;   // [n] the walk's structural error
+    uint32_t *sidx;       // [n] data chunk it precedes (0xFFFFFFFF = none)
+    uint32_t *first_bad;  // [n] first chunk with an error
+    // per data chunk of the list
+    FrameChunk *chunks;
+    uint32_t *c_stream;
+    uint64_t *dlens;
+    uint64_t *offs; // [total+1] exclusive scan of dlens
+    snapmi_error *cerrs;
+    snapmi_error *derrs;
+    const void **c_in;
+    uint64_t *c_in_len;
+    void **c_out;
+    uint64_t *c_caps;
+    uint64_t *c_out_lens;
+    uint8_t *modes;
+    uint32_t *crcs;
+};
+
+// pass 1: one thread per stream (a wavefront walks 64 streams) counts the
+// data chunks in front of the stream's first structural error
+__global__ __launch_bounds__(64) void k_fbd_walk_count(FrameBatchDecodeArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n)
+        return;
+    const uint8_t fresh[10] = {0}; // every stream of a batch starts fresh
+    uint32_t nd;
+    const snapmi_error e =
+        frame_walk((gcptr)a.in_ptrs[i], a.in_lens[i], 0, fresh, nd,
+                   [](uint32_t, const FrameChunk &) {});
+    a.counts[i] = nd;
+    a.serr[i] = e;
+    a.sidx[i] = e.kind != SNAPMI_OK ? nd : 0xFFFFFFFFu;
+}
+
+// pass 2: the same walk writes the chunk records at the stream's place
+__global__ __launch_bounds__(64) void k_fbd_walk_fill(FrameBatchDecodeArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n || a.counts[i] == 0)
+        return;
+    const uint8_t fresh[10] = {0};
+    const uint64_t base = a.first[i];
+    const uint64_t cnt = a.counts[i];
+    uint32_t nd;
+    frame_walk((gcptr)a.in_ptrs[i], a.in_lens[i], 0, fresh, nd,
+               [&](uint32_t k, const FrameChunk &c) {
+                   if (k < cnt) {
+                       a.chunks[base + k] = c;
+                       a.c_stream[base + k] = i;
+                   }
+               });
+}
+
+__global__ void k_fbd_lens(FrameBatchDecodeArgs a)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.total)
+        return;
+    const FrameChunk ch = a.chunks[c];
+    gcptr in = (gcptr)a.in_ptrs[a.c_stream[c]];
+    snapmi_error e;
+    a.dlens[c] = frame_chunk_len(in + ch.payload_off, ch, e);
+    a.cerrs[c] = e;
+}
+
+// does stream s's output fit its buffer?
+__device__ inline bool fbd_fits(const FrameBatchDecodeArgs &a, uint32_t s)
+{
+    const uint64_t b = a.first[s], e = a.first[s + 1];
+    return a.offs[e] - a.offs[b] <= a.out_caps[s];
+}
+
+// descriptors for the raw decompressor, as k_frame_desc per stream
+__global__ void k_fbd_desc(FrameBatchDecodeArgs a)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.total)
+        return;
+    const uint32_t s = a.c_stream[c];
+    const FrameChunk ch = a.chunks[c];
+    const bool skip = a.cerrs[c].kind != SNAPMI_OK || !fbd_fits(a, s);
+    a.c_in[c] = (const uint8_t *)a.in_ptrs[s] + ch.payload_off;
+    a.c_in_len[c] = skip ? 0 : ch.payload_len;
+    a.modes[c] = skip ? 1 : (uint8_t)ch.type;
+    a.c_out[c] = (uint8_t *)a.out_ptrs[s] + (a.offs[c] - a.offs[a.first[s]]);
+    a.c_caps[c] = a.dlens[c];
+    a.c_out_lens[c] = 0;
+}
+
+// per chunk: the decode stage's verdict, and the first bad chunk per stream
+__global__ void k_fbd_verify_chunks(FrameBatchDecodeArgs a)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.total)
+        return;
+    const uint32_t s = a.c_stream[c];
+    bool bad = a.cerrs[c].kind != SNAPMI_OK;
+    if (!bad && a.out_ptrs && fbd_fits(a, s))
+        bad = frame_chunk_decode_err(a.derrs[c], a.chunks[c].crc, a.crcs[c],
+                                     a.cerrs[c]);
+    if (bad)
+        atomicMin(&a.first_bad[s], (uint32_t)(c - a.first[s]));
+}
+
+__global__ void k_fbd_verify_streams(FrameBatchDecodeArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n)
+        return;
+    const uint64_t b = a.first[i];
+    snapmi_error e;
+    uint64_t len;
+    frame_verdict(a.first_bad[i], a.sidx[i], (uint32_t)(a.first[i + 1] - b),
+                  a.cerrs + b, a.serr[i], a.out_ptrs != nullptr,
+                  a.out_ptrs ? a.out_caps[i] : 0, a.offs + b, e, len);
+    if (a.errs)
+        a.errs[i] = e;
+    a.out_lens[i] = len;
 }
 
 // ---------------------------------------------------------------------
@@ -1493,6 +1804,244 @@ int snapmi_frame_decompress(snapmi_ctx *ctx, const void *d_in,
     return snapmi_frame_decompress_ex(ctx, d_in, in_len, d_out, out_cap,
                                       d_out_len, d_err, d_chunk_offsets,
                                       n_chunks, 0, nullptr);
+}
+
+int snapmi_frame_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
+                                const uint64_t *d_in_lens,
+                                const uint64_t *h_in_lens,
+                                void *const *d_out_ptrs,
+                                const uint64_t *d_out_caps,
+                                uint64_t *d_out_lens, snapmi_error *d_errs,
+                                size_t n)
+{
+    if (!ctx)
+        return SNAPMI_E_ARGUMENT;
+    if (n == 0)
+        return SNAPMI_OK;
+    if (!d_in_ptrs || !d_in_lens || !d_out_ptrs || !d_out_lens)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame_compress_batch: bad args");
+    if (n > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame_compress_batch: %zu streams (at most 2^31 - 1)",
+                        n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::vector<uint64_t> fetched;
+    if (!h_in_lens) {
+        fetched.resize(n);
+        HIP_TRY(ctx, hipMemcpyAsync(fetched.data(), d_in_lens,
+                                    n * sizeof(uint64_t),
+                                    hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        h_in_lens = fetched.data();
+    }
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++)
+        total += (h_in_lens[i] + kMaxBlock - 1) / kMaxBlock;
+    if (total > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame_compress_batch: %llu chunks (at most 2^31 - 1)",
+                        (unsigned long long)total);
+    // segments of the list as in frame_compress_impl; per segment the chunks
+    // of at most 8 KiB for the compressor's routing (only a stream's last
+    // chunk can be one)
+    const uint32_t seg = total < ctx->lane_segment_blocks
+                             ? (uint32_t)total
+                             : ctx->lane_segment_blocks;
+    std::vector<uint64_t> c8(seg ? (total + seg - 1) / seg : 0, 0);
+    for (uint64_t i = 0, at = 0; i < n; i++) {
+        const uint64_t len = h_in_lens[i];
+        const uint64_t k = (len + kMaxBlock - 1) / kMaxBlock;
+        if (k && len - (k - 1) * kMaxBlock <= 8192)
+            c8[(at + k - 1) / seg]++;
+        at += k;
+    }
+    int rc = ensure_tables(ctx);
+    if (rc)
+        return rc;
+    const size_t bytes = n * (8 + 8 + 1 + 8) + 8 + total * (8 + 8 + 4) +
+                         (size_t)seg * (8 + 8 + 4 + 8 + 8) + 8 + 8 + 16 * 16;
+    if ((rc = reserve(ctx, ctx->fr_desc, bytes)) ||
+        (seg && (rc = reserve(ctx, ctx->fr_slots, (size_t)seg * kFrameSlot))))
+        return rc;
+    FrameBatchCompressArgs a;
+    uint8_t *p = (uint8_t *)ctx->fr_desc.p;
+    a.in_ptrs = d_in_ptrs;
+    a.in_lens = d_in_lens;
+    a.out_ptrs = d_out_ptrs;
+    a.out_caps = d_out_caps;
+    a.out_lens = d_out_lens;
+    a.errs = d_errs;
+    a.n = (uint32_t)n;
+    a.total = (uint32_t)total;
+    a.seg = seg;
+    a.counts = carve<uint64_t>(p, n);
+    a.first = carve<uint64_t>(p, n + 1);
+    a.refused = carve<uint8_t>(p, n);
+    a.sbase = carve<uint64_t>(p, n);
+    a.c_in = carve<const void *>(p, total);
+    a.c_len = carve<uint64_t>(p, total);
+    a.c_stream = carve<uint32_t>(p, total);
+    a.carry = carve<uint64_t>(p, 1);
+    a.slot_ptrs = carve<void *>(p, seg);
+    a.clens = carve<uint64_t>(p, seg);
+    a.crcs = carve<uint32_t>(p, seg);
+    a.sizes = carve<uint64_t>(p, seg);
+    a.offs = carve<uint64_t>(p, (size_t)seg + 1);
+    a.slots = (uint8_t *)ctx->fr_slots.p;
+    a.lo = a.cnt = 0;
+
+    const uint32_t tb = 256;
+    uint64_t most = total > n ? total : n;
+    HIP_TRY(ctx, hipMemsetAsync(a.carry, 0, sizeof(uint64_t), s));
+    hipLaunchKernelGGL(k_fb_counts, dim3((uint32_t)((n + tb - 1) / tb)),
+                       dim3(tb), 0, s, a);
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.counts,
+                       a.first, (uint32_t)n);
+    hipLaunchKernelGGL(k_fb_chunks, dim3((uint32_t)((most + tb - 1) / tb)),
+                       dim3(tb), 0, s, a);
+    for (uint32_t lo = 0; lo < total; lo += seg) {
+        const uint32_t cnt = total - lo < seg ? (uint32_t)total - lo : seg;
+        a.lo = lo;
+        a.cnt = cnt;
+        const uint32_t gb = (cnt + tb - 1) / tb;
+        // (the CRC beside the compressor, as in frame_compress_impl)
+        const bool side = ctx->frame_crc_side_stream;
+        if (side) {
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_crc[0], s));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_crc[0], 0));
+        }
+        hipLaunchKernelGGL(k_crc32c, dim3(cnt), dim3(64), 0,
+                           side ? ctx->stream2 : s, a.c_in + lo, a.c_len + lo,
+                           a.crcs, cnt, (const CrcTables *)ctx->fr_tables.p);
+        if (side)
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_crc[1], ctx->stream2));
+        rc = launch_compress(ctx, a.c_in + lo, a.c_len + lo, a.slot_ptrs,
+                             nullptr, a.clens, nullptr, cnt, cnt, 0, 0xF,
+                             c8[lo / seg]);
+        if (rc)
+            return rc;
+        if (side)
+            HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_crc[1], 0));
+        hipLaunchKernelGGL(k_fb_sizes, dim3(gb), dim3(tb), 0, s, a);
+        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.sizes,
+                           a.offs, cnt);
+        hipLaunchKernelGGL(k_fb_base, dim3(gb), dim3(tb), 0, s, a);
+        hipLaunchKernelGGL(k_fb_emit, dim3(cnt), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_fb_advance, dim3(1), dim3(1), 0, s, a);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return SNAPMI_OK;
+}
+
+int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
+                                  const void *const *d_in_ptrs,
+                                  const uint64_t *d_in_lens,
+                                  void *const *d_out_ptrs,
+                                  const uint64_t *d_out_caps,
+                                  uint64_t *d_out_lens, snapmi_error *d_errs,
+                                  size_t n)
+{
+    if (!ctx)
+        return SNAPMI_E_ARGUMENT;
+    if (n == 0)
+        return SNAPMI_OK;
+    if (!d_in_ptrs || !d_in_lens || !d_out_lens || (d_out_ptrs && !d_out_caps))
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame_decompress_batch: bad args");
+    if (n > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame_decompress_batch: %zu streams (at most 2^31 - "
+                        "1)", n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int rc = ensure_tables(ctx);
+    if (rc)
+        return rc;
+    // per-stream scratch and per-chunk scratch in two buffers: the second is
+    // sized after the walk, and growing it must not drop the first
+    if ((rc = reserve(ctx, ctx->fb_streams,
+                      n * (8 + 8 + sizeof(snapmi_error) + 4 + 4) + 8 +
+                          16 * 8)) ||
+        (rc = mailbox(ctx)))
+        return rc;
+    FrameBatchDecodeArgs a;
+    uint8_t *p = (uint8_t *)ctx->fb_streams.p;
+    a.in_ptrs = d_in_ptrs;
+    a.in_lens = d_in_lens;
+    a.out_ptrs = d_out_ptrs;
+    a.out_caps = d_out_caps;
+    a.out_lens = d_out_lens;
+    a.errs = d_errs;
+    a.n = (uint32_t)n;
+    a.total = 0;
+    a.counts = carve<uint64_t>(p, n);
+    a.first = carve<uint64_t>(p, n + 1);
+    a.serr = carve<snapmi_error>(p, n);
+    a.sidx = carve<uint32_t>(p, n);
+    a.first_bad = carve<uint32_t>(p, n);
+    const uint32_t gs = (uint32_t)((n + 63) / 64);
+    hipLaunchKernelGGL(k_fbd_walk_count, dim3(gs), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.counts,
+                       a.first, (uint32_t)n);
+    // the one wait: the number of data chunks sizes everything below
+    hipLaunchKernelGGL(k_post_words, dim3(1), dim3(64), 0, s,
+                       (uint32_t *)ctx->h_mail, (const uint32_t *)(a.first + n),
+                       2u);
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    const uint64_t total =
+        (uint64_t)ctx->h_mail[0] | ((uint64_t)ctx->h_mail[1] << 32);
+    if (total > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame_decompress_batch: %llu chunks (at most 2^31 - "
+                        "1)", (unsigned long long)total);
+    const size_t t = (size_t)total;
+    if ((rc = reserve(ctx, ctx->fb_chunks,
+                      t * (sizeof(FrameChunk) + 4 + 8 + 8 +
+                           2 * sizeof(snapmi_error) + 8 + 8 + 8 + 8 + 8 + 1 +
+                           4) + 8 + 16 * 16)))
+        return rc;
+    p = (uint8_t *)ctx->fb_chunks.p;
+    a.total = (uint32_t)total;
+    a.chunks = carve<FrameChunk>(p, t);
+    a.c_stream = carve<uint32_t>(p, t);
+    a.dlens = carve<uint64_t>(p, t);
+    a.offs = carve<uint64_t>(p, t + 1);
+    a.cerrs = carve<snapmi_error>(p, t);
+    a.derrs = carve<snapmi_error>(p, t);
+    a.c_in = carve<const void *>(p, t);
+    a.c_in_len = carve<uint64_t>(p, t);
+    a.c_out = carve<void *>(p, t);
+    a.c_caps = carve<uint64_t>(p, t);
+    a.c_out_lens = carve<uint64_t>(p, t);
+    a.modes = carve<uint8_t>(p, t);
+    a.crcs = carve<uint32_t>(p, t);
+    HIP_TRY(ctx, hipMemsetAsync(a.first_bad, 0xFF, n * sizeof(uint32_t), s));
+    const uint32_t tb = 256;
+    const uint32_t gc = total ? (uint32_t)((total + tb - 1) / tb) : 1;
+    if (total) {
+        hipLaunchKernelGGL(k_fbd_walk_fill, dim3(gs), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_fbd_lens, dim3(gc), dim3(tb), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.dlens, a.offs,
+                       a.total);
+    if (d_out_ptrs && total) {
+        hipLaunchKernelGGL(k_fbd_desc, dim3(gc), dim3(tb), 0, s, a);
+        rc = launch_decompress(ctx, a.c_in, a.c_in_len, a.c_out, a.c_caps,
+                               a.c_out_lens, a.derrs, a.modes, t);
+        if (rc)
+            return rc;
+        hipLaunchKernelGGL(k_crc32c, dim3(a.total), dim3(64), 0, s,
+                           (const void *const *)a.c_out, a.c_out_lens, a.crcs,
+                           a.total, (const CrcTables *)ctx->fr_tables.p);
+    }
+    if (total)
+        hipLaunchKernelGGL(k_fbd_verify_chunks, dim3(gc), dim3(tb), 0, s, a);
+    hipLaunchKernelGGL(k_fbd_verify_streams,
+                       dim3((uint32_t)((n + tb - 1) / tb)), dim3(tb), 0, s, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNAPMI_OK;
 }
 
 // ----------------------------------------------------------------------

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, raw
+from . import batch as _batch
 from .error import Error
 
 STREAM_IDENTIFIER = b"\xff\x06\x00\x00sNaPpY"   # reference src/frame.rs:18
@@ -167,6 +168,73 @@ def decompress_batch_device(ctx, d_in, n_in, n_chunks, index=None,
     e = _err_tuple(err)
     good = out[:int(out_len.item())].cpu().numpy().tobytes()
     return good, (Error(*e) if e[0] else None)
+
+
+def compress_many_ptrs(ctx, in_ptrs, in_lens, out_ptrs, out_caps, out_lens,
+                       errs=None, host_in_lens=None):
+    """snapmi_frame_compress_batch: n independent framed streams, arguments as
+    raw.compress_batch (out_caps None = not checked).  Enqueue-only."""
+    n = in_ptrs.numel()
+    h = C.c_void_p(host_in_lens.data_ptr()) if host_in_lens is not None \
+        else None
+    rc = _lib.of(ctx).snapmi_frame_compress_batch(
+        ctx._h, raw._ptr(in_ptrs), raw._ptr(in_lens), h, raw._ptr(out_ptrs),
+        raw._ptr(out_caps), raw._ptr(out_lens), raw._ptr(errs), n)
+    if rc:
+        raw._raise(ctx, rc)
+
+
+def decompress_many_ptrs(ctx, in_ptrs, in_lens, out_ptrs, out_caps,
+                         out_lens, errs=None):
+    """snapmi_frame_decompress_batch: n independent framed streams, arguments
+    as raw.decompress_batch (out_ptrs None = lengths only).  Waits once for
+    the context's stream."""
+    n = in_ptrs.numel()
+    rc = _lib.of(ctx).snapmi_frame_decompress_batch(
+        ctx._h, raw._ptr(in_ptrs), raw._ptr(in_lens), raw._ptr(out_ptrs),
+        raw._ptr(out_caps), raw._ptr(out_lens), raw._ptr(errs), n)
+    if rc:
+        raw._raise(ctx, rc)
+
+
+def compress_many(ctx, src, check_caps=True, caps=None):
+    """Frame-compress every stream of `src` (a batch.StreamBatch) in one call:
+    stream i is what compress_device gives for it alone.  Output capacities
+    are frame_max_len(len_i) unless `caps` says otherwise.  Returns (dst
+    StreamBatch, out_lens, errs as (kind, a, b, c) tuples)."""
+    if caps is None:
+        caps = [frame_max_len(int(n)) for n in src.lens]
+    dev = src.data.device
+    dst = _batch.StreamBatch.empty(caps, dev)
+    out_lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+    errs = torch.zeros(32 * src.n, dtype=torch.uint8, device=dev)
+    compress_many_ptrs(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs,
+                       dst.d_lens if check_caps else None, out_lens, errs,
+                       host_in_lens=src.h_lens)
+    ctx.synchronize()
+    return dst, out_lens.cpu().numpy(), _batch.read_errors(errs)
+
+
+def decompress_many(ctx, src, caps=None):
+    """Frame-decompress every stream of `src` (a batch.StreamBatch) in one
+    call: stream i's length, error and bytes are those of one
+    snapmi_frame_decompress of it with capacity caps[i].  caps=None: a
+    lengths-only pass sizes the outputs first (like batch.decompress), so a
+    stream that pass rejects gets no room and reports what it reported.
+    Returns (dst StreamBatch, out_lens, errs as (kind, a, b, c) tuples)."""
+    dev = src.data.device
+    out_lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+    errs = torch.zeros(32 * src.n, dtype=torch.uint8, device=dev)
+    if caps is None:
+        decompress_many_ptrs(ctx, src.d_ptrs, src.d_lens, None, None,
+                             out_lens, errs)
+        ctx.synchronize()
+        caps = out_lens.cpu().numpy()
+    dst = _batch.StreamBatch.empty(caps, dev)
+    decompress_many_ptrs(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs, dst.d_lens,
+                         out_lens, errs)
+    ctx.synchronize()
+    return dst, out_lens.cpu().numpy(), _batch.read_errors(errs)
 
 
 def encode_host(ctx, data, chunk_lens, ident=True):

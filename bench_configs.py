@@ -1113,6 +1113,231 @@ def frames_batch(args, ctx, dev):
     return res
 
 
+def host_batch(args, ctx, dev):
+    """Many raw streams in HOST memory per call (snapmi_compress_batch_host /
+    snapmi_decompress_batch_host) from pageable and from pinned buffers,
+    against a loop of snapmi_raw_compress / snapmi_raw_decompress over the
+    same buffers (timed on the first `loop_streams` streams and scaled), the
+    device-resident batch calls on the same data (the kernel floor) and the
+    host-to-host rate of `pcie` (the link floor).  Three sets: 4 096 streams
+    of 16 KiB of corpus text, 65 536 of 4 KiB, 512 of 100 B .. 1 MiB
+    (log-uniform).  Then the sweeps the defaults were chosen from: the slice
+    size, and - with the test build (SNAPMI_TESTING=1) - the direct-copy
+    threshold and where k_hb_pack stores."""
+    import random
+    import oracle_lib as O
+    from rust_snappy_amd import _lib, batch, frame, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+
+    def piece(n):
+        o = rng.randrange(len(text) - n)
+        return text[o:o + n]
+    sets = {"text_4096x16k": [piece(16384) for _ in range(4096)],
+            "text_65536x4k": [piece(4096) for _ in range(65536)],
+            "mixed_512_100b_1m": [piece(int(100 * (10486 ** rng.random())))
+                                  for _ in range(512)]}
+    L = _lib.of(ctx)
+    has_test = hasattr(L, "snapmi_ctx_set_test_option")
+
+    class Arena:
+        """buffers of the given sizes, 64 bytes apart at least, in one
+        pageable array or one snapmi_host_alloc allocation"""
+
+        def __init__(self, sizes, pinned):
+            sizes = np.asarray(sizes, dtype=np.uint64)
+            step = (sizes + np.uint64(127)) // np.uint64(64) * np.uint64(64)
+            self.offs = np.concatenate(([0], np.cumsum(step)[:-1])).astype(
+                np.uint64)
+            total = int(step.sum()) + 64
+            self.host = frame.HostBuffer(total) if pinned else None
+            self.arr = self.host.array if pinned \
+                else np.zeros(total, dtype=np.uint8)
+            self.arr[:] = 0
+            self.ptrs = self.offs + np.uint64(self.arr.ctypes.data)
+            self.sizes = sizes
+
+        def fill(self, datas):
+            for o, d in zip(self.offs, datas):
+                self.arr[int(o):int(o) + len(d)] = np.frombuffer(
+                    d, dtype=np.uint8)
+
+        def bytes(self, i, n):
+            o = int(self.offs[i])
+            return self.arr[o:o + int(n)].tobytes()
+
+        def close(self):
+            if self.host is not None:
+                self.arr = None
+                self.host.close()
+
+    def measure(datas, pinned, steps):
+        n = len(datas)
+        lens = np.array([len(d) for d in datas], dtype=np.uint64)
+        caps = np.array([raw.max_compress_len(len(d)) for d in datas],
+                        dtype=np.uint64)
+        src, comp, back = Arena(lens, pinned), Arena(caps, pinned), \
+            Arena(lens, pinned)
+        src.fill(datas)
+        state = {}
+
+        def enc():
+            state["clens"], state["errs"] = raw.batch_host(
+                ctx, True, src.ptrs, lens, comp.ptrs, caps)
+        enc()
+        assert not state["errs"]["kind"].any()
+        clens = state["clens"]
+        for i in (0, n // 2, n - 1):
+            assert comp.bytes(i, clens[i]) == O.compress(datas[i])
+        info = {k: ctx.info("host_batch_" + k)
+                for k in ("slices", "h2d_bytes", "d2h_bytes")}
+
+        def dec():
+            state["blens"], state["errs"] = raw.batch_host(
+                ctx, False, comp.ptrs, clens, back.ptrs, lens)
+        dec()
+        assert not state["errs"]["kind"].any()
+        assert np.array_equal(state["blens"], lens)
+        assert np.array_equal(back.arr, src.arr), "host batch round trip"
+        out = {"compress_ms": time_it(enc, steps, ctx) * 1e3,
+               "decompress_ms": time_it(dec, steps, ctx) * 1e3,
+               "compress_info": info, "compressed_bytes": int(clens.sum())}
+        keep = (src, comp, back, lens, caps, clens)
+        return out, keep
+
+    def loop_of_scalar_calls(keep, k):
+        src, comp, back, lens, caps, clens = keep
+        w, err = C.c_size_t(0), _lib.SnapmiError()
+        a = [(int(src.ptrs[i]), int(lens[i]), int(comp.ptrs[i]), int(caps[i]),
+              int(clens[i]), int(back.ptrs[i])) for i in range(k)]
+
+        def s_enc():
+            for sp, sl, cp, cc, _, _ in a:
+                L.snapmi_raw_compress(ctx._h, C.c_char_p(sp), sl, cp, cc,
+                                      C.byref(w), C.byref(err))
+
+        def s_dec():
+            for sp, sl, cp, cc, cl, bp in a:
+                L.snapmi_raw_decompress(ctx._h, C.c_char_p(cp), cl, bp, sl,
+                                        C.byref(w), C.byref(err))
+        return time_it(s_enc, 1, ctx), time_it(s_dec, 1, ctx)
+
+    import ctypes as C
+    res = {"config": "host_batch: n raw streams in host memory per call vs a "
+                     "loop of scalar calls, the device-resident batch and "
+                     "the link", "steps": args.steps,
+           "defaults": {"host_batch_slice": 16 << 20,
+                        "host_batch_direct_min": 1 << 20,
+                        "host_batch_pack_to_host": 1}}
+    try:
+        gib = args.gib
+        args.gib = 0.5
+        link = pcie(args, ctx, dev)
+        args.gib = gib
+        res["link_floor_pcie"] = {k: link[k] for k in (
+            "gib", "frame_encode_gibs", "frame_decode_gibs")}
+    except Exception as e:  # noqa: BLE001 - reported, not hidden
+        res["link_floor_pcie"] = {"error": f"{type(e).__name__}: {e}"[:200]}
+    for key, datas in sets.items():
+        n = len(datas)
+        nbytes = sum(len(d) for d in datas)
+        row = {"streams": n, "bytes": nbytes}
+        for pinned in (False, True):
+            out, keep = measure(datas, pinned, args.steps)
+            name = "pinned" if pinned else "pageable"
+            row[name] = {
+                "compress_ms": round(out["compress_ms"], 3),
+                "decompress_ms": round(out["decompress_ms"], 3),
+                "compress_gibs": round(nbytes / GIB / out["compress_ms"] * 1e3,
+                                       2),
+                "decompress_gibs": round(
+                    nbytes / GIB / out["decompress_ms"] * 1e3, 2)}
+            row["compressed_bytes"] = out["compressed_bytes"]
+            row["compress_info"] = out["compress_info"]
+            if not pinned:
+                k = min(n, 1024)
+                te, td = loop_of_scalar_calls(keep, k)
+                row["scalar_loop"] = {
+                    "loop_streams": k,
+                    "call_us": {"compress": round(te / k * 1e6, 1),
+                                "decompress": round(td / k * 1e6, 1)},
+                    "ms_for_all": {"compress": round(te / k * n * 1e3, 1),
+                                   "decompress": round(td / k * n * 1e3, 1)}}
+                row["host_batch_over_scalar_loop_speedup"] = {
+                    "compress": round(te / k * n * 1e3 / out["compress_ms"], 1),
+                    "decompress": round(
+                        td / k * n * 1e3 / out["decompress_ms"], 1)}
+            for a in keep[:3]:
+                a.close()
+        # the kernel floor: the same streams, device resident
+        src = batch.StreamBatch.from_bytes(datas, dev)
+        rout = batch.StreamBatch.empty(
+            [raw.max_compress_len(len(d)) for d in datas], dev)
+        rlens = torch.zeros(n, dtype=torch.int64, device=dev)
+        rback = batch.StreamBatch.empty([len(d) for d in datas], dev)
+        rblens = torch.zeros(n, dtype=torch.int64, device=dev)
+
+        def r_enc():
+            raw.compress_batch(ctx, src.d_ptrs, src.d_lens, rout.d_ptrs,
+                               rout.d_lens, rlens, None,
+                               host_in_lens=src.h_lens)
+
+        def r_dec():
+            raw.decompress_batch(ctx, rout.d_ptrs, rlens, rback.d_ptrs,
+                                 rback.d_lens, rblens, None)
+        r_enc()
+        ctx.synchronize()
+        te, td = time_it(r_enc, args.steps, ctx), time_it(r_dec, args.steps,
+                                                          ctx)
+        assert rback.stream_bytes(n - 1) == datas[n - 1]
+        row["device_resident_batch"] = {
+            "compress_ms": round(te * 1e3, 3),
+            "decompress_ms": round(td * 1e3, 3),
+            "compress_gibs": round(nbytes / GIB / te, 2),
+            "decompress_gibs": round(nbytes / GIB / td, 2)}
+        del src, rout, rback
+        res[key] = row
+
+    # the sweeps behind the defaults (pinned buffers; two steps each)
+    def sweep(datas, pinned, setter, values):
+        out = {}
+        for v in values:
+            setter(v)
+            m, keep = measure(datas, pinned, 2)
+            out[str(v)] = {"compress_ms": round(m["compress_ms"], 3),
+                           "decompress_ms": round(m["decompress_ms"], 3)}
+            for a in keep[:3]:
+                a.close()
+        return out
+    sw = {}
+    for key in ("text_4096x16k", "text_65536x4k"):
+        sw["host_batch_slice/" + key] = sweep(
+            sets[key], True, lambda v: ctx.set_option("host_batch_slice", v),
+            [1 << 20, 4 << 20, 16 << 20, 64 << 20])
+    ctx.set_option("host_batch_slice", 16 << 20)
+    if has_test:
+        for pinned in (False, True):
+            sw["host_batch_direct_min/mixed_512_100b_1m/" +
+               ("pinned" if pinned else "pageable")] = sweep(
+                sets["mixed_512_100b_1m"], pinned,
+                lambda v: ctx.set_test_option("host_batch_direct_min", v),
+                [64 << 10, 256 << 10, 1 << 20, 1 << 40])
+        ctx.set_test_option("host_batch_direct_min", 1 << 20)
+        for key in ("text_4096x16k", "text_65536x4k"):
+            sw["host_batch_pack_to_host/" + key] = sweep(
+                sets[key], True,
+                lambda v: ctx.set_test_option("host_batch_pack_to_host", v),
+                [0, 1])
+        ctx.set_test_option("host_batch_pack_to_host", 1)
+    else:
+        sw["host_batch_direct_min"] = sw["host_batch_pack_to_host"] = \
+            "test options: run with SNAPMI_TESTING=1"
+    res["sweeps"] = sw
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=8.0)
@@ -1145,7 +1370,7 @@ def main():
     table = {"cfg3": cfg3, "cfg5": cfg5, "files": files, "pcie": pcie,
              "adapters": adapters, "stream": stream, "cfg4": cfg4,
              "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
-             "frames_batch": frames_batch}
+             "frames_batch": frames_batch, "host_batch": host_batch}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1164,10 +1389,12 @@ def main():
     for name, fn in (("cfg3", cfg3), ("cfg5", cfg5), ("files", files),
                      ("pcie", pcie), ("adapters", adapters),
                      ("stream", stream), ("cfg4", cfg4),
-                     ("frames_batch", frames_batch)):
+                     ("frames_batch", frames_batch),
+                     ("host_batch", host_batch)):
         if args.only != name and (args.only or name in ("cfg4",
-                                                         "frames_batch")):
-            continue  # cfg4 (the multi-rank config), frames_batch: on request
+                                                         "frames_batch",
+                                                         "host_batch")):
+            continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:
             print(json.dumps(res), flush=True)

@@ -264,6 +264,10 @@ SNAPMI_API const char *snapmi_version(void);
  *   "host_copy_kernel"     bit 0 / bit 1: decoded / encoded results go home
  *                          by a copy kernel instead of hipMemcpyAsync when
  *                          the caller's buffer is pinned (default 1)
+ *   "host_batch_slice"     input bytes per slice of snapmi_compress_batch_host
+ *                          / snapmi_decompress_batch_host (default 16 MiB, at
+ *                          least 64 KiB): what bounds their device and pinned
+ *                          staging, three slices of it being in flight
  * The knobs of the test suite and of the experiment drivers are declared in
  * snapmi_test.h (snapmi_ctx_set_test_option).
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
@@ -302,6 +306,12 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *   "token_pages_asked"     pages the last token-path launch asked for, and
  *   "token_blocks_spilled"  blocks of it that found none and were compressed
  *                           a second time (both wait for the launch)
+ *   "host_batch_slices"     slices the last host batch call (section 2b) made
+ *   "host_batch_h2d_bytes"  bytes it copied to the device (descriptors, inputs
+ *                           and their alignment padding) and
+ *   "host_batch_d2h_bytes"  back: one length and one error record per stream
+ *                           and the outputs, packed (compress: what was
+ *                           written, each stream rounded to 16 bytes)
  * SNAPMI_E_ARGUMENT for a name that is not in this list. */
 SNAPMI_API int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name,
                                    int64_t *value);
@@ -326,6 +336,65 @@ SNAPMI_API int snapmi_raw_decompress(snapmi_ctx *ctx, const uint8_t *input,
                           size_t input_len, uint8_t *output,
                           size_t output_cap, size_t *written,
                           snapmi_error *err);
+
+/* ------------------------------------------------------------------ */
+/* 2b. Many independent raw streams in HOST memory per call.            */
+/* ------------------------------------------------------------------ */
+/*
+ * What a loop of snapmi_raw_compress / snapmi_raw_decompress over n buffers
+ * gives, in one blocking call: for every i, h_out_lens[i], h_errs[i] (variant
+ * and fields a, b, c) and the bytes h_out_ptrs[i][0, h_out_lens[i]) are
+ * exactly those of the scalar call on stream i alone with capacity
+ * h_out_caps[i] - one Encoder::compress / Decoder::decompress of the
+ * reference each (src/compress.rs:99-154, src/decompress.rs:75-95).  No
+ * stream affects another.
+ *   a stream that fails   h_out_lens[i] = 0, h_errs[i] says why, and not one
+ *                         byte of h_out_ptrs[i] is written
+ *   a stream that succeeds  exactly [0, h_out_lens[i]) is written, nothing
+ *                         behind it
+ *   return value          failures of the call itself only (SNAPMI_E_DEVICE,
+ *                         SNAPMI_E_ARGUMENT); SNAPMI_OK when the call ran,
+ *                         whatever the streams did
+ *   h_errs                may be NULL
+ *   h_out_caps            may not be NULL (these are host buffers: there is
+ *                         no unchecked mode); compress: cap_i <
+ *                         snapmi_max_compress_len(len_i) is BufferTooSmall
+ *                         {given, min} for stream i; decompress: cap_i <
+ *                         the header's length is BufferTooSmall {cap, n}
+ *   n                     below 2^31; n == 0 does nothing and returns OK
+ * The buffers may be pageable or pinned (snapmi_host_alloc): same results,
+ * other speed.  One context per thread, as everywhere.
+ *
+ * The batch is cut into slices of whole streams (option "host_batch_slice";
+ * a stream larger than a slice is a slice of its own) that overlap: slice
+ * i+1 is packed into pinned staging and sent - descriptors and inputs in one
+ * copy - while the kernels of snapmi_compress_batch / snapmi_decompress_batch
+ * run on slice i and slice i-1 comes home.  Only what was written crosses the
+ * link on the way back: compressed streams are gathered on the device
+ * (k_hb_pack) to 16-byte-aligned packed offsets first.  Info
+ * "host_batch_slices", "host_batch_h2d_bytes", "host_batch_d2h_bytes"
+ * describe the last call.
+ * Measured (profiles/host_batch.json, one MI355X): 4 096 streams of 16 KiB of
+ * text from pageable / pinned buffers 12.1 / 8.1 ms to compress (5.2 / 7.8
+ * GiB/s) and 8.0 / 8.8 ms to decompress, where a loop of scalar calls takes
+ * 1 752 / 805 ms (145x / 100x); 65 536 streams of 4 KiB 44.5 / 41.5 ms
+ * (214x / 138x); 512 streams of 100 B .. 1 MiB 12.1 / 8.3 ms (26x / 22x).
+ * The device-resident batch calls take 1.7 / 0.3 ms on the first set and the
+ * link moved 17.8 / 27.8 GiB/s host to host on that box: one host thread
+ * copies every byte into staging and out of it.
+ */
+SNAPMI_API int snapmi_compress_batch_host(snapmi_ctx *ctx,
+                               const void *const *h_in_ptrs,
+                               const size_t *h_in_lens,
+                               void *const *h_out_ptrs,
+                               const size_t *h_out_caps, size_t *h_out_lens,
+                               snapmi_error *h_errs, size_t n);
+SNAPMI_API int snapmi_decompress_batch_host(snapmi_ctx *ctx,
+                                 const void *const *h_in_ptrs,
+                                 const size_t *h_in_lens,
+                                 void *const *h_out_ptrs,
+                                 const size_t *h_out_caps, size_t *h_out_lens,
+                                 snapmi_error *h_errs, size_t n);
 
 /* ------------------------------------------------------------------ */
 /* 3. Batched device-resident API.  Every d_* pointer is device memory  */

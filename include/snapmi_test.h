@@ -58,6 +58,13 @@ extern "C" {
  *                          suite lowers it to reach the kernel with 40 000)
  *   "frame_walk_segment"   segment of the parallel chunk-header walk (>= 128
  *                          KiB; default 32 MiB)
+ *   "host_batch_direct_min"  the host batch calls copy a stream of at least
+ *                          this many bytes to the device from where it lies
+ *                          instead of through pinned staging (default 1 MiB)
+ *   "host_batch_pack_to_host"  1 (default): k_hb_pack stores the packed
+ *                          output of a compress slice straight into pinned
+ *                          host memory; 0: into device memory, followed by
+ *                          one D2H of exactly that much
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
  */
 SNAPMI_API int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,

@@ -66,6 +66,10 @@ SYMBOLS = [
      [_P, C.c_char_p, _SZ, _P, _SZ, _SZP, _ERRP]),
     ("snapmi_raw_decompress", C.c_int,
      [_P, C.c_char_p, _SZ, _P, _SZ, _SZP, _ERRP]),
+    ("snapmi_compress_batch_host", C.c_int,
+     [_P, _P, _P, _P, _P, _P, _P, _SZ]),
+    ("snapmi_decompress_batch_host", C.c_int,
+     [_P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_decompress_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_decompress_len_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),

@@ -396,6 +396,8 @@ int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
         ctx->host_encode_slice = (uint64_t)value;
     else if (strcmp(name, "host_decode_slice_chunks") == 0 && value >= 1)
         ctx->host_decode_slice_chunks = (uint64_t)value;
+    else if (strcmp(name, "host_batch_slice") == 0 && value >= (1 << 16))
+        ctx->host_batch_slice = (uint64_t)value;
     else if (strcmp(name, "decode_kernel") == 0 &&
              (value == 0 || (value == 2 && kDec2) || value == 3))
         ctx->decode_kernel = ctx->lds_store_order_ok ? (int)value : 0;
@@ -456,6 +458,11 @@ int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
         ctx->stream_scan_segs = (uint32_t)value; // 0: by size
     else if (strcmp(name, "lds_order_ok") == 0 && value >= 0 && value <= 1)
         ctx->lds_order_ok = ctx->lds_order_hw && value != 0; // can only lower
+    else if (strcmp(name, "host_batch_direct_min") == 0 && value >= 0)
+        ctx->host_batch_direct_min = (uint64_t)value;
+    else if (strcmp(name, "host_batch_pack_to_host") == 0 && value >= 0 &&
+             value <= 1)
+        ctx->host_batch_pack_to_host = (int)value;
     else
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "unknown test option %s",
                         name);
@@ -791,6 +798,12 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const volatile uint32_t *t = ctx->h_tokstat;
         *value = !t ? 0 : name[6] == 'p' ? t[0] : t[1];
+    } else if (strcmp(name, "host_batch_slices") == 0) {
+        *value = (int64_t)ctx->hb_slices;
+    } else if (strcmp(name, "host_batch_h2d_bytes") == 0) {
+        *value = (int64_t)ctx->hb_h2d_bytes;
+    } else if (strcmp(name, "host_batch_d2h_bytes") == 0) {
+        *value = (int64_t)ctx->hb_d2h_bytes;
     } else {
         ctx->last_error = std::string("unknown info: ") + name;
         return SNAPMI_E_ARGUMENT;

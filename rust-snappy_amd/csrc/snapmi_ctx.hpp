@@ -43,6 +43,17 @@ struct snapmi_ctx {
     // (snapmi_host_alloc).  Encode: off - the copy kernel would wait for the
     // match finder's persistent workgroups.
     int host_copy_kernel = 1;
+    // the host-memory batch calls (snapmi_hostbatch.hip): input bytes per
+    // slice; streams of at least host_batch_direct_min bytes are copied to
+    // the device from where they lie instead of through the pinned staging;
+    // 1: k_hb_pack stores a compress slice's packed output straight into
+    // pinned host memory, 0: into device memory, followed by one D2H
+    // (measured, profiles/host_batch.json; the last two are test options)
+    uint64_t host_batch_slice = 16ull << 20;
+    uint64_t host_batch_direct_min = 1ull << 20;
+    int host_batch_pack_to_host = 1;
+    // what the last host batch call did: slices, bytes copied each way
+    uint64_t hb_slices = 0, hb_h2d_bytes = 0, hb_d2h_bytes = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
     std::string last_error;

@@ -32,6 +32,7 @@
 
 #include "snapmi.h"
 #include "snapmi_ctx.hpp"
+#include "snapmi_hostpipe.hpp"
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
 
@@ -2057,34 +2058,7 @@ size_t snapmi_frame_encode_bound(size_t total_bytes, size_t n_chunks)
 } // extern "C"
 
 // ---- the pipeline behind the two host-buffer calls -----------------------
-// A batch is cut into slices; slice i+1 is on its way to the device (copy
-// stream 1) while the kernels of slice i run (the context's stream) and the
-// result of slice i-1 goes back to the host (copy stream 2): PCIe is full
-// duplex, and the three legs of a batch cost about the same (a 4 GiB corpus
-// batch: 78 ms in, 60 ms of kernels, 39 ms out - 177 ms one after the other).
-// Three slots of device staging, so that none of the three legs waits for a
-// buffer of the other two.  Host memory from snapmi_host_alloc (pinned) is
-// what makes the copies asynchronous; pageable memory works, one leg at a
-// time.
-namespace {
-constexpr int kSlots = 3;
-struct PipeSlot {
-    snapmi::DevBuf in, out, desc; // desc: u64 len | snapmi_error | index...
-    hipEvent_t ev_h2d = nullptr, ev_k = nullptr, ev_d2h = nullptr;
-    struct Result {
-        uint64_t len;
-        snapmi_error e;
-    } *h_res = nullptr;            // pinned
-    uint64_t *h_off = nullptr;     // pinned: chunk offsets of the slice
-    size_t h_off_cap = 0;
-};
-} // namespace
-
-struct snapmi_host_pipe {
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    PipeSlot slot[kSlots];
-};
-
+// The staging pipeline of the host-buffer calls: snapmi_hostpipe.hpp.
 namespace snapmi {
 void host_pipe_destroy(snapmi_ctx *ctx)
 {
@@ -2100,9 +2074,12 @@ void host_pipe_destroy(snapmi_ctx *ctx)
         (void)hipStreamDestroy(p->s_out);
     }
     for (PipeSlot &sl : p->slot) {
-        for (DevBuf *b : {&sl.in, &sl.out, &sl.desc})
+        for (DevBuf *b : {&sl.in, &sl.out, &sl.desc, &sl.home})
             if (b->p)
                 (void)hipFree(b->p);
+        for (PinBuf *b : {&sl.hb_in, &sl.hb_home})
+            if (b->p)
+                (void)hipHostFree(b->p);
         for (hipEvent_t e : {sl.ev_h2d, sl.ev_k, sl.ev_d2h})
             if (e)
                 (void)hipEventDestroy(e);
@@ -2116,7 +2093,7 @@ void host_pipe_destroy(snapmi_ctx *ctx)
 }
 } // namespace snapmi
 
-static int host_pipe(snapmi_ctx *ctx, snapmi_host_pipe **out)
+int snapmi::host_pipe(snapmi_ctx *ctx, snapmi_host_pipe **out)
 {
     if (!ctx->pipe) {
         snapmi_host_pipe *p = new snapmi_host_pipe;
@@ -2135,27 +2112,6 @@ static int host_pipe(snapmi_ctx *ctx, snapmi_host_pipe **out)
     return SNAPMI_OK;
 }
 
-// Every exit of a host-buffer call that comes after its first asynchronous
-// operation goes through this: an early return (a failed allocation, a
-// capacity check, an error of the codec call) must not hand the caller's
-// buffers back while copies of earlier slices still read or write them, and
-// the next call relies on "the previous call ended with its streams idle".
-namespace {
-struct PipeDrain {
-    snapmi_ctx *ctx;
-    snapmi_host_pipe *pipe;
-    bool armed = true;
-    ~PipeDrain()
-    {
-        if (!armed)
-            return;
-        (void)hipStreamSynchronize(pipe->s_in);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(pipe->s_out);
-    }
-};
-} // namespace
-
 static int slot_offsets(snapmi_ctx *ctx, PipeSlot &sl, size_t n)
 {
     if (n <= sl.h_off_cap)
@@ -2172,7 +2128,7 @@ static int slot_offsets(snapmi_ctx *ctx, PipeSlot &sl, size_t n)
 }
 
 // a slot's device buffer grows only when nothing of the slot is in flight
-static int slot_reserve(snapmi_ctx *ctx, snapmi::DevBuf &b, size_t bytes)
+int snapmi::slot_reserve(snapmi_ctx *ctx, snapmi::DevBuf &b, size_t bytes)
 {
     if (bytes <= b.cap)
         return SNAPMI_OK;
@@ -2185,6 +2141,20 @@ static int slot_reserve(snapmi_ctx *ctx, snapmi::DevBuf &b, size_t bytes)
     const size_t want = bytes + bytes / 8 + 256;
     HIP_TRY(ctx, hipMalloc(&b.p, want));
     b.cap = want;
+    return SNAPMI_OK;
+}
+
+int snapmi::pipe_copy_home(snapmi_ctx *ctx, hipStream_t st, uint8_t *h_dst,
+                           const void *d_src, uint64_t n, bool by_kernel)
+{
+    return copy_home(ctx, st, h_dst, d_src, n, by_kernel);
+}
+
+int snapmi::launch_scan_u64(snapmi_ctx *ctx, hipStream_t st,
+                            const uint64_t *in, uint64_t *out, uint32_t n)
+{
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, in, out, n);
+    HIP_TRY(ctx, hipGetLastError());
     return SNAPMI_OK;
 }
 

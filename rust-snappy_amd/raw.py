@@ -7,11 +7,15 @@
   Decoder().decompress / decompress_vec  reference src/decompress.rs:75-110
 
 plus the batched, device-resident form (`compress_batch`, `decompress_batch`)
-that takes torch CUDA tensors -- torch is only the owner of device memory.
+that takes torch CUDA tensors -- torch is only the owner of device memory --
+and the batched host-memory form (`compress_many`, `decompress_many`) over
+sequences of bytes-like objects.
 All compute happens in the HIP kernels; without a GPU these raise
 `DeviceError`.
 """
 import ctypes as C
+
+import numpy as np
 
 from . import _lib
 from .error import DeviceError, Error
@@ -101,7 +105,8 @@ class Context:
     def info(self, name):
         """snapmi_ctx_get_info: "scratch_bytes", "token_scratch_bytes",
         "token_pool_pages", "token_pool_pct_now", "token_pages_asked",
-        "token_blocks_spilled" (include/snapmi.h)."""
+        "token_blocks_spilled", "host_batch_slices", "host_batch_h2d_bytes",
+        "host_batch_d2h_bytes" (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:
@@ -215,6 +220,94 @@ class Decoder:
         buf = bytearray(decompress_len(data))
         n = self.decompress(data, buf)
         return bytes(buf[:n])
+
+
+# ---------------------------------------------------------------------
+# batched, host memory (section 2b of include/snapmi.h)
+# ---------------------------------------------------------------------
+ERROR_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<u4"), ("a", "<u8"),
+                        ("b", "<u8"), ("c", "<u8")])
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def batch_host(ctx, compress, in_ptrs, in_lens, out_ptrs, out_caps):
+    """snapmi_compress_batch_host / snapmi_decompress_batch_host over arrays of
+    host addresses and lengths (anything np.asarray takes); the buffers behind
+    them are the caller's to keep alive.  Returns (out_lens as uint64 array,
+    errors as an ERROR_DTYPE array)."""
+    in_ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64)
+    in_lens = np.ascontiguousarray(in_lens, dtype=np.uint64)
+    out_ptrs = np.ascontiguousarray(out_ptrs, dtype=np.uint64)
+    out_caps = np.ascontiguousarray(out_caps, dtype=np.uint64)
+    n = int(in_ptrs.size)
+    assert in_lens.size == out_ptrs.size == out_caps.size == n
+    out_lens = np.zeros(n, dtype=np.uint64)
+    errs = np.zeros(n, dtype=ERROR_DTYPE)
+    L = _lib.of(ctx)
+    f = L.snapmi_compress_batch_host if compress \
+        else L.snapmi_decompress_batch_host
+    rc = f(ctx._h, _np_ptr(in_ptrs), _np_ptr(in_lens), _np_ptr(out_ptrs),
+           _np_ptr(out_caps), _np_ptr(out_lens), _np_ptr(errs), n)
+    if rc:
+        _raise(ctx, rc)
+    return out_lens, errs
+
+
+def _many(ctx, compress, streams, caps):
+    ctx = ctx or default_context()
+    # the inputs where they lie (no join, no copy)
+    views = [np.frombuffer(s, dtype=np.uint8) if len(s) else None
+             for s in streams]
+    in_ptrs = [v.ctypes.data if v is not None else 0 for v in views]
+    in_lens = [v.size if v is not None else 0 for v in views]
+    caps = np.asarray([int(c) for c in caps], dtype=np.uint64)
+    offs = np.zeros(len(caps) + 1, dtype=np.uint64)
+    np.cumsum(caps, out=offs[1:])
+    slab = np.empty(max(int(offs[-1]), 1), dtype=np.uint8)
+    out_ptrs = offs[:-1] + np.uint64(slab.ctypes.data)
+    out_lens, errs = batch_host(ctx, compress, in_ptrs, in_lens, out_ptrs,
+                                caps)
+    del views
+    outputs, errors = [], []
+    for i in range(len(caps)):
+        e = errs[i]
+        if e["kind"] == 0:
+            o = int(offs[i])
+            outputs.append(slab[o:o + int(out_lens[i])].tobytes())
+            errors.append(None)
+        else:
+            outputs.append(b"")
+            errors.append(Error(int(e["kind"]), int(e["a"]), int(e["b"]),
+                                int(e["c"])))
+    return outputs, errors
+
+
+def compress_many(streams, ctx=None):
+    """Encoder::compress_vec of every stream (bytes-like objects) in one
+    snapmi_compress_batch_host call.  Returns (outputs, errors): the
+    compressed bytes (b"" for a stream that failed) and None or the Error of
+    every stream."""
+    return _many(ctx, True, streams,
+                 [max_compress_len(len(s)) for s in streams])
+
+
+def decompress_many(streams, ctx=None, caps=None):
+    """Decoder::decompress_vec of every stream in one
+    snapmi_decompress_batch_host call; caps: output capacities (default: what
+    every stream's header announces; a header that does not parse gets none
+    and the device reports the error).  Returns (outputs, errors) as
+    compress_many."""
+    if caps is None:
+        L, n = _lib.load(), C.c_size_t(0)
+        caps = []
+        for s in streams:
+            s = bytes(s[:16])
+            ok = L.snapmi_decompress_len(s, len(s), C.byref(n), None) == 0
+            caps.append(n.value if ok else 0)
+    return _many(ctx, False, streams, caps)
 
 
 # ---------------------------------------------------------------------

@@ -1113,6 +1113,39 @@ def frames_batch(args, ctx, dev):
     return res
 
 
+class HostArena:
+    """buffers of the given sizes, 64 bytes apart at least, in one
+    pageable array or one snapmi_host_alloc allocation"""
+
+    def __init__(self, sizes, pinned):
+        sizes = np.asarray(sizes, dtype=np.uint64)
+        step = (sizes + np.uint64(127)) // np.uint64(64) * np.uint64(64)
+        self.offs = np.concatenate(([0], np.cumsum(step)[:-1])).astype(
+            np.uint64)
+        total = int(step.sum()) + 64
+        from rust_snappy_amd import frame
+        self.host = frame.HostBuffer(total) if pinned else None
+        self.arr = self.host.array if pinned \
+            else np.zeros(total, dtype=np.uint8)
+        self.arr[:] = 0
+        self.ptrs = self.offs + np.uint64(self.arr.ctypes.data)
+        self.sizes = sizes
+
+    def fill(self, datas):
+        for o, d in zip(self.offs, datas):
+            self.arr[int(o):int(o) + len(d)] = np.frombuffer(
+                d, dtype=np.uint8)
+
+    def bytes(self, i, n):
+        o = int(self.offs[i])
+        return self.arr[o:o + int(n)].tobytes()
+
+    def close(self):
+        if self.host is not None:
+            self.arr = None
+            self.host.close()
+
+
 def host_batch(args, ctx, dev):
     """Many raw streams in HOST memory per call (snapmi_compress_batch_host /
     snapmi_decompress_batch_host) from pageable and from pinned buffers,
@@ -1142,36 +1175,7 @@ def host_batch(args, ctx, dev):
     L = _lib.of(ctx)
     has_test = hasattr(L, "snapmi_ctx_set_test_option")
 
-    class Arena:
-        """buffers of the given sizes, 64 bytes apart at least, in one
-        pageable array or one snapmi_host_alloc allocation"""
-
-        def __init__(self, sizes, pinned):
-            sizes = np.asarray(sizes, dtype=np.uint64)
-            step = (sizes + np.uint64(127)) // np.uint64(64) * np.uint64(64)
-            self.offs = np.concatenate(([0], np.cumsum(step)[:-1])).astype(
-                np.uint64)
-            total = int(step.sum()) + 64
-            self.host = frame.HostBuffer(total) if pinned else None
-            self.arr = self.host.array if pinned \
-                else np.zeros(total, dtype=np.uint8)
-            self.arr[:] = 0
-            self.ptrs = self.offs + np.uint64(self.arr.ctypes.data)
-            self.sizes = sizes
-
-        def fill(self, datas):
-            for o, d in zip(self.offs, datas):
-                self.arr[int(o):int(o) + len(d)] = np.frombuffer(
-                    d, dtype=np.uint8)
-
-        def bytes(self, i, n):
-            o = int(self.offs[i])
-            return self.arr[o:o + int(n)].tobytes()
-
-        def close(self):
-            if self.host is not None:
-                self.arr = None
-                self.host.close()
+    Arena = HostArena
 
     def measure(datas, pinned, steps):
         n = len(datas)
@@ -1338,6 +1342,158 @@ def host_batch(args, ctx, dev):
     return res
 
 
+def frames_host_batch(args, ctx, dev):
+    """Many FRAMED streams in HOST memory per call
+    (snapmi_frame_compress_batch_host / snapmi_frame_decompress_batch_host)
+    from pageable and from pinned buffers, against a loop of
+    snapmi_frame_encode_host / snapmi_frame_decode_host one-stream calls over
+    the same buffers (timed on the first streams and scaled), the raw host
+    batch calls on the same payload, and - with the test build
+    (SNAPMI_TESTING=1) - the decode from the host's chunk list against the
+    device's walk (host_batch_listed 1 / 0, three repeats each: their spread
+    is the noise the difference is read against).  The sets of host_batch
+    and 64 streams of 16 MiB (256 chunks each), where the walk matters."""
+    import ctypes as C
+    import random
+    import oracle_lib as O
+    from rust_snappy_amd import _lib, frame, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+
+    def piece(n):
+        o = rng.randrange(len(text) - n)
+        return text[o:o + n]
+
+    def long_piece(n):
+        return b"".join(piece(1 << 20) for _ in range(n >> 20))
+    sets = {"text_4096x16k": [piece(16384) for _ in range(4096)],
+            "text_65536x4k": [piece(4096) for _ in range(65536)],
+            "mixed_512_100b_1m": [piece(int(100 * (10486 ** rng.random())))
+                                  for _ in range(512)],
+            "text_64x16m": [long_piece(16 << 20) for _ in range(64)]}
+    only = getattr(args, "sets", "")
+    L = _lib.of(ctx)
+    has_test = hasattr(L, "snapmi_ctx_set_test_option")
+    res = {"config": "frames_host_batch: n framed streams in host memory per "
+                     "call vs a loop of one-stream host calls, the raw host "
+                     "batch, and listed vs walked decode",
+           "steps": args.steps}
+    for key, datas in sets.items():
+        if only and key not in only.split(","):
+            continue
+        n = len(datas)
+        nbytes = sum(len(d) for d in datas)
+        row = {"streams": n, "bytes": nbytes}
+        lens = np.array([len(d) for d in datas], dtype=np.uint64)
+        fcaps = np.array([frame.frame_max_len(len(d)) for d in datas],
+                         dtype=np.uint64)
+        rcaps = np.array([raw.max_compress_len(len(d)) for d in datas],
+                         dtype=np.uint64)
+        for pinned in (False, True):
+            src, comp, back = HostArena(lens, pinned), \
+                HostArena(fcaps, pinned), HostArena(lens, pinned)
+            src.fill(datas)
+            st = {}
+
+            def enc():
+                st["clens"], st["errs"] = frame.batch_host(
+                    ctx, True, src.ptrs, lens, comp.ptrs, fcaps)
+            enc()
+            assert not st["errs"]["kind"].any()
+            clens = st["clens"]
+            for i in (0, n - 1):
+                if len(datas[i]) <= 1 << 20:
+                    assert comp.bytes(i, clens[i]) == O.frame_compress(datas[i])
+
+            def dec():
+                st["blens"], st["errs"] = frame.batch_host(
+                    ctx, False, comp.ptrs, clens, back.ptrs, lens)
+            dec()
+            assert not st["errs"]["kind"].any()
+            assert np.array_equal(st["blens"], lens)
+            assert np.array_equal(back.arr, src.arr), "round trip"
+            info = {k: ctx.info("host_batch_" + k)
+                    for k in ("slices", "listed_slices", "h2d_bytes",
+                              "d2h_bytes")}
+            out = {"compress_ms": round(time_it(enc, args.steps, ctx) * 1e3, 3),
+                   "decompress_ms": round(time_it(dec, args.steps, ctx) * 1e3,
+                                          3),
+                   "decompress_info": info}
+            if has_test:
+                rep = {}
+                for listed in (1, 0, 1, 0, 1, 0):
+                    ctx.set_test_option("host_batch_listed", listed)
+                    rep.setdefault(str(listed), []).append(
+                        round(time_it(dec, args.steps, ctx) * 1e3, 3))
+                ctx.set_test_option("host_batch_listed", 1)
+                noise = max(max(v) - min(v) for v in rep.values())
+                out["decompress_ms_by_host_batch_listed"] = rep
+                out["listed_noise_ms"] = round(noise, 3)
+                out["walked_minus_listed_ms"] = round(
+                    sorted(rep["0"])[1] - sorted(rep["1"])[1], 3)
+            # the raw host batch on the same payload
+            rcomp = HostArena(rcaps, pinned)
+
+            def r_enc():
+                st["rlens"], st["errs"] = raw.batch_host(
+                    ctx, True, src.ptrs, lens, rcomp.ptrs, rcaps)
+            r_enc()
+            rlens = st["rlens"]
+
+            def r_dec():
+                raw.batch_host(ctx, False, rcomp.ptrs, rlens, back.ptrs, lens)
+            if int(lens.max()) <= 0xFFFFFFFF:
+                out["raw_host_batch_ms"] = {
+                    "compress": round(time_it(r_enc, args.steps, ctx) * 1e3, 3),
+                    "decompress": round(time_it(r_dec, args.steps, ctx) * 1e3,
+                                        3)}
+            if not pinned:
+                # a loop of one-stream calls, on the first streams
+                k = min(n, 256)
+                w, got, err = C.c_size_t(0), C.c_size_t(0), _lib.SnapmiError()
+                chunk_lens = [np.array(
+                    [min(65536, len(d) - o) for o in range(0, len(d), 65536)],
+                    dtype=np.uint32) for d in datas[:k]]
+
+                # (the one-stream decoder wants room for whole chunks)
+                back1 = HostArena(np.maximum(lens[:k], 65536), False)
+
+                def s_enc():
+                    for i in range(k):
+                        L.snapmi_frame_encode_host(
+                            ctx._h, C.c_void_p(int(src.ptrs[i])),
+                            chunk_lens[i].ctypes.data_as(C.c_void_p),
+                            len(chunk_lens[i]), 0,
+                            C.c_void_p(int(comp.ptrs[i])), int(fcaps[i]),
+                            C.byref(w))
+
+                def s_dec():
+                    for i in range(k):
+                        L.snapmi_frame_decode_host(
+                            ctx._h, C.c_void_p(int(comp.ptrs[i])),
+                            int(clens[i]), 2, None,
+                            C.c_void_p(int(back1.ptrs[i])),
+                            int(back1.sizes[i]), C.byref(w), C.byref(got),
+                            C.byref(err))
+                te, td = time_it(s_enc, 1, ctx), time_it(s_dec, 1, ctx)
+                out["one_stream_loop"] = {
+                    "loop_streams": k,
+                    "ms_for_all": {"compress": round(te / k * n * 1e3, 1),
+                                   "decompress": round(td / k * n * 1e3, 1)},
+                    "speedup": {
+                        "compress": round(te / k * n * 1e3 / out["compress_ms"],
+                                          1),
+                        "decompress": round(
+                            td / k * n * 1e3 / out["decompress_ms"], 1)}}
+            row["pinned" if pinned else "pageable"] = out
+            for a in (src, comp, back, rcomp):
+                a.close()
+        res[key] = row
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=8.0)
@@ -1345,6 +1501,8 @@ def main():
                     help="period of the synthetic text (SURVEY 8d: 1 GiB)")
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--only", default="")
+    ap.add_argument("--sets", default="",
+                    help="frames_host_batch: only these data sets (a,b,...)")
     ap.add_argument("--plan", default="",
                     help="name:gib,... - run these configs at these sizes, "
                          "one JSON line each with a \"name\" key; a config "
@@ -1370,7 +1528,8 @@ def main():
     table = {"cfg3": cfg3, "cfg5": cfg5, "files": files, "pcie": pcie,
              "adapters": adapters, "stream": stream, "cfg4": cfg4,
              "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
-             "frames_batch": frames_batch, "host_batch": host_batch}
+             "frames_batch": frames_batch, "host_batch": host_batch,
+             "frames_host_batch": frames_host_batch}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1390,10 +1549,12 @@ def main():
                      ("pcie", pcie), ("adapters", adapters),
                      ("stream", stream), ("cfg4", cfg4),
                      ("frames_batch", frames_batch),
-                     ("host_batch", host_batch)):
+                     ("host_batch", host_batch),
+                     ("frames_host_batch", frames_host_batch)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
-                                                         "host_batch")):
+                                                         "host_batch",
+                                                         "frames_host_batch")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

@@ -306,12 +306,15 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *   "token_pages_asked"     pages the last token-path launch asked for, and
  *   "token_blocks_spilled"  blocks of it that found none and were compressed
  *                           a second time (both wait for the launch)
- *   "host_batch_slices"     slices the last host batch call (section 2b) made
+ *   "host_batch_slices"     slices the last host batch call (sections 2b, 4b)
+ *                           made
  *   "host_batch_h2d_bytes"  bytes it copied to the device (descriptors, inputs
  *                           and their alignment padding) and
  *   "host_batch_d2h_bytes"  back: one length and one error record per stream
  *                           and the outputs, packed (compress: what was
  *                           written, each stream rounded to 16 bytes)
+ *   "host_batch_listed_slices"  slices of it that were decoded from the host's
+ *                           chunk list (snapmi_frame_decompress_batch_host)
  * SNAPMI_E_ARGUMENT for a name that is not in this list. */
 SNAPMI_API int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name,
                                    int64_t *value);
@@ -602,6 +605,66 @@ SNAPMI_API int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
                                   const uint64_t *d_out_caps,
                                   uint64_t *d_out_lens, snapmi_error *d_errs,
                                   size_t n);
+
+/* ------------------------------------------------------------------ */
+/* 4b. Many independent framed streams in HOST memory per call.         */
+/* ------------------------------------------------------------------ */
+/*
+ * The two batch calls above on host buffers, in one blocking call each - how
+ * a directory of .sz files is packed and unpacked.  For every i,
+ * h_out_lens[i], h_errs[i] (variant and fields a, b, c) and the bytes
+ * h_out_ptrs[i][0, h_out_lens[i]) are exactly what snapmi_frame_compress_batch
+ * / snapmi_frame_decompress_batch give for stream i alone with capacity
+ * h_out_caps[i]: one write::FrameEncoder::write_all + into_inner, or one
+ * read::FrameDecoder read to its end.  No stream affects another, and nothing
+ * is ever written behind h_out_lens[i].
+ *   compress     cap_i < snapmi_frame_max_len(len_i) with len_i > 0: stream i
+ *                fails with SNAPMI_BUFFER_TOO_SMALL {cap_i, max_len}, its
+ *                length is 0 and its buffer is untouched; an empty input
+ *                gives length 0 and OK (no identifier)
+ *   decompress   on an error h_out_lens[i] is the number of bytes in front of
+ *                the failing chunk, and those bytes are delivered, as in the
+ *                device call; an output that does not fit is BufferTooSmall
+ *                {cap, total} and nothing is written
+ *   h_out_ptrs   decompress: NULL = lengths only - h_out_lens[i] gets the
+ *                decoded length of stream i; h_out_caps may then be NULL
+ *   return value failures of the call itself only (SNAPMI_E_DEVICE,
+ *                SNAPMI_E_ARGUMENT)
+ *   h_errs       may be NULL
+ *   n            below 2^31, and so is the number of chunks of a slice;
+ *                n == 0 does nothing
+ * The buffers may be pageable or pinned (snapmi_host_alloc).
+ *
+ * The pipeline is that of section 2b (slices cut by "host_batch_slice", one
+ * copy in, packed output home; info "host_batch_slices",
+ * "host_batch_h2d_bytes", "host_batch_d2h_bytes" describe the last call of any
+ * of the four).  Decompress: the host walks the chunk headers of every stream
+ * before it sends it (the walk of snapmi_frame_decompress_batch, compiled for
+ * the host), which gives the room of every stream in the output slab - only
+ * decoded bytes come home - and, for a slice whose streams are all
+ * well-formed, the chunk list: it travels with the inputs, one thread per
+ * chunk checks it against the bytes on the device (k_fbd_from_list), and the
+ * device neither walks the streams (0.7 us per chunk on one thread) nor makes
+ * the host wait for a chunk count.  A slice that holds a malformed stream is
+ * decoded by snapmi_frame_decompress_batch as it is.  Verdicts, lengths and
+ * error fields come from the device either way; a list that disagrees with
+ * the bytes fails the call (SNAPMI_E_DEVICE).  Info "host_batch_listed_slices":
+ * slices of the last call decoded from the list.
+ */
+SNAPMI_API int snapmi_frame_compress_batch_host(snapmi_ctx *ctx,
+                                     const void *const *h_in_ptrs,
+                                     const size_t *h_in_lens,
+                                     void *const *h_out_ptrs,
+                                     const size_t *h_out_caps,
+                                     size_t *h_out_lens, snapmi_error *h_errs,
+                                     size_t n);
+SNAPMI_API int snapmi_frame_decompress_batch_host(snapmi_ctx *ctx,
+                                       const void *const *h_in_ptrs,
+                                       const size_t *h_in_lens,
+                                       void *const *h_out_ptrs,
+                                       const size_t *h_out_caps,
+                                       size_t *h_out_lens,
+                                       snapmi_error *h_errs, size_t n);
 
 /* flags of the frame entry points below */
 #define SNAPMI_FRAME_NO_IDENT 1u     /* compress: do not emit the identifier */

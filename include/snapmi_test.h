@@ -65,6 +65,10 @@ extern "C" {
  *                          output of a compress slice straight into pinned
  *                          host memory; 0: into device memory, followed by
  *                          one D2H of exactly that much
+ *   "host_batch_listed"    1 (default): a slice of
+ *                          snapmi_frame_decompress_batch_host whose streams
+ *                          are all well-formed is decoded from the host's
+ *                          chunk list; 0: the device always walks
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
  */
 SNAPMI_API int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,

@@ -20,6 +20,15 @@ for ln in (P / "r6_final_kernel_stats.md").read_text().splitlines():
 suite = (P / "r6_final_gpu_suite.txt").read_text()
 FB = json.loads((P / "frames_batch.json").read_text())["text_4096x16k"]
 HB = json.loads((P / "host_batch.json").read_text())["text_4096x16k"]
+FH = json.loads((P / "frame_host_batch.json").read_text())[
+    "frames_host_batch"]["text_4096x16k"]
+
+
+def fh(kind, way):
+    return FH["bytes"] / 2**30 / FH[kind][way + "_ms"] * 1e3
+
+
+FHL = FH["pageable"]["one_stream_loop"]["speedup"]
 passed = re.search(r"(\d+) passed", suite).group(1)
 lat = {}
 for ln in (P / "r6_final_scalar_latency.txt").read_text().splitlines():
@@ -98,6 +107,7 @@ readme = f"""## Results (1× MI355X, device resident; ONE box, one `python bench
 | host memory to host memory, 4 GiB (`snapmi_frame_encode_host` / `_decode_host`, pinned) | {g(ex['pcie']['frame_encode_gibs'])} GiB/s | {g(ex['pcie']['frame_decode_gibs'])} GiB/s |
 | 4 096 framed streams of 16 KiB in one call (`snapmi_frame_compress_batch` / `_decompress_batch`; a loop of one-stream calls: {FB['batch_over_single_loop_speedup']['compress']:.0f}× / {FB['batch_over_single_loop_speedup']['decompress']:.0f}× slower; the raw batch calls: {FB['batch_over_raw_floor']['compress']}× / {FB['batch_over_raw_floor']['decompress']}× faster, `profiles/frames_batch.json`) | {g(FB['batch_gibs']['compress'])} GiB/s | {g(FB['batch_gibs']['decompress'],0)} GiB/s |
 | 4 096 raw streams of 16 KiB in HOST memory in one call (`snapmi_compress_batch_host` / `_decompress_batch_host`, pageable / pinned buffers; a loop of `snapmi_raw_compress` / `_decompress` calls: {HB['host_batch_over_scalar_loop_speedup']['compress']:.0f}× / {HB['host_batch_over_scalar_loop_speedup']['decompress']:.0f}× slower; `profiles/host_batch.json`) | {g(HB['pageable']['compress_gibs'])} / {g(HB['pinned']['compress_gibs'])} GiB/s | {g(HB['pageable']['decompress_gibs'])} / {g(HB['pinned']['decompress_gibs'])} GiB/s |
+| 4 096 framed streams of 16 KiB in HOST memory in one call (`snapmi_frame_compress_batch_host` / `_decompress_batch_host`, pageable / pinned buffers; a loop of `snapmi_frame_encode_host` / `_decode_host` calls: {FHL['compress']:.0f}× / {FHL['decompress']:.0f}× slower; `profiles/frame_host_batch.json`) | {g(fh('pageable','compress'))} / {g(fh('pinned','compress'))} GiB/s | {g(fh('pageable','decompress'))} / {g(fh('pinned','decompress'))} GiB/s |
 | Python adapters: `FrameEncoder.write_all` / `FrameDecoder.readinto` (pinned, from a pinned reader) / `read_to_end` | {g(ex['adapters']['frame_encoder_write_all_gibs'])} GiB/s | {g(ex['adapters']['frame_decoder_readinto_pinned_from_pinned_gibs'])} / {g(ex['adapters']['frame_decoder_read_to_end_gibs'])} GiB/s |
 | CPU: the reference's algorithm with its fast paths (`oracle/snappy_port_fast.c`), the box's {cb['cores']} usable cores | {g(cb['compress_gibs'])} GiB/s | {g(cb['decompress_gibs'])} GiB/s |
 | Google libsnappy 1.1.8, {cb['cores']} cores | {g(cb['libsnappy_1_1_8']['all_cores']['compress_gibs'])} GiB/s | {g(cb['libsnappy_1_1_8']['all_cores']['decompress_gibs'])} GiB/s |

@@ -100,6 +100,10 @@ SYMBOLS = [
      [_P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_frame_decompress_batch", C.c_int,
      [_P, _P, _P, _P, _P, _P, _P, _SZ]),
+    ("snapmi_frame_compress_batch_host", C.c_int,
+     [_P, _P, _P, _P, _P, _P, _P, _SZ]),
+    ("snapmi_frame_decompress_batch_host", C.c_int,
+     [_P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_frame_index_host", C.c_int,
      [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("snapmi_crc32c_masked_batch", C.c_int, [_P, _P, _P, _P, _SZ]),

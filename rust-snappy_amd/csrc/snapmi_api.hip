@@ -463,6 +463,9 @@ int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
     else if (strcmp(name, "host_batch_pack_to_host") == 0 && value >= 0 &&
              value <= 1)
         ctx->host_batch_pack_to_host = (int)value;
+    else if (strcmp(name, "host_batch_listed") == 0 && value >= 0 &&
+             value <= 1)
+        ctx->host_batch_listed = (int)value;
     else
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "unknown test option %s",
                         name);
@@ -804,6 +807,8 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
         *value = (int64_t)ctx->hb_h2d_bytes;
     } else if (strcmp(name, "host_batch_d2h_bytes") == 0) {
         *value = (int64_t)ctx->hb_d2h_bytes;
+    } else if (strcmp(name, "host_batch_listed_slices") == 0) {
+        *value = (int64_t)ctx->hb_listed_slices;
     } else {
         ctx->last_error = std::string("unknown info: ") + name;
         return SNAPMI_E_ARGUMENT;

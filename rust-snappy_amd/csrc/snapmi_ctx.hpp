@@ -52,8 +52,14 @@ struct snapmi_ctx {
     uint64_t host_batch_slice = 16ull << 20;
     uint64_t host_batch_direct_min = 1ull << 20;
     int host_batch_pack_to_host = 1;
-    // what the last host batch call did: slices, bytes copied each way
+    // 1: a slice of snapmi_frame_decompress_batch_host whose streams the host
+    // found well-formed sends its chunk list along and the device does not
+    // walk (k_fbd_from_list); 0: the device always walks (test option)
+    int host_batch_listed = 1;
+    // what the last host batch call did: slices, bytes copied each way,
+    // slices decoded from the host's chunk list
     uint64_t hb_slices = 0, hb_h2d_bytes = 0, hb_d2h_bytes = 0;
+    uint64_t hb_listed_slices = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
     std::string last_error;

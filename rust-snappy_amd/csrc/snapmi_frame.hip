@@ -35,14 +35,17 @@
 #include "snapmi_hostpipe.hpp"
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
+#include "snapmi_framewalk.hpp"
 
 using namespace snapmi;
 
 namespace snapmi {
 
 constexpr uint32_t kCrcPoly = 0x82F63B78u;      // reference build.rs:6
-constexpr uint32_t kMaxChunk = 76490;           // reference src/frame.rs:12
 constexpr uint32_t kFrameSlot = 76496;          // kMaxChunk rounded to 16
+// (kMaxChunk, FrameChunk and the chunk-header walk: snapmi_framewalk.hpp)
+static_assert(kFwMaxBlock == kMaxBlock && kFwMaxInput == kMaxInput,
+              "snapmi_framewalk.hpp restates the codec's limits");
 
 // Tables for k_crc32c, generated once per context on the host (the
 // reference generates its tables at build time, build.rs:97-124).
@@ -50,14 +53,6 @@ struct CrcTables {
     uint32_t z256[4][256]; // state advanced by 256 zero bytes, per input byte
     uint32_t lane_mul[64]; // x^(8*4*(64-j)) mod P: final advance of lane j
     uint32_t init_adv[65537]; // 0xFFFFFFFF advanced by n zero bytes
-};
-
-struct FrameChunk { // one data chunk of a framed stream (decode side)
-    uint64_t payload_off; // offset of the payload in the stream
-    uint32_t payload_len;
-    uint32_t crc;   // stored masked crc
-    uint32_t type;  // 0 compressed, 1 stored
-    uint32_t pad;
 };
 
 // GF(2) polynomial product mod P, reflected representation (bit 31 = x^0)
@@ -330,93 +325,6 @@ struct FrameDecodeArgs {
     unsigned long long fw_seg; // segment bytes (32 MiB; smaller in tests)
 };
 
-__device__ inline snapmi_error frame_err(int kind, uint64_t fa, uint64_t fb)
-{
-    snapmi_error e;
-    e.kind = kind;
-    e.reserved = 0;
-    e.a = fa;
-    e.b = fb;
-    e.c = 0;
-    return e;
-}
-
-// A compressed chunk whose payload is shorter than 10 bytes and holds no
-// varint terminator (every byte >= 0x80; an empty payload too).  The
-// reference calls decompress_len on its WHOLE 76 490-byte scratch buffer
-// `src` (src/read.rs:216), so the varint continues into whatever earlier
-// reads left there: this chunk's own 4 header bytes at src[0..4) (read.rs:118),
-// and the bodies of earlier stream-identifier / skippable / padding /
-// compressed chunks (read.rs:151,157,168,214; stored chunks go to `dst`).
-// The outcome then is TooBig, UnsupportedChunkLength, or - when the phantom
-// length is acceptable - whatever Decoder::decompress says about the real
-// payload: Empty or Header (src/decompress.rs:80-83).  Rare and always an
-// error, so the model of src[0..10) is rebuilt here by walking the stream
-// `in` again from its start up to `stop` (the offset of this chunk's header);
-// `stale` is src[0..10) when the walk started.
-__device__ inline snapmi_error frame_short_varint(gcptr in,
-                                                  const uint8_t *stale,
-                                                  uint64_t stop)
-{
-    uint8_t m[10];
-    for (int k = 0; k < 10; k++)
-        m[k] = stale[k];
-    uint64_t r = 0;
-    for (;;) { // every chunk before `stop` was accepted by the walk
-        const uint32_t hd = ld32u(in + r);
-        for (int k = 0; k < 4; k++)
-            m[k] = (uint8_t)(hd >> (8 * k));
-        const uint32_t ty = hd & 0xFF;
-        const uint64_t len = hd >> 8;
-        uint64_t body = r + 4, blen = len; // bytes read into src[0..blen)
-        if (ty == 0x00) {
-            body = r + 8;
-            blen = len - 4;
-        } else if (ty == 0x01) {
-            blen = 0;
-        }
-        for (uint64_t k = 0; k < blen && k < 10; k++)
-            m[k] = in[body + k];
-        if (r == stop)
-            break;
-        r += 4 + len;
-    }
-    // decompress_len(&src): read_varu64 (src/bytes.rs:73-90) over m[0..10)
-    uint64_t v = 0;
-    uint32_t shift = 0;
-    bool ok = false;
-    for (int k = 0; k < 10; k++) {
-        const uint64_t b = m[k];
-        if (b < 0x80) {
-            v |= b << shift;
-            ok = true;
-            break;
-        }
-        v |= (b & 0x7F) << shift;
-        shift += 7;
-    }
-    const uint64_t sn = (ld32u(in + stop) >> 8) - 4;
-    if (!ok)
-        return frame_err(SNAPMI_HEADER, 0, 0);
-    if (v > kMaxInput)
-        return frame_err(SNAPMI_TOO_BIG, v, kMaxInput);
-    if (v > kMaxBlock) // read.rs:217-222
-        return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, v, 0);
-    // Decoder::decompress(&src[0..sn]), src/decompress.rs:80-83
-    return frame_err(sn == 0 ? SNAPMI_EMPTY : SNAPMI_HEADER, 0, 0);
-}
-
-// true when the payload [p, p + pl) needs frame_short_varint
-__device__ inline bool short_varint(gcptr p, uint64_t pl)
-{
-    if (pl >= 10)
-        return false;
-    for (uint64_t k = 0; k < pl; k++)
-        if (p[k] < 0x80)
-            return false;
-    return true;
-}
-
 // ---------------------------------------------------------------------
 // Parallel header walk.  The frame format is a linked list without an index:
 // k_frame_walk below hops from header to header, 0.7 us per hop (1.1 s for the
@@ -575,88 +483,6 @@ __global__ void k_fw_emit(FrameDecodeArgs a)
     }
 }
 
-// Sequential walk over the chunk headers of one framed stream
-// in[0, in_len): reference FrameDecoder::read, src/read.rs:111-236 (checks
-// in the reference's order; `flags` and `stale` as in
-// snapmi_frame_decompress_ex).  Every hop depends on the previous header, so
-// a stream is walked by one thread.  on_data(k, chunk) is called for data
-// chunk k (0, 1, ...) in front of the first structural error; returns that
-// error (kind SNAPMI_OK at a clean end) and *nd = the data chunks in front
-// of it.
-template <class OnData>
-__device__ inline snapmi_error frame_walk(gcptr in, uint64_t in_len,
-                                          uint32_t flags,
-                                          const uint8_t *stale, uint32_t &nd,
-                                          OnData on_data)
-{
-    uint64_t r = 0;
-    nd = 0;
-    bool seen_ident = (flags & SNAPMI_FRAME_CONTINUATION) != 0;
-    for (;;) {
-        if (r == in_len)
-            return frame_err(SNAPMI_OK, 0, 0); // clean EOF, :119-121
-        if (in_len - r < 4)
-            return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-        const uint32_t hd = ld32u(in + r);
-        r += 4;
-        const uint32_t ty = hd & 0xFF;
-        const uint64_t len = hd >> 8;
-        if (!seen_ident) { // :123-128
-            if (ty != 0xFF)
-                return frame_err(SNAPMI_STREAM_HEADER, ty, 0);
-            seen_ident = true;
-        }
-        if (len > kMaxChunk) // :129-135
-            return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 0);
-        if (ty >= 0x02 && ty <= 0x7F) // :138-142
-            return frame_err(SNAPMI_UNSUPPORTED_CHUNK_TYPE, ty, 0);
-        if ((ty >= 0x80 && ty <= 0xFD) || ty == 0xFE) { // skippable, padding
-            if (in_len - r < len)
-                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-            r += len;
-        } else if (ty == 0xFF) { // :159-172
-            if (len != 6)
-                return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 1);
-            if (in_len - r < 6)
-                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-            const uint8_t body[6] = {'s', 'N', 'a', 'P', 'p', 'Y'};
-            uint64_t got = 0;
-            bool same = true;
-            for (int k = 0; k < 6; k++) {
-                const uint8_t b = in[r + k];
-                got |= (uint64_t)b << (8 * k);
-                same = same && b == body[k];
-            }
-            if (!same)
-                return frame_err(SNAPMI_STREAM_HEADER_MISMATCH, got, 0);
-            r += 6;
-        } else { // 0x00 compressed / 0x01 stored: :173-235
-            if (len < 4)
-                return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, len, 0);
-            if (in_len - r < 4)
-                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-            const uint32_t crc = ld32u(in + r);
-            r += 4;
-            const uint64_t pl = len - 4;
-            if (ty == 0x01 && pl > kMaxBlock) // :182-187
-                return frame_err(SNAPMI_UNSUPPORTED_CHUNK_LENGTH, pl, 0);
-            if (in_len - r < pl)
-                return frame_err(SNAPMI_E_UNEXPECTED_EOF, 0, 0);
-            if (ty == 0x00 && short_varint(in + r, pl)) // read.rs:216
-                return frame_short_varint(in, stale, r - 8);
-            FrameChunk c;
-            c.payload_off = r;
-            c.payload_len = (uint32_t)pl;
-            c.crc = crc;
-            c.type = ty;
-            c.pad = 0;
-            on_data(nd, c);
-            nd++;
-            r += pl;
-        }
-    }
-}
-
 // the walk of the one stream of snapmi_frame_decompress[_ex]
 __global__ void k_frame_walk(FrameDecodeArgs a)
 {
@@ -738,54 +564,6 @@ __global__ void k_frame_index(FrameDecodeArgs a)
     if (!good)
         a.meta[3] = 1;
     a.chunks[i] = c;
-}
-
-// decompressed length of data chunk c, whose payload starts at p: reference
-// src/read.rs:181-187 (stored) and :215-222 (compressed: decompress_len, then
-// dn <= 65536); 0 and *e on an error
-__device__ inline uint64_t frame_chunk_len(gcptr p, const FrameChunk &c,
-                                           snapmi_error &e)
-{
-    e = frame_err(SNAPMI_OK, 0, 0);
-    if (c.type > 1) { // only reachable through a bad side index
-        e.kind = SNAPMI_UNSUPPORTED_CHUNK_TYPE;
-        e.a = c.pad;
-        return 0;
-    }
-    if (c.type == 1)
-        return c.payload_len;
-    uint64_t acc = 0;
-    uint32_t shift = 0;
-    bool ok = false;
-    for (uint32_t k = 0; k < c.payload_len; k++) {
-        const uint32_t b = p[k];
-        if (shift >= 64)
-            break;
-        if (b < 0x80) {
-            acc |= (uint64_t)b << shift;
-            ok = true;
-            break;
-        }
-        acc |= (uint64_t)(b & 0x7F) << shift;
-        shift += 7;
-    }
-    if (c.payload_len == 0) {
-        // reference: decompress_len of the scratch reads a stale byte;
-        // the decode of the empty payload then fails with Empty
-        e.kind = SNAPMI_EMPTY;
-    } else if (!ok) {
-        e.kind = SNAPMI_HEADER;
-    } else if (acc > kMaxInput) {
-        e.kind = SNAPMI_TOO_BIG;
-        e.a = acc;
-        e.b = kMaxInput;
-    } else if (acc > kMaxBlock) {
-        e.kind = SNAPMI_UNSUPPORTED_CHUNK_LENGTH;
-        e.a = acc;
-    } else {
-        return acc;
-    }
-    return 0;
 }
 
 __global__ void k_frame_lens(FrameDecodeArgs a)
@@ -1121,6 +899,95 @@ __global__ __launch_bounds__(64) void k_fbd_walk_fill(FrameBatchDecodeArgs a)
                });
 }
 
+// From the last chunk the reader accepted (or the stream's start) to `to`:
+// true when in[r, to) is a run of chunks the walk skips - the identifier,
+// skippable and padding chunks - that ends exactly at `to`.
+__device__ inline bool fbd_gap(gcptr in, uint64_t in_len, uint64_t r,
+                               bool seen_ident, uint64_t to)
+{
+    const uint8_t fresh[10] = {0};
+    if (to > in_len)
+        return false;
+    while (r < to) {
+        bool data;
+        FrameChunk c;
+        if (frame_hop(in, in_len, fresh, r, seen_ident, data, c).kind !=
+                SNAPMI_OK ||
+            data)
+            return false;
+    }
+    return r == to;
+}
+
+// The walk kernels' work for streams the HOST has walked already
+// (snapmi_frame_decompress_batch_listed): list[t] names data chunk t of the
+// batch and l_first[i] the first chunk of stream i, both written by the host
+// from the bytes it staged.  The list is a hint that is checked, never
+// trusted: thread t < total hops with the walk's own rules from the chunk in
+// front of its chunk (the stream's start for a first chunk) to its header and
+// over it, thread total + i from stream i's last chunk to the stream's end,
+// so together they are one walk of every stream.  Whatever does not come out
+// as listed raises *bad (the call fails) and leaves a chunk that decodes to
+// nothing.
+__global__ __launch_bounds__(256) void k_fbd_from_list(FrameBatchDecodeArgs a,
+                                                       const uint64_t *l_first,
+                                                       const FwEntry *list,
+                                                       uint32_t *bad)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint8_t fresh[10] = {0};
+    bool good = true;
+    if (t < a.total) {
+        const FwEntry x = list[t];
+        const uint32_t s = x.stream < a.n ? x.stream : 0;
+        FrameChunk c;
+        c.payload_off = 0;
+        c.payload_len = 0;
+        c.crc = 0;
+        c.type = 0xFF;
+        c.pad = 0xFF;
+        good = x.stream < a.n && l_first[s] <= t && t < l_first[s + 1];
+        if (good) {
+            gcptr in = (gcptr)a.in_ptrs[s];
+            const uint64_t in_len = a.in_lens[s];
+            uint64_t r = 0;
+            bool seen = false, data = false;
+            if (t > l_first[s]) {
+                r = list[t - 1].off + 4 + (list[t - 1].hd >> 8);
+                seen = true;
+            }
+            FrameChunk got;
+            good = fbd_gap(in, in_len, r, seen, x.off) && x.off < in_len;
+            r = x.off;
+            seen = true; // (a first chunk lies behind the identifier: r > 0)
+            good = good && x.off > 0 &&
+                   frame_hop(in, in_len, fresh, r, seen, data, got).kind ==
+                       SNAPMI_OK &&
+                   data && fw_ld32(in + x.off) == x.hd;
+            if (good)
+                c = got;
+        }
+        a.chunks[t] = c;
+        a.c_stream[t] = s;
+    } else if (t - a.total < a.n) {
+        const uint32_t i = t - a.total;
+        const uint64_t b = l_first[i], e = l_first[i + 1];
+        uint64_t r = 0;
+        if (e > b)
+            r = list[e - 1].off + 4 + (list[e - 1].hd >> 8);
+        good = fbd_gap((gcptr)a.in_ptrs[i], a.in_lens[i], r, e > b,
+                       a.in_lens[i]);
+        a.counts[i] = e - b;
+        a.first[i] = b;
+        if (i + 1 == a.n)
+            a.first[a.n] = e;
+        a.serr[i] = frame_err(SNAPMI_OK, 0, 0);
+        a.sidx[i] = 0xFFFFFFFFu;
+    }
+    if (!good)
+        *bad = 1;
+}
+
 __global__ void k_fbd_lens(FrameBatchDecodeArgs a)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1444,45 +1311,8 @@ int snapmi_frame_index_host(const void *h_in, uint64_t in_len,
     // anything else is left to the device walk, which owns the error report
     if (!n_chunks || (in_len && !h_in))
         return 1;
-    const uint8_t *in = (const uint8_t *)h_in;
-    uint64_t r = 0, nd = 0;
-    bool seen_ident = false;
-    while (r != in_len) {
-        if (in_len - r < 4)
-            return 1;
-        const uint32_t ty = in[r];
-        const uint64_t len = (uint64_t)in[r + 1] | ((uint64_t)in[r + 2] << 8) |
-                             ((uint64_t)in[r + 3] << 16);
-        const uint64_t at = r;
-        r += 4;
-        if (!seen_ident && ty != 0xFF)
-            return 1;
-        seen_ident = true;
-        if (len > kMaxChunk || (ty >= 0x02 && ty <= 0x7F) ||
-            in_len - r < len)
-            return 1;
-        if (ty == 0xFF) {
-            if (len != 6 || memcmp(in + r, "sNaPpY", 6) != 0)
-                return 1;
-        } else if (ty <= 0x01) {
-            if (len < 4 || (ty == 0x01 && len - 4 > kMaxBlock))
-                return 1;
-            if (h_offsets) {
-                if (nd + 1 >= cap)
-                    return 1;
-                h_offsets[nd] = at;
-            }
-            nd++;
-        }
-        r += len;
-    }
-    if (h_offsets) {
-        if (nd + 1 > cap)
-            return 1;
-        h_offsets[nd] = in_len;
-    }
-    *n_chunks = nd;
-    return 0;
+    return frame_index_walk((const uint8_t *)h_in, in_len, h_offsets, cap,
+                            n_chunks);
 }
 
 // meta[] and the structural error slot before the index kernel (whose
@@ -1936,27 +1766,19 @@ int snapmi_frame_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     return SNAPMI_OK;
 }
 
-int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
-                                  const void *const *d_in_ptrs,
-                                  const uint64_t *d_in_lens,
-                                  void *const *d_out_ptrs,
-                                  const uint64_t *d_out_caps,
-                                  uint64_t *d_out_lens, snapmi_error *d_errs,
-                                  size_t n)
+// The per-stream scratch of a batch decode; false arguments are reported.
+static int fbd_begin(snapmi_ctx *ctx, const char *what,
+                     const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+                     void *const *d_out_ptrs, const uint64_t *d_out_caps,
+                     uint64_t *d_out_lens, snapmi_error *d_errs, size_t n,
+                     FrameBatchDecodeArgs &a)
 {
-    if (!ctx)
-        return SNAPMI_E_ARGUMENT;
-    if (n == 0)
-        return SNAPMI_OK;
     if (!d_in_ptrs || !d_in_lens || !d_out_lens || (d_out_ptrs && !d_out_caps))
-        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
-                        "frame_decompress_batch: bad args");
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "%s: bad args", what);
     if (n > 0x7FFFFFFFu)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
-                        "frame_decompress_batch: %zu streams (at most 2^31 - "
-                        "1)", n);
+                        "%s: %zu streams (at most 2^31 - 1)", what, n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     int rc = ensure_tables(ctx);
     if (rc)
         return rc;
@@ -1964,10 +1786,8 @@ int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
     // sized after the walk, and growing it must not drop the first
     if ((rc = reserve(ctx, ctx->fb_streams,
                       n * (8 + 8 + sizeof(snapmi_error) + 4 + 4) + 8 +
-                          16 * 8)) ||
-        (rc = mailbox(ctx)))
+                          16 * 8)))
         return rc;
-    FrameBatchDecodeArgs a;
     uint8_t *p = (uint8_t *)ctx->fb_streams.p;
     a.in_ptrs = d_in_ptrs;
     a.in_lens = d_in_lens;
@@ -1982,28 +1802,32 @@ int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
     a.serr = carve<snapmi_error>(p, n);
     a.sidx = carve<uint32_t>(p, n);
     a.first_bad = carve<uint32_t>(p, n);
-    const uint32_t gs = (uint32_t)((n + 63) / 64);
-    hipLaunchKernelGGL(k_fbd_walk_count, dim3(gs), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.counts,
-                       a.first, (uint32_t)n);
-    // the one wait: the number of data chunks sizes everything below
-    hipLaunchKernelGGL(k_post_words, dim3(1), dim3(64), 0, s,
-                       (uint32_t *)ctx->h_mail, (const uint32_t *)(a.first + n),
-                       2u);
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    const uint64_t total =
-        (uint64_t)ctx->h_mail[0] | ((uint64_t)ctx->h_mail[1] << 32);
+    return SNAPMI_OK;
+}
+
+// Everything behind the count of the batch's data chunks: the chunk records -
+// by the walk again, or from the host's list (l_first, list, bad:
+// k_fbd_from_list) -, lengths, descriptors, the codec, the checksums and the
+// verdicts.
+static int fbd_finish(snapmi_ctx *ctx, const char *what,
+                      FrameBatchDecodeArgs &a, uint64_t total,
+                      const uint64_t *l_first, const FwEntry *list,
+                      uint32_t *bad)
+{
+    hipStream_t s = ctx->stream;
+    const size_t n = a.n;
     if (total > 0x7FFFFFFFu)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
-                        "frame_decompress_batch: %llu chunks (at most 2^31 - "
-                        "1)", (unsigned long long)total);
+                        "%s: %llu chunks (at most 2^31 - 1)", what,
+                        (unsigned long long)total);
     const size_t t = (size_t)total;
+    int rc;
     if ((rc = reserve(ctx, ctx->fb_chunks,
                       t * (sizeof(FrameChunk) + 4 + 8 + 8 +
                            2 * sizeof(snapmi_error) + 8 + 8 + 8 + 8 + 8 + 1 +
                            4) + 8 + 16 * 16)))
         return rc;
-    p = (uint8_t *)ctx->fb_chunks.p;
+    uint8_t *p = (uint8_t *)ctx->fb_chunks.p;
     a.total = (uint32_t)total;
     a.chunks = carve<FrameChunk>(p, t);
     a.c_stream = carve<uint32_t>(p, t);
@@ -2021,13 +1845,19 @@ int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
     HIP_TRY(ctx, hipMemsetAsync(a.first_bad, 0xFF, n * sizeof(uint32_t), s));
     const uint32_t tb = 256;
     const uint32_t gc = total ? (uint32_t)((total + tb - 1) / tb) : 1;
+    const uint32_t gs = (uint32_t)((n + 63) / 64);
+    if (list)
+        hipLaunchKernelGGL(k_fbd_from_list,
+                           dim3((uint32_t)((total + n + tb - 1) / tb)),
+                           dim3(tb), 0, s, a, l_first, list, bad);
     if (total) {
-        hipLaunchKernelGGL(k_fbd_walk_fill, dim3(gs), dim3(64), 0, s, a);
+        if (!list)
+            hipLaunchKernelGGL(k_fbd_walk_fill, dim3(gs), dim3(64), 0, s, a);
         hipLaunchKernelGGL(k_fbd_lens, dim3(gc), dim3(tb), 0, s, a);
     }
     hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.dlens, a.offs,
                        a.total);
-    if (d_out_ptrs && total) {
+    if (a.out_ptrs && total) {
         hipLaunchKernelGGL(k_fbd_desc, dim3(gc), dim3(tb), 0, s, a);
         rc = launch_decompress(ctx, a.c_in, a.c_in_len, a.c_out, a.c_caps,
                                a.c_out_lens, a.derrs, a.modes, t);
@@ -2044,6 +1874,72 @@ int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
     HIP_TRY(ctx, hipGetLastError());
     return SNAPMI_OK;
 }
+
+int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
+                                  const void *const *d_in_ptrs,
+                                  const uint64_t *d_in_lens,
+                                  void *const *d_out_ptrs,
+                                  const uint64_t *d_out_caps,
+                                  uint64_t *d_out_lens, snapmi_error *d_errs,
+                                  size_t n)
+{
+    const char *what = "frame_decompress_batch";
+    if (!ctx)
+        return SNAPMI_E_ARGUMENT;
+    if (n == 0)
+        return SNAPMI_OK;
+    FrameBatchDecodeArgs a;
+    int rc = fbd_begin(ctx, what, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
+                       d_out_lens, d_errs, n, a);
+    if (rc || (rc = mailbox(ctx)))
+        return rc;
+    hipStream_t s = ctx->stream;
+    const uint32_t gs = (uint32_t)((n + 63) / 64);
+    hipLaunchKernelGGL(k_fbd_walk_count, dim3(gs), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.counts,
+                       a.first, (uint32_t)n);
+    // the one wait: the number of data chunks sizes everything below
+    hipLaunchKernelGGL(k_post_words, dim3(1), dim3(64), 0, s,
+                       (uint32_t *)ctx->h_mail, (const uint32_t *)(a.first + n),
+                       2u);
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    const uint64_t total =
+        (uint64_t)ctx->h_mail[0] | ((uint64_t)ctx->h_mail[1] << 32);
+    return fbd_finish(ctx, what, a, total, nullptr, nullptr, nullptr);
+}
+
+} // extern "C"
+
+// snapmi_frame_decompress_batch of streams the host has walked
+// (snapmi_framewalk.hpp: frame_walk_host found every one of them well-formed
+// from start to end): d_first[i] is the first data chunk of stream i
+// (d_first[n] = total), d_list the chunks.  k_fbd_from_list stands in for the
+// two walk kernels, the scan of their counts and the wait for the total, so
+// this call only enqueues; a list that disagrees with the bytes sets *d_bad
+// (device memory the caller has cleared) and leaves nothing decoded from the
+// chunks in question.  Verdicts, lengths and error fields come from the
+// kernels behind it, as ever.
+int snapmi::frame_decompress_batch_listed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    void *const *d_out_ptrs, const uint64_t *d_out_caps, uint64_t *d_out_lens,
+    snapmi_error *d_errs, size_t n, const uint64_t *d_first,
+    const void *d_list, uint64_t total, uint32_t *d_bad)
+{
+    const char *what = "frame_decompress_batch (listed)";
+    if (!ctx || !d_first || !d_list || !d_bad)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "%s: bad args", what);
+    if (n == 0)
+        return SNAPMI_OK;
+    FrameBatchDecodeArgs a;
+    int rc = fbd_begin(ctx, what, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
+                       d_out_lens, d_errs, n, a);
+    if (rc)
+        return rc;
+    return fbd_finish(ctx, what, a, total, d_first, (const FwEntry *)d_list,
+                      d_bad);
+}
+
+extern "C" {
 
 // ----------------------------------------------------------------------
 // Host-buffer forms (H2D + kernels + D2H, blocking): what a host-language

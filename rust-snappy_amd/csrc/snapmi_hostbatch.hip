@@ -1,5 +1,7 @@
-// snapmi_hostbatch.hip -- many independent raw streams in HOST memory per
-// call: snapmi_compress_batch_host / snapmi_decompress_batch_host.
+// snapmi_hostbatch.hip -- many independent streams in HOST memory per call,
+// raw (snapmi_compress_batch_host / snapmi_decompress_batch_host) or framed
+// (snapmi_frame_compress_batch_host / snapmi_frame_decompress_batch_host): one
+// pipeline, the codec is a parameter.
 //
 // The batch is cut into slices of whole streams (snapmi_hostbatch.hpp) and
 // the slices go through the three slots of the host pipe
@@ -12,9 +14,14 @@
 //         the slot's pinned staging and go to the device as ONE copy; a
 //         stream of host_batch_direct_min bytes or more is copied from where
 //         it lies instead (the staging copy would cost what the H2D costs)
-//   codec snapmi_compress_batch / snapmi_decompress_batch, unchanged, on the
-//         context's stream; lengths and errors land in the head of the
-//         slice's "home image"
+//   codec snapmi_compress_batch / snapmi_decompress_batch or their frame_
+//         forms, unchanged, on the context's stream; lengths and errors land
+//         in the head of the slice's "home image".  Framed decode: the host
+//         has walked every stream's chunk headers (snapmi_framewalk.hpp) for
+//         the rooms below, so a slice whose streams are all well-formed sends
+//         its chunk list behind the inputs, in the same copy, and the device
+//         neither walks nor makes the host wait for a chunk count
+//         (frame_decompress_batch_listed)
 //   out   compress: the kernels leave every stream in a slot of
 //         max_compress_len bytes and only the device knows what was written:
 //         k_hb_sizes + k_scan_u64 give packed offsets and k_hb_pack gathers
@@ -24,7 +31,9 @@
 //         decompress: the host has read every header, the output slab is
 //         tight already: one D2H of head + slab.
 //   home  the host hands every successful stream from staging to its
-//         caller's buffer; a failed stream's buffer is not touched.
+//         caller's buffer; a failed stream's buffer is not touched - except
+//         that a framed stream that fails to decode delivers the chunks in
+//         front of the failure, as the reader it mirrors has by then.
 //
 // Verdicts, lengths and error fields always come from the device.
 #include <hip/hip_runtime.h>
@@ -36,6 +45,7 @@
 #include "snapmi_ctx.hpp"
 #include "snapmi_hostpipe.hpp"
 #include "snapmi_hostbatch.hpp"
+#include "snapmi_framewalk.hpp"
 #include "snapmi_device.hpp"
 
 using namespace snapmi;
@@ -117,14 +127,28 @@ struct SliceState {
     size_t m = 0;       // streams
     uint64_t desc = 0;  // bytes of the four descriptor arrays, aligned
     uint64_t head = 0;  // bytes of out_lens + errs in the home image, aligned
+    // framed decode from the host's chunk list: its data chunks, and the
+    // bytes of first[m + 1] + list[chunks] behind the slice's inputs
+    bool listed = false;
+    uint64_t chunks = 0, extra = 0;
 };
 
-int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
-               const size_t *h_in_lens, void *const *h_out_ptrs,
-               const size_t *h_out_caps, size_t *h_out_lens,
-               snapmi_error *h_errs, size_t n)
+enum Codec { kRaw, kFrame };
+
+int host_batch(snapmi_ctx *ctx, Codec codec, bool compress,
+               const void *const *h_in_ptrs, const size_t *h_in_lens,
+               void *const *h_out_ptrs, const size_t *h_out_caps,
+               size_t *h_out_lens, snapmi_error *h_errs, size_t n)
 {
-    const char *what = compress ? "compress_batch_host" : "decompress_batch_host";
+    const bool frame = codec == kFrame;
+    const char *what =
+        frame ? (compress ? "frame_compress_batch_host"
+                          : "frame_decompress_batch_host")
+              : (compress ? "compress_batch_host" : "decompress_batch_host");
+    // framed decode: a failing stream delivers the chunks in front of the
+    // failure; without output buffers it reports lengths only
+    const bool prefix = frame && !compress;
+    const bool lens_only = prefix && !h_out_ptrs;
     if (!ctx) {
         // (no context can be made without a device: say so)
         int count = 0;
@@ -136,24 +160,49 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
     }
     if (n == 0)
         return SNAPMI_OK;
-    if (!h_in_ptrs || !h_in_lens || !h_out_ptrs || !h_out_caps ||
-        !h_out_lens || n > 0x7FFFFFFFu)
+    if (!h_in_ptrs || !h_in_lens || !h_out_lens ||
+        (!lens_only && (!h_out_ptrs || !h_out_caps)) || n > 0x7FFFFFFFu)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "%s: bad args", what);
     for (size_t i = 0; i < n; i++)
         if ((h_in_lens[i] && !h_in_ptrs[i]) ||
-            (h_out_caps[i] && !h_out_ptrs[i]))
+            (!lens_only && h_out_caps[i] && !h_out_ptrs[i]))
             return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
                             "%s: stream %zu: NULL buffer", what, i);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->hb_slices = ctx->hb_h2d_bytes = ctx->hb_d2h_bytes = 0;
+    ctx->hb_listed_slices = 0;
     // what the codec may write for every stream: the slot the reference
-    // demands (src/compress.rs:111-116) / the length the header announces,
-    // and nothing for a stream the device is going to refuse
+    // demands (src/compress.rs:111-116, src/frame.rs:12) / the length the
+    // header announces / the lengths the chunk headers announce, and nothing
+    // for a stream the device is going to refuse
     std::vector<uint64_t> rooms(n);
+    // framed decode: the data chunks of every stream (stream i owns
+    // list[first[i], first[i + 1])) and whether the walk accepted all of it
+    const bool want_list = prefix && ctx->host_batch_listed;
+    std::vector<FwEntry> list;
+    std::vector<uint64_t> first(want_list ? n + 1 : 0);
+    std::vector<uint8_t> regular(want_list ? n : 0);
     for (size_t i = 0; i < n; i++) {
         h_out_lens[i] = 0;
         uint64_t room = 0;
-        if (compress) {
+        if (frame && compress) {
+            const size_t need = snapmi_frame_max_len(h_in_lens[i]);
+            if (h_in_lens[i] && need <= h_out_caps[i])
+                room = need;
+        } else if (frame) {
+            if (want_list)
+                first[i] = list.size();
+            const FwStream w = frame_walk_host(
+                (const uint8_t *)h_in_ptrs[i], h_in_lens[i],
+                [&](uint64_t off, uint32_t hd) {
+                    if (want_list)
+                        list.push_back(FwEntry{off, (uint32_t)i, hd});
+                });
+            if (want_list)
+                regular[i] = w.e.kind == SNAPMI_OK;
+            if (!lens_only && w.room <= h_out_caps[i])
+                room = w.room;
+        } else if (compress) {
             const size_t need = snapmi_max_compress_len(h_in_lens[i]);
             if (need && need <= h_out_caps[i])
                 room = need;
@@ -168,6 +217,8 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
         }
         rooms[i] = room;
     }
+    if (want_list)
+        first[n] = list.size();
     snapmi_host_pipe *P;
     int rc = host_pipe(ctx, &P);
     if (rc)
@@ -199,21 +250,33 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
                                  st.out_offs.data());
             const size_t m = st.m;
             st.desc = hb_align(32 * (uint64_t)m);
-            st.head = hb_align((8 + sizeof(snapmi_error)) * (uint64_t)m);
+            // (framed decode: 16 bytes more, the word k_fbd_from_list raises)
+            st.head = hb_align((8 + sizeof(snapmi_error)) * (uint64_t)m) +
+                      (prefix ? 16 : 0);
+            st.listed = want_list;
+            for (size_t i = 0; st.listed && i < m; i++)
+                st.listed = regular[cursor + i];
+            st.chunks = st.listed ? first[st.x.s1] - first[cursor] : 0;
+            if (st.chunks > 0x7FFFFFFFu)
+                st.listed = false; // (the device call reports it)
+            st.extra = st.listed ? hb_align(8 * (uint64_t)(m + 1)) +
+                                       sizeof(FwEntry) * st.chunks
+                                 : 0;
             uint64_t staged = st.desc;
             for (size_t i = 0; i < m; i++) {
                 const uint64_t len = h_in_lens[cursor + i];
                 if (len < direct_min)
                     staged += hb_align(len + kHbInSlack);
             }
-            if ((rc = slot_reserve(ctx, s.in, st.desc + st.x.in_bytes + 16)) ||
+            if ((rc = slot_reserve(ctx, s.in, st.desc + st.x.in_bytes +
+                                                  st.extra + 16)) ||
                 (rc = slot_reserve(ctx, s.home,
                                    st.head + (to_host ? 0 : st.x.out_bytes) +
                                        64)) ||
                 (compress &&
                  ((rc = slot_reserve(ctx, s.out, st.x.out_bytes + 64)) ||
                   (rc = slot_reserve(ctx, s.desc, (2 * m + 1) * 8 + 64)))) ||
-                (rc = pin_buf(ctx, s.hb_in, staged + 16)) ||
+                (rc = pin_buf(ctx, s.hb_in, staged + st.extra + 16)) ||
                 (rc = pin_buf(ctx, s.hb_home, st.head + st.x.out_bytes + 64)))
                 return rc;
             uint8_t *hs = (uint8_t *)s.hb_in.p;
@@ -237,7 +300,7 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
                 a_out_ptrs[i] = (uint64_t)(uintptr_t)(d_out + st.out_offs[i]);
                 // (the caller's capacity is what the device validates and
                 // reports; it writes no more than the room worked out above)
-                a_out_caps[i] = h_out_caps[g];
+                a_out_caps[i] = lens_only ? 0 : h_out_caps[g];
                 if (len < direct_min) {
                     if (len)
                         memcpy(hs + stage, h_in_ptrs[g], len);
@@ -257,6 +320,20 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
                 run_stage = stage;
                 run_dev = dev_off + hb_align(len + kHbInSlack);
                 split = true;
+            }
+            if (st.listed) {
+                // behind the last input, on the device as in staging: part
+                // of the slice's last (or only) copy
+                uint64_t *l_first = (uint64_t *)(hs + stage);
+                FwEntry *l = (FwEntry *)(hs + stage + hb_align(8 * (m + 1)));
+                const uint64_t base = first[cursor];
+                for (size_t i = 0; i <= m; i++)
+                    l_first[i] = first[cursor + i] - base;
+                for (uint64_t c = 0; c < st.chunks; c++) {
+                    l[c] = list[base + c];
+                    l[c].stream -= (uint32_t)cursor;
+                }
+                stage += st.extra;
             }
             if (split && stage > run_stage) {
                 HIP_TRY(ctx, hipMemcpyAsync(d_in + run_dev, hs + run_stage,
@@ -290,9 +367,10 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
             HIP_TRY(ctx, hipMemsetAsync(s.home.p, 0, st.head, sK));
             if (compress) {
                 const uint64_t *h_lens = (const uint64_t *)s.hb_in.p + m;
-                if ((rc = snapmi_compress_batch(ctx, d_in_ptrs, d_in_lens,
-                                                h_lens, d_out_ptrs, d_out_caps,
-                                                d_out_lens, d_errs, m)))
+                if ((rc = (frame ? snapmi_frame_compress_batch
+                                 : snapmi_compress_batch)(
+                         ctx, d_in_ptrs, d_in_lens, h_lens, d_out_ptrs,
+                         d_out_caps, d_out_lens, d_errs, m)))
                     return rc;
                 uint64_t *sizes = (uint64_t *)s.desc.p, *offs = sizes + m;
                 hipLaunchKernelGGL(k_hb_sizes,
@@ -319,9 +397,26 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
                     return rc;
                 HIP_TRY(ctx, hipEventRecord(s.ev_k, sK));
             } else {
-                if ((rc = snapmi_decompress_batch(ctx, d_in_ptrs, d_in_lens,
-                                                  d_out_ptrs, d_out_caps,
-                                                  d_out_lens, d_errs, m)))
+                void *const *d_outs = lens_only ? nullptr : d_out_ptrs;
+                const uint8_t *d_extra = dd + st.desc + st.x.in_bytes;
+                if (st.listed) {
+                    rc = frame_decompress_batch_listed(
+                        ctx, d_in_ptrs, d_in_lens, d_outs, d_out_caps,
+                        d_out_lens, d_errs, m, (const uint64_t *)d_extra,
+                        d_extra + hb_align(8 * (m + 1)), st.chunks,
+                        (uint32_t *)((uint8_t *)s.home.p + st.head - 16));
+                    ctx->hb_listed_slices++;
+                } else if (frame) {
+                    rc = snapmi_frame_decompress_batch(ctx, d_in_ptrs,
+                                                       d_in_lens, d_outs,
+                                                       d_out_caps, d_out_lens,
+                                                       d_errs, m);
+                } else {
+                    rc = snapmi_decompress_batch(ctx, d_in_ptrs, d_in_lens,
+                                                 d_out_ptrs, d_out_caps,
+                                                 d_out_lens, d_errs, m);
+                }
+                if (rc)
                     return rc;
                 HIP_TRY(ctx, hipEventRecord(s.ev_k, sK));
                 HIP_TRY(ctx, hipStreamWaitEvent(P->s_out, s.ev_k, 0));
@@ -360,14 +455,23 @@ int host_batch(snapmi_ctx *ctx, bool compress, const void *const *h_in_ptrs,
             const uint64_t *lens = (const uint64_t *)h_home;
             const snapmi_error *errs = (const snapmi_error *)(h_home + 8 * m);
             const uint8_t *payload = h_home + st.head;
+            if (prefix && *(const uint32_t *)(h_home + st.head - 16))
+                return fail_ctx(ctx, SNAPMI_E_DEVICE,
+                                "%s: streams %zu..%zu: the chunk list "
+                                "disagrees with the bytes on the device",
+                                what, st.x.s0, st.x.s1);
             uint64_t off = 0;
             for (size_t i = 0; i < m; i++) {
                 const size_t g = st.x.s0 + i;
                 if (h_errs)
                     h_errs[g] = errs[i];
-                if (errs[i].kind != SNAPMI_OK)
+                if (errs[i].kind != SNAPMI_OK && !prefix)
                     continue;
                 const uint64_t len = lens[i];
+                if (lens_only) {
+                    h_out_lens[g] = (size_t)len;
+                    continue;
+                }
                 if (len > rooms[g])
                     return fail_ctx(ctx, SNAPMI_E_DEVICE,
                                     "%s: stream %zu: device wrote %llu > %llu",
@@ -403,8 +507,8 @@ int snapmi_compress_batch_host(snapmi_ctx *ctx, const void *const *h_in_ptrs,
                                const size_t *h_out_caps, size_t *h_out_lens,
                                snapmi_error *h_errs, size_t n)
 {
-    return host_batch(ctx, true, h_in_ptrs, h_in_lens, h_out_ptrs, h_out_caps,
-                      h_out_lens, h_errs, n);
+    return host_batch(ctx, kRaw, true, h_in_ptrs, h_in_lens, h_out_ptrs,
+                      h_out_caps, h_out_lens, h_errs, n);
 }
 
 int snapmi_decompress_batch_host(snapmi_ctx *ctx,
@@ -414,7 +518,31 @@ int snapmi_decompress_batch_host(snapmi_ctx *ctx,
                                  const size_t *h_out_caps, size_t *h_out_lens,
                                  snapmi_error *h_errs, size_t n)
 {
-    return host_batch(ctx, false, h_in_ptrs, h_in_lens, h_out_ptrs,
+    return host_batch(ctx, kRaw, false, h_in_ptrs, h_in_lens, h_out_ptrs,
+                      h_out_caps, h_out_lens, h_errs, n);
+}
+
+int snapmi_frame_compress_batch_host(snapmi_ctx *ctx,
+                                     const void *const *h_in_ptrs,
+                                     const size_t *h_in_lens,
+                                     void *const *h_out_ptrs,
+                                     const size_t *h_out_caps,
+                                     size_t *h_out_lens, snapmi_error *h_errs,
+                                     size_t n)
+{
+    return host_batch(ctx, kFrame, true, h_in_ptrs, h_in_lens, h_out_ptrs,
+                      h_out_caps, h_out_lens, h_errs, n);
+}
+
+int snapmi_frame_decompress_batch_host(snapmi_ctx *ctx,
+                                       const void *const *h_in_ptrs,
+                                       const size_t *h_in_lens,
+                                       void *const *h_out_ptrs,
+                                       const size_t *h_out_caps,
+                                       size_t *h_out_lens,
+                                       snapmi_error *h_errs, size_t n)
+{
+    return host_batch(ctx, kFrame, false, h_in_ptrs, h_in_lens, h_out_ptrs,
                       h_out_caps, h_out_lens, h_errs, n);
 }
 

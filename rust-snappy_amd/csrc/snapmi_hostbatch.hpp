@@ -1,6 +1,6 @@
 // snapmi_hostbatch.hpp -- the plan of the host-memory batch calls
-// (snapmi_compress_batch_host / snapmi_decompress_batch_host,
-// snapmi_hostbatch.hip), in plain C++ that the host code, the pack kernel and
+// (snapmi_compress_batch_host / snapmi_decompress_batch_host and their
+// frame_ forms, snapmi_hostbatch.hip), in plain C++ that the host code, the pack kernel and
 // a CPU test (tests/hostbatch_host.cpp) compile alike:
 //
 //   hb_plan_slice   which streams form the next slice of a batch, where each
@@ -53,8 +53,8 @@ struct HbSlice {
 
 // The slice that starts at stream s0 (s0 < n).  in_lens[i]: input bytes of
 // stream i; rooms[i]: bytes the codec may write for it (compress:
-// max_compress_len, decompress: the header's length; 0 for a stream that
-// will be refused).  Streams are added in order while the slice's input
+// max_compress_len / frame_max_len, decompress: the header's length / what
+// the chunk headers announce; 0 for a stream that will be refused).  Streams are added in order while the slice's input
 // stays within in_limit and its rooms within out_limit; a stream that alone
 // exceeds either is a slice of its own.  in_offs / out_offs (each s1 - s0
 // values when not NULL, indexed i - s0) receive the streams' offsets in the

@@ -80,5 +80,18 @@ int pipe_copy_home(snapmi_ctx *ctx, hipStream_t st, uint8_t *h_dst,
 // k_scan_u64: out[0..n) = exclusive scan of in[0..n), out[n] = total
 int launch_scan_u64(snapmi_ctx *ctx, hipStream_t st, const uint64_t *in,
                     uint64_t *out, uint32_t n);
+// snapmi_frame_decompress_batch of n streams the host has walked: d_first
+// [n + 1] and d_list [total] (FwEntry, snapmi_framewalk.hpp) replace the
+// device's walk and its wait; *d_bad (cleared by the caller) is raised when
+// the list disagrees with the bytes
+int frame_decompress_batch_listed(snapmi_ctx *ctx,
+                                  const void *const *d_in_ptrs,
+                                  const uint64_t *d_in_lens,
+                                  void *const *d_out_ptrs,
+                                  const uint64_t *d_out_caps,
+                                  uint64_t *d_out_lens, snapmi_error *d_errs,
+                                  size_t n, const uint64_t *d_first,
+                                  const void *d_list, uint64_t total,
+                                  uint32_t *d_bad);
 
 } // namespace snapmi

@@ -237,6 +237,97 @@ def decompress_many(ctx, src, caps=None):
     return dst, out_lens.cpu().numpy(), _batch.read_errors(errs)
 
 
+def batch_host(ctx, compress, in_ptrs, in_lens, out_ptrs, out_caps):
+    """snapmi_frame_compress_batch_host / snapmi_frame_decompress_batch_host
+    over arrays of host addresses and lengths, as raw.batch_host; out_ptrs
+    None (decompress): lengths only.  Returns (out_lens as uint64 array,
+    errors as a raw.ERROR_DTYPE array)."""
+    in_ptrs = np.ascontiguousarray(in_ptrs, dtype=np.uint64)
+    in_lens = np.ascontiguousarray(in_lens, dtype=np.uint64)
+    n = int(in_ptrs.size)
+    assert in_lens.size == n
+    if out_ptrs is not None:
+        out_ptrs = np.ascontiguousarray(out_ptrs, dtype=np.uint64)
+        out_caps = np.ascontiguousarray(out_caps, dtype=np.uint64)
+        assert out_ptrs.size == out_caps.size == n
+    out_lens = np.zeros(n, dtype=np.uint64)
+    errs = np.zeros(n, dtype=raw.ERROR_DTYPE)
+    L = _lib.of(ctx)
+    f = L.snapmi_frame_compress_batch_host if compress \
+        else L.snapmi_frame_decompress_batch_host
+    p = raw._np_ptr
+    rc = f(ctx._h, p(in_ptrs), p(in_lens),
+           p(out_ptrs) if out_ptrs is not None else None,
+           p(out_caps) if out_ptrs is not None else None, p(out_lens),
+           p(errs), n)
+    if rc:
+        raw._raise(ctx, rc)
+    return out_lens, errs
+
+
+def _host_views(streams):
+    # the inputs where they lie (no join, no copy)
+    views = [np.frombuffer(s, dtype=np.uint8) if len(s) else None
+             for s in streams]
+    return (views, [v.ctypes.data if v is not None else 0 for v in views],
+            [v.size if v is not None else 0 for v in views])
+
+
+def _many_host(ctx, compress, streams, caps):
+    ctx = ctx or raw.default_context()
+    views, in_ptrs, in_lens = _host_views(streams)
+    caps = np.asarray([int(c) for c in caps], dtype=np.uint64)
+    offs = np.zeros(len(caps) + 1, dtype=np.uint64)
+    np.cumsum(caps, out=offs[1:])
+    slab = np.empty(max(int(offs[-1]), 1), dtype=np.uint8)
+    out_ptrs = offs[:-1] + np.uint64(slab.ctypes.data)
+    out_lens, errs = batch_host(ctx, compress, in_ptrs, in_lens, out_ptrs,
+                                caps)
+    del views
+    result = []
+    for i in range(len(caps)):
+        o, e = int(offs[i]), errs[i]
+        got = slab[o:o + int(out_lens[i])].tobytes()
+        if e["kind"]:
+            got, delivered = Error(int(e["kind"]), int(e["a"]), int(e["b"]),
+                                   int(e["c"])), got
+            got.partial = delivered    # the chunks in front of the failure
+        result.append(got)
+    return result
+
+
+def compress_many_host(streams, ctx=None):
+    """One write::FrameEncoder::write_all + into_inner per stream (bytes-like
+    objects in host memory), all in one snapmi_frame_compress_batch_host
+    call.  Returns a list: the framed bytes of every stream (an Error in the
+    place of a stream that failed)."""
+    return _many_host(ctx, True, streams,
+                      [frame_max_len(len(s)) for s in streams])
+
+
+def decoded_lens_host(streams, ctx=None):
+    """The lengths-only form of snapmi_frame_decompress_batch_host: (lengths
+    as uint64 array, errors as a raw.ERROR_DTYPE array) - what every stream
+    decodes to; for a stream that fails, the bytes in front of the failure."""
+    ctx = ctx or raw.default_context()
+    views, in_ptrs, in_lens = _host_views(streams)
+    res = batch_host(ctx, False, in_ptrs, in_lens, None, None)
+    del views
+    return res
+
+
+def decompress_many_host(streams, ctx=None, caps=None):
+    """One read::FrameDecoder read to its end per stream, all in one
+    snapmi_frame_decompress_batch_host call; caps: output capacities
+    (default: a lengths-only pass sizes them, like decompress_many).  Returns
+    a list: the decoded bytes of every stream, or its Error, whose `partial`
+    holds the bytes the reader had delivered by then."""
+    ctx = ctx or raw.default_context()
+    if caps is None:
+        caps = decoded_lens_host(streams, ctx)[0]
+    return _many_host(ctx, False, streams, caps)
+
+
 def encode_host(ctx, data, chunk_lens, ident=True):
     """snapmi_frame_encode_host: host bytes -> framed bytes, chunk boundaries
     given by the caller."""

@@ -106,7 +106,8 @@ class Context:
         """snapmi_ctx_get_info: "scratch_bytes", "token_scratch_bytes",
         "token_pool_pages", "token_pool_pct_now", "token_pages_asked",
         "token_blocks_spilled", "host_batch_slices", "host_batch_h2d_bytes",
-        "host_batch_d2h_bytes" (include/snapmi.h)."""
+        "host_batch_d2h_bytes", "host_batch_listed_slices"
+        (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:

@@ -1,0 +1,341 @@
+"""The host-memory frame batch calls (snapmi_frame_compress_batch_host /
+snapmi_frame_decompress_batch_host) on the CPU: the chunk-header walk the
+host runs while it stages a framed stream (csrc/snapmi_framewalk.hpp, the
+kernels' own walk compiled for the host) - its regular / irregular answer
+against snapmi_frame_index_host, its chunk list against the oracle's chunk
+structure, its room against what the oracle's decoder delivers -, the exports
+and bindings, the option and info names, and the loud failure without a
+GPU."""
+import ctypes as C
+import random
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import oracle_lib as O
+from conftest import ROOT
+
+IDENT = b"\xff\x06\x00\x00sNaPpY"
+E_DEVICE, E_ARGUMENT = 100, 101
+UNEXPECTED_EOF = 64
+CORPUS = ["html", "urls.10K", "fireworks.jpeg", "paper-100k.pdf", "html_x_4",
+          "alice29.txt", "asyoulik.txt", "lcet10.txt", "plrabn12.txt",
+          "geo.protodata", "kppkn.gtb", "Mark.Twain-Tom.Sawyer.txt"]
+CAP = 1 << 20
+
+
+@pytest.fixture(scope="module")
+def W(tmp_path_factory):
+    so = tmp_path_factory.mktemp("framewalk") / "framewalk_host.so"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-shared",
+                           "-fPIC", "-I", str(ROOT / "include"),
+                           str(ROOT / "tests" / "framewalk_host.cpp"),
+                           "-o", str(so)])
+    L = C.CDLL(str(so))
+    L.t_entry_bytes.restype = C.c_uint64
+    L.t_walk.restype = None
+    L.t_walk.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                         C.c_uint64]
+    L.t_index.restype = C.c_int
+    L.t_index.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                          C.POINTER(C.c_uint64)]
+    return L
+
+
+def chunk(ty, body, crc=b""):
+    n = len(crc) + len(body)
+    return bytes([ty, n & 255, (n >> 8) & 255, n >> 16]) + crc + body
+
+
+def error_streams():
+    """Malformed streams of every kind the reader knows, streams with chunks
+    it skips, errors behind good chunks, and the payloads of fewer than 10
+    bytes without a varint terminator (the stale-buffer rule)."""
+    html = (O.CORPUS / "html").read_bytes()
+    good = O.frame_compress(html)
+    out = [b"123", b"\x00\x05\x00\x00abcde", b"\xff\x06\x00\x00sNaPpX",
+           b"\xff\x05\x00\x00sNaPp", IDENT + b"\x02\x01\x00\x00a",
+           IDENT + b"\x00\xff\xff\xff", IDENT + b"\x00\x03\x00\x00abc",
+           IDENT + chunk(1, b"x" * 65537, b"\0\0\0\0")]
+    bad = bytearray(good)
+    bad[10 + 4] ^= 0x55
+    out.append(bytes(bad))                              # checksum
+    bad = bytearray(good)
+    bad[10 + 8 + 3 + 5] ^= 0xFF
+    out.append(bytes(bad))                              # corrupt payload
+    rng = random.Random(5)
+    for _ in range(12):
+        bad = bytearray(good)
+        bad[10 + 8 + rng.randrange(3, 2000)] ^= 1 << rng.randrange(8)
+        out.append(bytes(bad))
+    out.append(good[:-5])                               # truncated
+    out.append(IDENT + b"\x80\x03\x00\x00xyz" + b"\xfe\x02\x00\x00pp"
+               + good[10:] + IDENT)
+    out.append(good + good[10:])
+    out.append(good + good[10:40])
+    out.append(good + b"\x02\x01\x00\x00a")
+    out.append(good + b"\xff\x06\x00\x00sNaPpZ")
+    crc = b"\x11\x22\x33\x44"
+    skip = lambda body: chunk(0x80, body)  # noqa: E731
+    out += [
+        IDENT + chunk(0, b"\xff\xff", crc),
+        IDENT + chunk(0, b"", crc),
+        IDENT + skip(b"\xaa" * 5 + b"\x7f" + b"\xaa" * 4)
+        + chunk(0, b"\xff" * 5, crc),
+        IDENT + skip(b"\xbb" * 4 + b"\x01" + b"\xbb" * 5)
+        + chunk(0, b"\x80" * 4, crc),
+        good + chunk(0, b"\x80" * 6, crc),
+        IDENT + skip(b"\xcc" * 10) + chunk(0, b"\x80" * 4, crc),
+        IDENT + skip(b"\xdd" * 5 + b"\x03" + b"\xdd" * 4)
+        + chunk(1, b"x" * 20, O.crc32c_masked(b"x" * 20).to_bytes(4, "little"))
+        + chunk(0, b"\x80" * 5, crc),
+        # a chunk that announces more than a block, between good ones
+        good + chunk(0, b"\x81\x80\x04" + b"a" * 9, crc) + good[10:],
+        b"", IDENT,
+    ]
+    return out
+
+
+def mixed_batch():
+    goods = [(O.CORPUS / n).read_bytes()[:90000] for n in CORPUS]
+    streams = []
+    for k, s in enumerate(error_streams()):
+        streams += [O.frame_compress(goods[k % len(goods)]), s]
+    return streams
+
+
+def walk(W, s, cap=4096):
+    out = np.zeros(6, dtype=np.uint64)
+    ent = np.zeros(2 * cap, dtype=np.uint64)
+    W.t_walk(bytes(s), len(s), out.ctypes.data_as(C.c_void_p),
+             ent.ctypes.data_as(C.c_void_p), cap)
+    kind, a, b, room, chunks, k = (int(x) for x in out)
+    assert k == chunks <= cap
+    kind = kind - (1 << 64) if kind >> 63 else kind
+    return (kind, a, b), room, [(int(ent[2 * i]), int(ent[2 * i + 1]))
+                                for i in range(chunks)]
+
+
+def index_host(s):
+    """snapmi_frame_index_host of the library: (answer, header offsets)."""
+    from rust_snappy_amd import _lib
+    L = _lib.load()
+    offs = np.zeros(len(s) // 8 + 2, dtype=np.uint64)
+    n = C.c_uint64(0)
+    rc = L.snapmi_frame_index_host(bytes(s), len(s),
+                                   offs.ctypes.data_as(C.c_void_p), offs.size,
+                                   C.byref(n))
+    return rc, [int(x) for x in offs[:n.value]] if rc == 0 else None
+
+
+class Delivered:
+    """What the oracle's FrameDecoder hands out before its verdict: the
+    oracle reports a length only on success, so the stream is decoded into
+    two buffers of opposite fill - the bytes it delivered are where they
+    agree."""
+
+    def __init__(self, cap=CAP):
+        self.cap = cap
+        self.a = np.zeros(cap, dtype=np.uint8)
+        self.b = np.full(cap, 0xFF, dtype=np.uint8)
+
+    def __call__(self, s):
+        res = []
+        for buf, fill in ((self.a, 0), (self.b, 0xFF)):
+            n, e = C.c_size_t(0), O.OracleError()
+            k = O.lib().snapo_frame_decompress(
+                bytes(s), len(s), buf.ctypes.data_as(C.c_void_p), self.cap,
+                C.byref(n), C.byref(e))
+            res.append((k, n.value, e.astuple()))
+        diff = np.flatnonzero(self.a != self.b)
+        got = int(diff[0]) if diff.size else self.cap
+        data = self.a[:got].tobytes()
+        self.a[:got + 65536] = 0
+        self.b[:got + 65536] = 0xFF
+        assert res[0] == res[1]
+        k, n, e = res[0]
+        if k == 0:
+            assert got == n
+        return got, data, (None if k == 0 else e)
+
+
+def py_chunks(s):
+    """The data chunks of a well-formed stream, parsed independently."""
+    r, out = 0, []
+    while r < len(s):
+        ty, n = s[r], int.from_bytes(s[r + 1:r + 4], "little")
+        if ty <= 1:
+            out.append((r, ty | n << 8))
+        r += 4 + n
+    assert r == len(s)
+    return out
+
+
+def check_stream(W, D, s):
+    """The three properties of one stream; returns (regular, walk verdict)."""
+    verdict, room, entries = walk(W, s)
+    rc, offs = index_host(s)
+    # the shared header's regular / irregular answer is the library's
+    n = C.c_uint64(0)
+    assert W.t_index(bytes(s), len(s), None, 0, C.byref(n)) == rc
+    regular = rc == 0
+    # a stream the walk accepts whole is regular; the one way to be regular
+    # and still refused by the walk is the stale-buffer rule
+    if verdict[0] == 0:
+        assert regular
+    delivered, data, oe = D(s)
+    assert room >= delivered, (room, delivered)
+    if regular:
+        assert n.value == len(offs)
+        if verdict[0] == 0:
+            assert [e[0] for e in entries] == offs
+            assert entries == py_chunks(s)
+        else:
+            assert oe is not None
+            assert [e[0] for e in entries] == offs[:len(entries)]
+        if oe is None:
+            assert verdict[0] == 0 and room == delivered == len(data)
+    else:
+        assert oe is not None and verdict[0] != 0
+    return regular, verdict
+
+
+def test_walk_on_error_streams_and_mixed_batch(W, built):
+    D = Delivered()
+    seen = set()
+    streams = error_streams() + mixed_batch()
+    for s in streams:
+        regular, verdict = check_stream(W, D, s)
+        seen.add((regular, verdict[0] == 0))
+    # well-formed, malformed, and regular but refused (stale-buffer rule)
+    assert seen == {(True, True), (False, False), (True, False)}
+
+
+def test_chunk_list_equals_the_oracles_chunks_on_the_corpus(W, built):
+    D = Delivered()
+    for name in CORPUS:
+        d = (O.CORPUS / name).read_bytes()
+        s = O.frame_compress(d)
+        regular, verdict = check_stream(W, D, s)
+        assert regular and verdict == (0, 0, 0)
+        # the oracle frames every 64 KiB block on its own
+        want, at = [], 10
+        for o in range(0, len(d), 65536):
+            c = O.frame_compress(d[o:o + 65536])[10:]
+            want.append((at, int.from_bytes(c[:4], "little")))
+            assert s[at:at + len(c)] == c
+            at += len(c)
+        assert at == len(s)
+        _, room, entries = walk(W, s)
+        assert entries == want and room == len(d)
+
+
+def test_truncations_at_every_byte_of_the_first_two_chunks(W, built):
+    d = (O.CORPUS / "geo.protodata").read_bytes()
+    s = O.frame_compress(d)
+    (o1, _), (o2, h2) = walk(W, s)[2]
+    o3 = o2 + 4 + (h2 >> 8)
+    assert o1 == 10 and o3 == len(s)
+    from rust_snappy_amd import _lib
+    L = _lib.load()
+    n = C.c_uint64(0)
+    # (the original is known here: one decode into a buffer that differs
+    # from it everywhere shows what was delivered)
+    cap = 1 << 17
+    orig = np.zeros(cap, dtype=np.uint8)
+    orig[:len(d)] = np.frombuffer(d, dtype=np.uint8)
+    buf = ~orig
+    for cut in range(0, o3 + 1):
+        t = s[:cut]
+        verdict, room, entries = walk(W, t, cap=4)
+        rc = L.snapmi_frame_index_host(t, cut, None, 0, C.byref(n))
+        regular = cut in (0, o1, o2, o3)
+        assert (rc == 0) == regular == (verdict[0] == 0), cut
+        assert W.t_index(t, cut, None, 0, C.byref(n)) == rc
+        chunks = (cut >= o2) + (cut >= o3)
+        assert len(entries) == chunks and room == (0, 65536, len(d))[chunks], cut
+        if not regular:
+            assert verdict[0] == UNEXPECTED_EOF, (cut, verdict)
+        w, e = C.c_size_t(0), O.OracleError()
+        k = O.lib().snapo_frame_decompress(
+            t, cut, buf.ctypes.data_as(C.c_void_p), cap, C.byref(w),
+            C.byref(e))
+        same = buf == orig
+        got = cap if same.all() else int(np.argmin(same))
+        buf[:got] = ~orig[:got]
+        assert room >= got, cut
+        assert (k == 0) == regular
+        if regular:
+            assert room == got == w.value
+
+
+def test_entry_layout(W):
+    assert W.t_entry_bytes() == 16
+
+
+def test_symbols_are_exported_and_bound(built):
+    from rust_snappy_amd import _lib, frame
+    bound = dict((s[0], s) for s in _lib.SYMBOLS)
+    names = ("snapmi_frame_compress_batch_host",
+             "snapmi_frame_decompress_batch_host")
+    for L in (_lib.load(), _lib.load_product()):
+        for name in names:
+            f = getattr(L, name)
+            assert name in bound and len(bound[name][2]) == 8
+            assert f.argtypes == bound[name][2] and f.restype is C.c_int
+    for m in ("snapmi.map", "snapmi_test.map"):
+        text = (ROOT / "rust-snappy_amd" / "csrc" / m).read_text()
+        for name in names:
+            assert name + ";" in text
+    assert subprocess.call(["python3", str(ROOT / "rust-snappy_amd" / "csrc" /
+                                           "gen_exports.py"), "--check"]) == 0
+    for f in (frame.compress_many_host, frame.decompress_many_host,
+              frame.decoded_lens_host, frame.batch_host):
+        assert callable(f)
+
+
+def test_library_carries_the_list_kernel(built):
+    for lib in ("libsnapmi.so", "libsnapmi_test.so"):
+        blob = (ROOT / "rust-snappy_amd" / lib).read_bytes()
+        assert b"k_fbd_from_list" in blob, lib
+
+
+def test_option_and_info_names_in_the_sources():
+    header = (ROOT / "include" / "snapmi.h").read_text()
+    test_h = (ROOT / "include" / "snapmi_test.h").read_text()
+    api = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_api.hip").read_text()
+    assert '"host_batch_listed_slices"' in header
+    assert '"host_batch_listed"' in test_h
+    for name in ("host_batch_listed_slices", "host_batch_listed"):
+        assert f'strcmp(name, "{name}") == 0' in api, name
+    for text in (header, ):
+        assert "4b. Many independent framed streams in HOST memory" in text
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="GPU present")
+def test_no_gpu_fails_loudly(built):
+    import rust_snappy_amd as R
+    from rust_snappy_amd import _lib, frame
+    with pytest.raises(R.DeviceError):
+        frame.compress_many_host([b"hello"])
+    with pytest.raises(R.DeviceError):
+        frame.decompress_many_host([O.frame_compress(b"hello")])
+    L = _lib.load()
+    data = np.frombuffer(b"hello world, hello world", dtype=np.uint8).copy()
+    out = np.full(128, 0xA5, dtype=np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    in_ptrs = np.array([data.ctypes.data], dtype=np.uint64)
+    in_lens = np.array([data.size], dtype=np.uint64)
+    out_ptrs = np.array([out.ctypes.data], dtype=np.uint64)
+    out_caps = np.array([out.size], dtype=np.uint64)
+    out_lens = np.array([77], dtype=np.uint64)
+    errs = np.full(32, 0x5A, dtype=np.uint8)
+    for f in (L.snapmi_frame_compress_batch_host,
+              L.snapmi_frame_decompress_batch_host):
+        rc = f(None, p(in_ptrs), p(in_lens), p(out_ptrs), p(out_caps),
+               p(out_lens), p(errs), 1)
+        assert rc == E_DEVICE
+        assert (out == 0xA5).all() and out_lens[0] == 77
+        assert (errs == 0x5A).all()

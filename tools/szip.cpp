@@ -13,6 +13,19 @@
 // stops the stream behind the bytes of the chunks in front of it, like the
 // reference's reader (src/read.rs:111-118).
 //
+// Several FILEs: runs of consecutive files below kBatchBelow bytes do not go
+// through that pipeline one by one - a context and three pipeline fills per
+// file, all overhead for a small file - but together through one
+// snapmi_frame_compress_batch_host / snapmi_frame_decompress_batch_host call
+// on one context (run_batch).  Names, flags, messages (one per failing file,
+// in argument order) and the exit status are the same either way.  The
+// threshold: measured (profiles/frame_host_batch.json) the pipeline costs
+// 54-67 ms per file whatever its size - a context each - and the batched path
+// won at every size tried, up to 1 MiB files, so no crossover was found; 1 MiB
+// is where a file alone gives the pipeline's three legs something to overlap
+// and where a run's staging would start to grow with the files, not their
+// count.
+//
 //   szip [-d] [-f] [-k] [-r] [-j N] [-v] [FILE...]     (stdin -> stdout without FILE)
 #include <sys/stat.h>
 #include <unistd.h>
@@ -21,6 +34,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,6 +51,8 @@ namespace {
 
 constexpr size_t kChunk = 65536;          // reference src/lib.rs:97
 constexpr size_t kSlab = 64u << 20;       // input bytes per device call
+constexpr size_t kBatchBelow = 1u << 20;  // smaller files are batched
+constexpr size_t kBatchBytes = 256u << 20; // input bytes of one batched run
 
 struct Options {
     bool decompress = false, force = false, keep = false, raw = false,
@@ -391,6 +407,33 @@ int run_stream(const Options &opt, FILE *src, FILE *dst, const char *name)
     return failed ? 1 : 0;
 }
 
+// The output name of `path` (reference new_path, szip/main.rs:183-205), or
+// why there is none: the message do_file and run_batch print.
+bool out_name(const Options &opt, const std::string &path, std::string &out,
+              std::string &why)
+{
+    const bool has_sz = path.size() > 3 &&
+                        path.compare(path.size() - 3, 3, ".sz") == 0;
+    if (opt.decompress) {
+        if (!has_sz) {
+            why = "szip: " + path + ": skipping uncompressed file";
+            return false;
+        }
+        out = path.substr(0, path.size() - 3);
+    } else {
+        if (has_sz) {
+            why = "szip: " + path + ": skipping compressed file";
+            return false;
+        }
+        out = path + ".sz";
+    }
+    if (!opt.force && access(out.c_str(), F_OK) == 0) {
+        why = "szip: skipping, file already exists: " + out;
+        return false;
+    }
+    return true;
+}
+
 int do_file(const Options &opt, const std::string &path)
 {
     struct stat st;
@@ -402,28 +445,9 @@ int do_file(const Options &opt, const std::string &path)
         fprintf(stderr, "szip: %s: is a directory\n", path.c_str());
         return 1;
     }
-    // reference new_path, szip/main.rs:183-205
-    std::string out;
-    const bool has_sz = path.size() > 3 &&
-                        path.compare(path.size() - 3, 3, ".sz") == 0;
-    if (opt.decompress) {
-        if (!has_sz) {
-            fprintf(stderr, "szip: %s: skipping uncompressed file\n",
-                    path.c_str());
-            return 1;
-        }
-        out = path.substr(0, path.size() - 3);
-    } else {
-        if (has_sz) {
-            fprintf(stderr, "szip: %s: skipping compressed file\n",
-                    path.c_str());
-            return 1;
-        }
-        out = path + ".sz";
-    }
-    if (!opt.force && access(out.c_str(), F_OK) == 0) {
-        fprintf(stderr, "szip: skipping, file already exists: %s\n",
-                out.c_str());
+    std::string out, why;
+    if (!out_name(opt, path, out, why)) {
+        fprintf(stderr, "%s\n", why.c_str());
         return 1;
     }
     FILE *src = fopen(path.c_str(), "rb");
@@ -459,6 +483,146 @@ int do_file(const Options &opt, const std::string &path)
     if (!opt.keep)
         unlink(path.c_str());
     return 0;
+}
+
+// A run of small files through one batch call.  What a loop of do_file over
+// them leaves behind and prints, message for message.
+struct BatchFile {
+    std::string path, out, msg; // msg: what went wrong, if anything
+    struct stat st;
+    size_t off = 0, len = 0;    // input in the run's slab
+};
+
+std::string error_text(int rc, snapmi_error e)
+{
+    char text[256];
+    e.kind = rc;
+    snapmi_error_string(&e, text, sizeof text);
+    return text;
+}
+
+int run_batch(const Options &opt, snapmi_ctx *&ctx,
+              std::vector<BatchFile> &files)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    // read what can be read; a file that cannot keeps its message
+    size_t total = 0;
+    for (BatchFile &f : files) {
+        std::string why;
+        if (!out_name(opt, f.path, f.out, why)) {
+            f.msg = why;
+            continue;
+        }
+        f.off = total;
+        f.len = (size_t)f.st.st_size;
+        total += (f.len + 63) & ~(size_t)63;
+    }
+    Buf in, out;
+    in.reserve(total + 64);
+    std::vector<size_t> live; // indices of the files in the call
+    for (size_t i = 0; i < files.size(); i++) {
+        BatchFile &f = files[i];
+        if (!f.msg.empty())
+            continue;
+        FILE *src = fopen(f.path.c_str(), "rb");
+        if (!src) {
+            f.msg = f.path + ": " + strerror(errno);
+            continue;
+        }
+        f.len = read_full(src, in.p + f.off, f.len); // (it may have shrunk)
+        fclose(src);
+        live.push_back(i);
+    }
+    const size_t n = live.size();
+    if (n && !ctx && snapmi_ctx_create(0, nullptr, &ctx) != SNAPMI_OK) {
+        ctx = nullptr;
+        for (size_t i : live)
+            files[i].msg = "szip: " + files[i].path + ": no usable GPU";
+        live.clear();
+    }
+    std::vector<const void *> in_ptrs(n);
+    std::vector<void *> out_ptrs(n);
+    std::vector<size_t> in_lens(n), caps(n), lens(n);
+    std::vector<snapmi_error> errs(n);
+    int rc = SNAPMI_OK;
+    if (!live.empty()) {
+        for (size_t k = 0; k < n; k++) {
+            in_ptrs[k] = in.p + files[live[k]].off;
+            in_lens[k] = files[live[k]].len;
+        }
+        if (opt.decompress) // sizes first: the lengths-only form
+            rc = snapmi_frame_decompress_batch_host(
+                ctx, in_ptrs.data(), in_lens.data(), nullptr, nullptr,
+                caps.data(), nullptr, n);
+        else
+            for (size_t k = 0; k < n; k++)
+                caps[k] = snapmi_frame_max_len(in_lens[k]);
+        size_t room = 0;
+        for (size_t k = 0; k < n; k++)
+            room += (caps[k] + 63) & ~(size_t)63;
+        out.reserve(room + 64);
+        for (size_t k = 0, at = 0; k < n; k++) {
+            out_ptrs[k] = out.p + at;
+            at += (caps[k] + 63) & ~(size_t)63;
+        }
+        if (rc == SNAPMI_OK)
+            rc = (opt.decompress ? snapmi_frame_decompress_batch_host
+                                 : snapmi_frame_compress_batch_host)(
+                ctx, in_ptrs.data(), in_lens.data(), out_ptrs.data(),
+                caps.data(), lens.data(), errs.data(), n);
+    }
+    const double secs = std::chrono::duration<double>(
+                            std::chrono::steady_clock::now() - t0).count();
+    for (size_t k = 0; k < live.size(); k++) {
+        BatchFile &f = files[live[k]];
+        if (rc != SNAPMI_OK) {
+            f.msg = "szip: " + f.path + ": " + snapmi_last_error(ctx);
+            continue;
+        }
+        if (errs[k].kind != SNAPMI_OK) {
+            f.msg = "szip: " + f.path + ": " +
+                    error_text(errs[k].kind, errs[k]);
+            continue;
+        }
+        FILE *dst = fopen(f.out.c_str(), "wb");
+        if (!dst) {
+            f.msg = f.out + ": " + strerror(errno);
+            continue;
+        }
+        const bool ok = fwrite(out_ptrs[k], 1, lens[k], dst) == lens[k];
+        if (fclose(dst) != 0 || !ok) {
+            f.msg = "szip: " + f.path + ": write failed";
+            unlink(f.out.c_str());
+            continue;
+        }
+        struct utimbuf tb = {f.st.st_atime, f.st.st_mtime};
+        utime(f.out.c_str(), &tb);
+        if (!opt.keep)
+            unlink(f.path.c_str());
+    }
+    int failed = 0;
+    for (size_t i = 0, k = 0; i < files.size(); i++) {
+        const BatchFile &f = files[i];
+        const bool was_live = k < live.size() && live[k] == i;
+        if (opt.verbose && was_live) {
+            // (the run's time, shared out by size)
+            const double u = (double)(opt.decompress ? lens[k] : f.len);
+            double all = 0;
+            for (size_t j = 0; j < live.size(); j++)
+                all += (double)(opt.decompress ? lens[j] : in_lens[j]);
+            fprintf(stderr,
+                    "szip: %s: %.3f s, %.2f GiB/s (uncompressed bytes)\n",
+                    f.path.c_str(), all > 0 ? secs * u / all : 0.0,
+                    secs > 0 ? all / secs / (1 << 30) : 0.0);
+        }
+        k += was_live;
+        if (!f.msg.empty()) {
+            fprintf(stderr, "%s\n", f.msg.c_str());
+            failed = 1;
+        }
+    }
+    files.clear();
+    return failed;
 }
 
 } // namespace
@@ -497,7 +661,35 @@ int main(int argc, char **argv)
     if (paths.empty())
         return run_stream(opt, stdin, stdout, "<stdin>");
     int rc = 0;
-    for (const auto &p : paths)
-        rc |= do_file(opt, p);
+    // runs of consecutive small files go through one batch call; everything
+    // else (and every file when there is only one) through the pipeline
+    snapmi_ctx *ctx = nullptr;
+    std::vector<BatchFile> run;
+    size_t run_bytes = 0;
+    for (const auto &p : paths) {
+        BatchFile f;
+        f.path = p;
+        const bool small = paths.size() > 1 && !opt.raw &&
+                           stat(p.c_str(), &f.st) == 0 &&
+                           S_ISREG(f.st.st_mode) &&
+                           (size_t)f.st.st_size < kBatchBelow;
+        if (small && run_bytes + (size_t)f.st.st_size <= kBatchBytes) {
+            run_bytes += (size_t)f.st.st_size;
+            run.push_back(f);
+            continue;
+        }
+        if (!run.empty())
+            rc |= run_batch(opt, ctx, run);
+        run_bytes = 0;
+        if (small) {
+            run_bytes = (size_t)f.st.st_size;
+            run.push_back(f);
+        } else
+            rc |= do_file(opt, p);
+    }
+    if (!run.empty())
+        rc |= run_batch(opt, ctx, run);
+    if (ctx)
+        snapmi_ctx_destroy(ctx);
     return rc;
 }

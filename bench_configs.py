@@ -1113,6 +1113,126 @@ def frames_batch(args, ctx, dev):
     return res
 
 
+def raw_index(args, ctx, dev):
+    """The block index of raw streams (snapmi_compress_batch_indexed /
+    snapmi_decompress_batch_indexed) on frames_batch's two device-resident
+    sets and on 256 streams of 1 MiB of the same text: decode with the index
+    compress wrote against snapmi_decompress_batch with batch_long_streams 1
+    and 0, compress with and without the index - all in this process on one
+    context, five alternating repeats of --steps calls each (medians, and the
+    spread max - min over the repeats).  Writes profiles/raw_index.json."""
+    import random
+    import statistics
+    import oracle_lib as O
+    from rust_snappy_amd import batch, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+
+    def piece(n):
+        o = rng.randrange(len(text) - n)
+        return text[o:o + n]
+    sets = {"text_4096x16k": [piece(16384) for _ in range(4096)],
+            "mixed_512_100b_1m": [piece(int(100 * (10486 ** rng.random())))
+                                  for _ in range(512)],
+            "text_256x1m": [piece(1 << 20) for _ in range(256)]}
+    repeats = 5
+    res = {"config": "raw_index: decode with the block index vs "
+                     "snapmi_decompress_batch (batch_long_streams 1 / 0), "
+                     "compress with / without the index",
+           "steps": args.steps, "repeats": repeats}
+    for key, datas in sets.items():
+        n = len(datas)
+        nbytes = sum(len(d) for d in datas)
+        src = batch.StreamBatch.from_bytes(datas, dev)
+        out = batch.StreamBatch.empty(
+            [raw.max_compress_len(len(d)) for d in datas], dev)
+        clens = torch.zeros(n, dtype=torch.int64, device=dev)
+        entries = raw.block_index_entries([len(d) for d in datas])
+        first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        index = torch.zeros(entries, dtype=torch.int64, device=dev)
+        back = batch.StreamBatch.empty([len(d) for d in datas], dev)
+        blens = torch.zeros(n, dtype=torch.int64, device=dev)
+        berrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+
+        def enc_plain():
+            raw.compress_batch(ctx, src.d_ptrs, src.d_lens, out.d_ptrs,
+                               out.d_lens, clens, None,
+                               host_in_lens=src.h_lens)
+
+        def enc_indexed():
+            raw.compress_batch(ctx, src.d_ptrs, src.d_lens, out.d_ptrs,
+                               out.d_lens, clens, None,
+                               host_in_lens=src.h_lens, index_first=first,
+                               index=index, index_cap=entries)
+
+        def dec_indexed():
+            raw.decompress_batch(ctx, out.d_ptrs, clens, back.d_ptrs,
+                                 back.d_lens, blens, berrs,
+                                 index_first=first, index=index,
+                                 index_entries=entries)
+
+        def dec_plain(long_streams):
+            def run():
+                raw.decompress_batch(ctx, out.d_ptrs, clens, back.d_ptrs,
+                                     back.d_lens, blens, berrs)
+
+            def timed():
+                ctx.set_option("batch_long_streams", long_streams)
+                try:
+                    return time_it(run, args.steps, ctx)
+                finally:
+                    ctx.set_option("batch_long_streams", 1)
+            return timed
+        enc_indexed()
+        ctx.synchronize()
+        for i in (0, n // 2, n - 1):
+            assert out.stream_bytes(i, int(clens[i])) == O.compress(datas[i])
+        blens.zero_()
+        back.data.zero_()
+        dec_indexed()
+        pieced = ctx.info("index_streams_pieced")
+        fallback = ctx.info("index_streams_fallback")
+        assert all(e[0] == 0 for e in batch.read_errors(berrs))
+        for i in (0, n // 2, n - 1):
+            assert back.stream_bytes(i, int(blens[i])) == datas[i]
+        timers = {"dec_indexed": lambda: time_it(dec_indexed, args.steps, ctx),
+                  "dec_long_streams_1": dec_plain(1),
+                  "dec_long_streams_0": dec_plain(0),
+                  "enc_indexed": lambda: time_it(enc_indexed, args.steps, ctx),
+                  "enc_plain": lambda: time_it(enc_plain, args.steps, ctx)}
+        t = {k: [] for k in timers}
+        for _ in range(repeats):
+            for k, fn in timers.items():
+                t[k].append(fn() * 1e3)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        spread = {k: max(v) - min(v) for k, v in t.items()}
+
+        def not_slower(a, b):
+            return med[a] <= med[b] + max(spread[a], spread[b])
+        res[key] = {
+            "streams": n, "bytes": nbytes, "index_entries": entries,
+            "index_streams_pieced": pieced,
+            "index_streams_fallback": fallback,
+            "ms_median": {k: round(v, 4) for k, v in med.items()},
+            "ms_spread": {k: round(v, 4) for k, v in spread.items()},
+            "ms_repeats": {k: [round(x, 4) for x in v] for k, v in t.items()},
+            "dec_indexed_gibs": round(nbytes / GIB / (med["dec_indexed"] / 1e3),
+                                      1),
+            "dec_indexed_over_long_streams_1": round(
+                med["dec_indexed"] / med["dec_long_streams_1"], 3),
+            "dec_indexed_over_long_streams_0": round(
+                med["dec_indexed"] / med["dec_long_streams_0"], 3),
+            "enc_indexed_over_plain": round(
+                med["enc_indexed"] / med["enc_plain"], 3),
+            "dec_indexed_not_slower_than_both_within_spread":
+                not_slower("dec_indexed", "dec_long_streams_1")
+                and not_slower("dec_indexed", "dec_long_streams_0")}
+    (ROOT / "profiles" / "raw_index.json").write_text(json.dumps(res) + "\n")
+    return res
+
+
 class HostArena:
     """buffers of the given sizes, 64 bytes apart at least, in one
     pageable array or one snapmi_host_alloc allocation"""
@@ -1529,7 +1649,7 @@ def main():
              "adapters": adapters, "stream": stream, "cfg4": cfg4,
              "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
              "frames_batch": frames_batch, "host_batch": host_batch,
-             "frames_host_batch": frames_host_batch}
+             "frames_host_batch": frames_host_batch, "raw_index": raw_index}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1550,11 +1670,13 @@ def main():
                      ("stream", stream), ("cfg4", cfg4),
                      ("frames_batch", frames_batch),
                      ("host_batch", host_batch),
-                     ("frames_host_batch", frames_host_batch)):
+                     ("frames_host_batch", frames_host_batch),
+                     ("raw_index", raw_index)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
-                                                         "frames_host_batch")):
+                                                         "frames_host_batch",
+                                                         "raw_index")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

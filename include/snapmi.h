@@ -315,6 +315,12 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *                           written, each stream rounded to 16 bytes)
  *   "host_batch_listed_slices"  slices of it that were decoded from the host's
  *                           chunk list (snapmi_frame_decompress_batch_host)
+ *   "index_streams_pieced"  streams of the last
+ *                           snapmi_decompress_batch_indexed whose index passed
+ *                           and that were delivered by their pieces, and
+ *   "index_streams_fallback"  streams of it whose index passed, whose pieces
+ *                           did not come out whole and that the batch's own
+ *                           launch decoded instead (both wait for the call)
  * SNAPMI_E_ARGUMENT for a name that is not in this list. */
 SNAPMI_API int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name,
                                    int64_t *value);
@@ -446,6 +452,73 @@ SNAPMI_API int snapmi_decompress_batch(snapmi_ctx *ctx, const void *const *d_in_
                             void *const *d_out_ptrs,
                             const uint64_t *d_out_caps, uint64_t *d_out_lens,
                             snapmi_error *d_errs, size_t n);
+
+/*
+ * The block index of raw streams: where, inside a compressed stream, the
+ * elements of every 64 KiB block of its input begin.  The compressor knows
+ * it for free and the decoder, given it, decodes a long stream on as many
+ * wavefronts as it has blocks without looking for the boundaries first.
+ *
+ * Layout.  Stream i owns d_index[d_index_first[i], d_index_first[i + 1]):
+ * blocks_i + 1 entries, blocks_i = ceil(len_i / 65536).  Entry j is the byte
+ * offset, inside stream i's compressed bytes, of the first element of block
+ * j: entry 0 is the length of the varint header, the last entry equals
+ * d_out_lens[i].  An empty input has the one entry {1}; a stream that fails
+ * (BufferTooSmall) has all its entries 0.
+ *
+ * snapmi_block_index_entries: entries the index of n streams takes, the sum
+ * of ceil(len_i / 65536) + 1.  Host code.
+ *
+ * snapmi_compress_batch_indexed: snapmi_compress_batch - the same bytes,
+ * lengths and errors, enqueue-only with the same h_in_lens == NULL exception -
+ * that also writes d_index_first [n + 1] and d_index.  index_cap: entries
+ * d_index has room for; fewer than snapmi_block_index_entries(h_in_lens, n)
+ * is SNAPMI_E_ARGUMENT, and nothing is enqueued.
+ *
+ * snapmi_decompress_batch_indexed: for every i, d_out_lens[i], d_errs[i]
+ * (variant and fields) and the bytes d_out_ptrs[i][0, d_out_lens[i]) are
+ * those of snapmi_decompress_batch WHATEVER the index holds: it is a hint and
+ * decides only how fast the result comes.  index_entries is the host's copy
+ * of d_index_first[n] (what snapmi_block_index_entries gave) and sizes every
+ * launch; entries at or behind it are never read.  A stream is indexed when
+ * it owns at least three entries (two blocks) inside the index, entry 0 is
+ * the length of its varint header, the entries strictly increase, the last
+ * one is its compressed length, their count is ceil(dlen / 65536) + 1 for the
+ * length dlen its header announces, and dlen <= d_out_caps[i].  Piece k of
+ * such a stream - input [entry k, entry k + 1) into output [k * 65536,
+ * min((k + 1) * 65536, dlen)) - is decoded like an independent stream that
+ * must fill exactly its room: no piece writes outside it, so nothing is
+ * written outside [d_out_ptrs[i], + d_out_caps[i]) however hostile the index.
+ * A stream all of whose pieces report OK and filled their room is done; any
+ * other indexed stream (a copy that reaches across a boundary, an entry in
+ * the middle of an element, a corrupt byte) and every stream that is not
+ * indexed is decoded whole by the batch's ordinary launch behind the pieces,
+ * which names the reference's error with whole-stream fields.
+ * The streams that are not indexed are decoded beside the pieces, in the
+ * same launch.  The call only enqueues - no look at the batch on the host
+ * ("batch_long_streams" is not consulted), no wait, so it can be captured
+ * into a hipGraph once the context's scratch has grown to the batch's size
+ * (a buffer that grows waits for the stream, as in every call of this
+ * section; all of them are reserved before the first launch) - and has no
+ * limit of 16 384 streams or 4 096 long ones; n + index_entries stays below
+ * 2^31 (SNAPMI_E_ARGUMENT).  n == 0 enqueues nothing; index_entries < 3 is
+ * snapmi_decompress_batch's plain launch.
+ * Info "index_streams_pieced" / "index_streams_fallback" describe the last
+ * call.
+ */
+SNAPMI_API uint64_t snapmi_block_index_entries(const uint64_t *h_in_lens,
+                                               size_t n);
+SNAPMI_API int snapmi_compress_batch_indexed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    const uint64_t *h_in_lens, void *const *d_out_ptrs,
+    const uint64_t *d_out_caps, uint64_t *d_out_lens, snapmi_error *d_errs,
+    size_t n, uint64_t *d_index_first /* out, [n+1] */,
+    uint64_t *d_index /* out */, uint64_t index_cap);
+SNAPMI_API int snapmi_decompress_batch_indexed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    void *const *d_out_ptrs, const uint64_t *d_out_caps, uint64_t *d_out_lens,
+    snapmi_error *d_errs, size_t n, const uint64_t *d_index_first /* [n+1] */,
+    const uint64_t *d_index, uint64_t index_entries);
 
 /*
  * ONE long raw stream, device resident, decoded by many wavefronts.

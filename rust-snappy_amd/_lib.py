@@ -72,6 +72,11 @@ SYMBOLS = [
      [_P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_compress_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
     ("snapmi_decompress_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _SZ]),
+    ("snapmi_block_index_entries", C.c_uint64, [_P, _SZ]),
+    ("snapmi_compress_batch_indexed", C.c_int,
+     [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, C.c_uint64]),
+    ("snapmi_decompress_batch_indexed", C.c_int,
+     [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, C.c_uint64]),
     ("snapmi_decompress_len_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
     ("snapmi_decompress_stream", C.c_int,
      [_P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),

@@ -70,13 +70,30 @@ def read_errors(errs):
             for r in rec]
 
 
-def compress(ctx, src: StreamBatch, check_caps=True):
-    """Compress every stream of `src`; returns (dst batch, out_lens, errs)."""
+def compress(ctx, src: StreamBatch, check_caps=True, want_index=False):
+    """Compress every stream of `src`; returns (dst batch, out_lens, errs) -
+    or, with want_index, (dst batch, index_first, index): the streams' block
+    index as int64 device tensors (snapmi_compress_batch_indexed; dst.lens
+    are then the compressed lengths).  The per-stream errors are not
+    returned in that form: a stream that failed (BufferTooSmall) has
+    dst.lens[i] == 0 and all its index entries 0; call without want_index to
+    see why."""
     caps = [raw.max_compress_len(int(n)) or 32 for n in src.lens]
     dst = StreamBatch.empty(caps, src.data.device)
     dev = src.data.device
     out_lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
     errs = torch.zeros(32 * src.n, dtype=torch.uint8, device=dev)
+    if want_index:
+        entries = raw.block_index_entries(src.lens)
+        index_first = torch.zeros(src.n + 1, dtype=torch.int64, device=dev)
+        index = torch.zeros(entries, dtype=torch.int64, device=dev)
+        raw.compress_batch(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs,
+                           dst.d_lens if check_caps else None, out_lens, errs,
+                           host_in_lens=src.h_lens, index_first=index_first,
+                           index=index, index_cap=entries)
+        ctx.synchronize()
+        done = StreamBatch(dst.data, dst.offsets, out_lens.cpu().numpy())
+        return done, index_first, index
     raw.compress_batch(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs,
                        dst.d_lens if check_caps else None, out_lens, errs,
                        host_in_lens=src.h_lens)
@@ -84,8 +101,10 @@ def compress(ctx, src: StreamBatch, check_caps=True):
     return dst, out_lens.cpu().numpy(), read_errors(errs)
 
 
-def decompress(ctx, src: StreamBatch, caps=None):
-    """Decompress every stream; caps default to the header lengths."""
+def decompress(ctx, src: StreamBatch, caps=None, index=None):
+    """Decompress every stream; caps default to the header lengths.  index:
+    the (index_first, index) pair compress(want_index=True) returned - the
+    same results through snapmi_decompress_batch_indexed."""
     dev = src.data.device
     if caps is None:
         lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
@@ -95,7 +114,14 @@ def decompress(ctx, src: StreamBatch, caps=None):
     dst = StreamBatch.empty(caps, dev)
     out_lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
     errs = torch.zeros(32 * src.n, dtype=torch.uint8, device=dev)
-    raw.decompress_batch(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs, dst.d_lens,
-                         out_lens, errs)
+    if index is not None:
+        index_first, index_tensor = index
+        raw.decompress_batch(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs,
+                             dst.d_lens, out_lens, errs,
+                             index_first=index_first, index=index_tensor,
+                             index_entries=index_tensor.numel())
+    else:
+        raw.decompress_batch(ctx, src.d_ptrs, src.d_lens, dst.d_ptrs,
+                             dst.d_lens, out_lens, errs)
     ctx.synchronize()
     return dst, out_lens.cpu().numpy(), read_errors(errs)

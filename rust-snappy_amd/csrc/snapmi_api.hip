@@ -290,7 +290,8 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
                       &ctx->ntok, &ctx->sched,
                       &ctx->lane_epochs, &ctx->sd_tables, &ctx->sd_desc,
                       &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs,
-                      &ctx->bl_order})
+                      &ctx->bl_order, &ctx->ix_modes, &ctx->ix_desc,
+                      &ctx->ix_gate})
         if (b->p)
             (void)hipFree(b->p);
     for (auto &ev : ctx->ev)
@@ -706,18 +707,22 @@ extern "C" {
 // ----------------------------------------------------------------------
 // batched device-resident API
 // ----------------------------------------------------------------------
-int snapmi_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
+// snapmi_compress_batch, and with `indexed` snapmi_compress_batch_indexed:
+// the same launches, and behind them the kernels that write the block index
+static int compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                           const uint64_t *d_in_lens,
                           const uint64_t *h_in_lens, void *const *d_out_ptrs,
                           const uint64_t *d_out_caps, uint64_t *d_out_lens,
-                          snapmi_error *d_errs, size_t n)
+                          snapmi_error *d_errs, size_t n, bool indexed,
+                          uint64_t *d_index_first, uint64_t *d_index,
+                          uint64_t index_cap)
 {
     if (!ctx)
         return SNAPMI_E_ARGUMENT;
     if (n == 0)
         return SNAPMI_OK;
     if (!d_in_ptrs || !d_in_lens || !d_out_ptrs || !d_out_lens ||
-        n > 0x7FFFFFFFu)
+        n > 0x7FFFFFFFu || (indexed && (!d_index_first || !d_index)))
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "compress_batch: bad args");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -754,9 +759,54 @@ int snapmi_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         const uint64_t last = len - (nb - 1) * kMaxBlock;
         cnt8 += last <= 8192;
     }
+    uint64_t entries = 0;
+    if (indexed) {
+        entries = snapmi_block_index_entries(h_in_lens, n);
+        if (entries > index_cap)
+            return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                            "compress_batch_indexed: the index takes %llu "
+                            "entries, index_cap is %llu",
+                            (unsigned long long)entries,
+                            (unsigned long long)index_cap);
+    }
     return launch_compress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
                            d_out_lens, d_errs, n, blocks, slots, classes,
-                           cnt8, block_bytes);
+                           cnt8, block_bytes, indexed ? d_index_first : nullptr,
+                           d_index, entries);
+}
+
+uint64_t snapmi_block_index_entries(const uint64_t *h_in_lens, size_t n)
+{
+    uint64_t entries = 0;
+    for (size_t i = 0; h_in_lens && i < n; i++)
+        entries += snapmi::bi_entries(h_in_lens[i]);
+    return entries;
+}
+
+int snapmi_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
+                          const uint64_t *d_in_lens,
+                          const uint64_t *h_in_lens, void *const *d_out_ptrs,
+                          const uint64_t *d_out_caps, uint64_t *d_out_lens,
+                          snapmi_error *d_errs, size_t n)
+{
+    return compress_batch(ctx, d_in_ptrs, d_in_lens, h_in_lens, d_out_ptrs,
+                          d_out_caps, d_out_lens, d_errs, n, false, nullptr,
+                          nullptr, 0);
+}
+
+int snapmi_compress_batch_indexed(snapmi_ctx *ctx,
+                                  const void *const *d_in_ptrs,
+                                  const uint64_t *d_in_lens,
+                                  const uint64_t *h_in_lens,
+                                  void *const *d_out_ptrs,
+                                  const uint64_t *d_out_caps,
+                                  uint64_t *d_out_lens, snapmi_error *d_errs,
+                                  size_t n, uint64_t *d_index_first,
+                                  uint64_t *d_index, uint64_t index_cap)
+{
+    return compress_batch(ctx, d_in_ptrs, d_in_lens, h_in_lens, d_out_ptrs,
+                          d_out_caps, d_out_lens, d_errs, n, true,
+                          d_index_first, d_index, index_cap);
 }
 
 int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks, uint32_t flags)
@@ -784,7 +834,8 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
               &ctx->tokens, &ctx->tok_pages, &ctx->tok_stage, &ctx->ntok,
               &ctx->sched,
               &ctx->lane_epochs, &ctx->sd_tables, &ctx->sd_desc,
-              &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs, &ctx->bl_order})
+              &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs, &ctx->bl_order,
+              &ctx->ix_modes, &ctx->ix_desc, &ctx->ix_gate})
             sum += b->cap;
         *value = (int64_t)sum;
     } else if (strcmp(name, "token_scratch_bytes") == 0) {
@@ -801,6 +852,17 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const volatile uint32_t *t = ctx->h_tokstat;
         *value = !t ? 0 : name[6] == 'p' ? t[0] : t[1];
+    } else if (strcmp(name, "index_streams_pieced") == 0 ||
+               strcmp(name, "index_streams_fallback") == 0) {
+        // of the last snapmi_decompress_batch_indexed: wait for it
+        unsigned long long w[3] = {0, 0, 0};
+        if (ctx->ix_stats_live && ctx->ix_gate.p) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(w, ctx->ix_gate.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        *value = (int64_t)(name[14] == 'p' ? w[1] : w[2]);
     } else if (strcmp(name, "host_batch_slices") == 0) {
         *value = (int64_t)ctx->hb_slices;
     } else if (strcmp(name, "host_batch_h2d_bytes") == 0) {
@@ -1287,7 +1349,8 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                     const uint64_t *d_out_caps, uint64_t *d_out_lens,
                     snapmi_error *d_errs, size_t n, uint64_t blocks,
                     uint64_t slots, uint32_t small_classes, uint64_t cnt8,
-                    uint64_t block_bytes)
+                    uint64_t block_bytes, uint64_t *d_index_first,
+                    uint64_t *d_index, uint64_t index_entries)
 {
     if (blocks > 0x7FFFFFFFu)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
@@ -1590,6 +1653,28 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         hipLaunchKernelGGL(k_compact, dim3((uint32_t)blocks), dim3(256), 0,
                            s, a);
     }
+    // the block index: first[], then a thread per entry (plan_part is free
+    // again: every scan of the batch is done)
+    if (d_index_first) {
+        uint64_t *part = (uint64_t *)ctx->plan_part.p;
+        if (n > kPlanOneWg) {
+            const uint32_t parts = (uint32_t)((n + 1023) / 1024);
+            hipLaunchKernelGGL(k_index_first_a, dim3(parts), dim3(1024), 0, s,
+                               d_in_lens, (uint32_t)n, d_index_first, part);
+            hipLaunchKernelGGL(k_index_first_b, dim3(1), dim3(1024), 0, s,
+                               (uint32_t)n, d_index_first, part, parts);
+            hipLaunchKernelGGL(k_index_first_c, dim3(parts), dim3(1024), 0, s,
+                               (uint32_t)n, d_index_first, part);
+        } else {
+            hipLaunchKernelGGL(k_index_first, dim3(1), dim3(1024), 0, s,
+                               d_in_lens, (uint32_t)n, d_index_first);
+        }
+        if (index_entries)
+            hipLaunchKernelGGL(k_block_index,
+                               dim3((uint32_t)((index_entries + 255) / 256)),
+                               dim3(256), 0, s, a, d_index_first, d_index,
+                               index_entries);
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->ev[3], s));
     HIP_TRY(ctx, hipGetLastError());
     ctx->timing_valid = true;
@@ -1606,7 +1691,7 @@ int launch_decompress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                       snapmi_error *d_errs, const uint8_t *d_modes, size_t n,
                       const unsigned long long *d_gate,
                       unsigned long long gate_value, hipStream_t side,
-                      DevBuf *side_order)
+                      DevBuf *side_order, bool wide_only)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf &order = side_order ? *side_order : ctx->order;
@@ -1679,11 +1764,15 @@ int launch_decompress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         // the streams of fewer than 256 compressed bytes, one per lane (how
         // many there are only the device knows: workgroups without any leave
         // at once, in both launches)
-        hipLaunchKernelGGL(k_decompress_tiny,
-                           dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, s, a);
+        if (!wide_only)
+            hipLaunchKernelGGL(k_decompress_tiny,
+                               dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, s,
+                               a);
         // ... and those of under 512 bytes in and out, 32 per wavefront
-        hipLaunchKernelGGL(k_decompress_small,
-                           dim3((uint32_t)((n + 31) / 32)), dim3(64), 0, s, a);
+        if (!wide_only)
+            hipLaunchKernelGGL(k_decompress_small,
+                               dim3((uint32_t)((n + 31) / 32)), dim3(64), 0, s,
+                               a);
     }
     HIP_TRY(ctx, hipGetLastError());
     if (side)
@@ -2004,6 +2093,96 @@ int snapmi_decompress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     }
     return launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
                              d_out_lens, d_errs, nullptr, n);
+}
+
+// The batch with the block index its compressor wrote
+// (snapmi_blockindex.hpp; the kernels: k_index_* in snapmi_decompress.hip).
+// Enqueue-only: index_entries, the host's copy of first[n], sizes every
+// launch, and what the device finds out - whether any stream is indexed,
+// which streams' pieces came out whole - reaches the launches behind it
+// through device memory (the gate, the modes of the batch's own launch).
+int snapmi_decompress_batch_indexed(snapmi_ctx *ctx,
+                                    const void *const *d_in_ptrs,
+                                    const uint64_t *d_in_lens,
+                                    void *const *d_out_ptrs,
+                                    const uint64_t *d_out_caps,
+                                    uint64_t *d_out_lens,
+                                    snapmi_error *d_errs, size_t n,
+                                    const uint64_t *d_index_first,
+                                    const uint64_t *d_index,
+                                    uint64_t index_entries)
+{
+    if (!ctx)
+        return SNAPMI_E_ARGUMENT;
+    if (n == 0)
+        return SNAPMI_OK;
+    if (!d_in_ptrs || !d_in_lens || !d_out_ptrs || !d_out_caps ||
+        !d_out_lens || (uint64_t)n + index_entries > 0x7FFFFFFFu ||
+        (index_entries && (!d_index_first || !d_index)))
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "decompress_batch_indexed: bad args");
+    ctx->ix_stats_live = false;
+    // (an indexed stream owns three entries or more)
+    if (index_entries < 3)
+        return launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs,
+                                 d_out_caps, d_out_lens, d_errs, nullptr, n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t E = (size_t)index_entries, T = n + E;
+    int rc;
+    const bool fresh_gate = !ctx->ix_gate.p;
+    // (everything the call's launches need, before the first of them: a
+    // buffer that grows waits for the stream)
+    if ((rc = reserve(ctx, ctx->ix_modes, n)) ||
+        (rc = reserve(ctx, ctx->ix_desc,
+                      T * (40 + sizeof(snapmi_error) + 1) + E * 4 + 64)) ||
+        (rc = reserve(ctx, ctx->ix_gate, 64)) ||
+        (rc = reserve(ctx, ctx->order, (T + 72) * sizeof(uint32_t))))
+        return rc;
+    if (fresh_gate)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ix_gate.p, 0, 64, s));
+    uint8_t *d = (uint8_t *)ctx->ix_desc.p;
+    IndexArgs x;
+    x.in_ptrs = d_in_ptrs;
+    x.in_lens = d_in_lens;
+    x.out_ptrs = d_out_ptrs;
+    x.out_caps = d_out_caps;
+    x.out_lens = d_out_lens;
+    x.errs = d_errs;
+    x.first = d_index_first;
+    x.index = d_index;
+    x.entries = index_entries;
+    x.n = (uint32_t)n;
+    x.modes = (uint8_t *)ctx->ix_modes.p;
+    x.c_in = (const void **)d;
+    x.c_inlen = (uint64_t *)(d + T * 8);
+    x.c_out = (void **)(d + T * 16);
+    x.c_cap = (uint64_t *)(d + T * 24);
+    x.c_outlen = (uint64_t *)(d + T * 32);
+    x.c_err = (snapmi_error *)(d + T * 40);
+    x.c_owner = (uint32_t *)(d + T * (40 + sizeof(snapmi_error)));
+    x.c_mode = d + T * (40 + sizeof(snapmi_error)) + E * 4;
+    x.gate = (unsigned long long *)ctx->ix_gate.p;
+    x.seq = ++ctx->ix_seq;
+    hipLaunchKernelGGL(k_index_plan, dim3((uint32_t)((n + 255) / 256)),
+                       dim3(256), 0, s, x);
+    LAUNCH_CHECK(k_index_plan);
+    ctx->ix_stats_live = true;
+    hipLaunchKernelGGL(k_index_pieces, dim3((uint32_t)((E + 255) / 256)),
+                       dim3(256), 0, s, x);
+    LAUNCH_CHECK(k_index_pieces);
+    // the batch: whole streams and pieces in one launch
+    if ((rc = launch_decompress(ctx, x.c_in, x.c_inlen, x.c_out, x.c_cap,
+                                x.c_outlen, x.c_err, x.c_mode, T)))
+        return rc;
+    hipLaunchKernelGGL(k_index_finish, dim3((uint32_t)((n + 3) / 4)),
+                       dim3(256), 0, s, x);
+    LAUNCH_CHECK(k_index_finish);
+    // the indexed streams that were handed back, if any (they announce more
+    // than a block of output: none is of the lane-per-stream classes)
+    return launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
+                             d_out_lens, d_errs, x.modes, n, x.gate + 3, x.seq,
+                             nullptr, nullptr, /*wide_only=*/true);
 }
 
 // One stream as a batch of one, enqueue-only (the scalar entry points wait

@@ -1,0 +1,129 @@
+// snapmi_blockindex.hpp -- the block index of raw streams
+// (snapmi_compress_batch_indexed / snapmi_decompress_batch_indexed), in plain
+// C++ that the host code, the kernels and a CPU test
+// (tests/blockindex_host.cpp) compile alike:
+//
+//   bi_entries        entries a stream of `len` input bytes owns
+//   bi_stream_indexed whether a compressed stream and the entries it was
+//                     given pass the rule (a hint is never trusted: anything
+//                     else is an ordinary stream of the batch launch)
+//   bi_piece          input and output range of piece k of an indexed stream
+//
+// Layout: stream i owns index[first[i], first[i + 1]): blocks + 1 entries,
+// blocks = ceil(len / 64 KiB); entry j is the offset, inside the stream's
+// compressed bytes, of the first element of block j - entry 0 the length of
+// the varint header, the last entry the compressed length.
+//
+// No HIP types, no allocation.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define SNAPMI_BI_HD __host__ __device__
+#else
+#define SNAPMI_BI_HD
+#endif
+
+namespace snapmi {
+
+// input bytes per block of the encoders (kMaxBlock), output bytes per piece
+// of the decoder (kStreamChunk)
+constexpr uint64_t kBiBlock = 65536;
+
+SNAPMI_BI_HD inline uint64_t bi_blocks(uint64_t len)
+{
+    return len / kBiBlock + (len % kBiBlock ? 1 : 0);
+}
+
+SNAPMI_BI_HD inline uint64_t bi_entries(uint64_t len)
+{
+    return bi_blocks(len) + 1;
+}
+
+// The varint at the head of in[0, in_len): its bytes (0: none that the
+// decoders accept - truncated, more than 64 bits, or a length above
+// 2^32 - 1) and its value.
+SNAPMI_BI_HD inline uint32_t bi_header(const uint8_t *in, uint64_t in_len,
+                                       uint64_t *dlen)
+{
+    uint64_t v = 0;
+    for (uint32_t k = 0; k < 10 && k < in_len; k++) {
+        const uint8_t b = in[k];
+        v |= (uint64_t)(b & 0x7F) << (7 * k);
+        if (b < 0x80) {
+            if (v > 0xFFFFFFFFull)
+                return 0;
+            *dlen = v;
+            return k + 1;
+        }
+    }
+    return 0;
+}
+
+// Is the stream in[0, in_len) with room for `cap` bytes of output, which owns
+// index[first, next) of an index of index_entries entries, indexed?  All of:
+// at least 3 entries (two blocks) inside the index; entry 0 is the length of
+// the varint header; the entries strictly increase; the last one is in_len;
+// their count is ceil(dlen / 64 KiB) + 1; dlen <= cap.
+SNAPMI_BI_HD inline bool bi_stream_indexed(const uint8_t *in, uint64_t in_len,
+                                           uint64_t cap,
+                                           const uint64_t *index,
+                                           uint64_t first, uint64_t next,
+                                           uint64_t index_entries)
+{
+    if (next > index_entries || first > next || next - first < 3)
+        return false;
+    const uint64_t count = next - first;
+    uint64_t dlen = 0;
+    const uint32_t hdr = bi_header(in, in_len, &dlen);
+    if (hdr == 0 || dlen > cap || count != bi_entries(dlen))
+        return false;
+    const uint64_t *e = index + first;
+    if (e[0] != hdr || e[count - 1] != in_len)
+        return false;
+    for (uint64_t j = 1; j < count; j++)
+        if (e[j] <= e[j - 1])
+            return false;
+    return true;
+}
+
+// Piece k (k < entries - 1) of an indexed stream of dlen output bytes whose
+// entries are e[]: input [in_off, in_off + in_len) into output
+// [out_off, out_off + out_len).
+struct BiPiece {
+    uint64_t in_off, in_len, out_off, out_len;
+};
+
+SNAPMI_BI_HD inline BiPiece bi_piece(const uint64_t *e, uint64_t dlen,
+                                     uint64_t k)
+{
+    BiPiece p;
+    p.in_off = e[k];
+    p.in_len = e[k + 1] - e[k];
+    p.out_off = k * kBiBlock;
+    const uint64_t end = (k + 1) * kBiBlock < dlen ? (k + 1) * kBiBlock : dlen;
+    p.out_len = end - p.out_off;
+    return p;
+}
+
+// the largest s in [0, n) with first[s] <= e (first[0] <= e is the caller's
+// to check): the stream entry e belongs to when first[] is what compress
+// wrote.  Whatever first[] holds, the answer is below n; the caller checks
+// first[s] <= e < first[s + 1].
+SNAPMI_BI_HD inline uint32_t bi_find_stream(const uint64_t *first, uint32_t n,
+                                            uint64_t e)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (first[mid] <= e)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+} // namespace snapmi

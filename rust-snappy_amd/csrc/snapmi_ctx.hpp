@@ -205,6 +205,13 @@ struct snapmi_ctx {
     void *pin_bl = nullptr;
     size_t pin_bl_cap = 0;
     void *pin_bl2 = nullptr; // descriptors of the long streams of a batch
+    // snapmi_decompress_batch_indexed: the modes of the launch behind, the
+    // descriptor list (a slot per stream and per index entry), and the gate /
+    // counter words of its kernels
+    // (IndexArgs::gate); calls so far; whether the last call ran them
+    snapmi::DevBuf ix_modes, ix_desc, ix_gate;
+    uint64_t ix_seq = 0;
+    bool ix_stats_live = false;
     // segment size of the long-stream scan: 0 = by size (1 KiB under 256 MiB
     // of long streams, 4 KiB from there), 10 / 12 forced (test option)
     uint32_t stream_seg_log2 = 0;
@@ -313,7 +320,10 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                     const uint64_t *d_out_caps, uint64_t *d_out_lens,
                     snapmi_error *d_errs, size_t n, uint64_t blocks,
                     uint64_t slots, uint32_t small_classes = 0xF,
-                    uint64_t cnt8 = 0, uint64_t block_bytes = 0);
+                    uint64_t cnt8 = 0, uint64_t block_bytes = 0,
+                    // the block index (snapmi_blockindex.hpp), or nullptr
+                    uint64_t *d_index_first = nullptr,
+                    uint64_t *d_index = nullptr, uint64_t index_entries = 0);
 // raw decompress; d_modes optional (1 = stored chunk, plain copy)
 int launch_decompress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                       const uint64_t *d_in_lens, void *const *d_out_ptrs,
@@ -323,5 +333,9 @@ int launch_decompress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                       unsigned long long gate_value = 0,
                       // a launch beside the context's stream: its stream and
                       // its own dispatch-order scratch (no timing events)
-                      hipStream_t side = nullptr, DevBuf *side_order = nullptr);
+                      hipStream_t side = nullptr, DevBuf *side_order = nullptr,
+                      // no stream of the launch is of the lane-per-stream
+                      // classes (under 512 bytes of output): their kernels
+                      // are not launched
+                      bool wide_only = false);
 } // namespace snapmi

@@ -2757,4 +2757,124 @@ __global__ __launch_bounds__(1024) void k_long_plan(
     }
 }
 
+// ---------------------------------------------------------------------
+// snapmi_decompress_batch_indexed: the caller hands the block boundaries in
+// (snapmi_blockindex.hpp), so nothing is scanned and the host waits for
+// nothing.  ONE descriptor list holds the batch: slot i < n is stream i -
+// whole (mode 0) when its entries do not pass the rule, not this launch's
+// (mode 3) when they do (k_index_plan) - and slot n + e is index entry e:
+// for every entry of an indexed stream but its last a piece in mode 2,
+// exactly its room, so a piece writes only its own 64 KiB whatever the
+// entries say (k_index_pieces).  One launch of the batch decoder runs over
+// all of it, the short streams beside the pieces.  k_index_finish carries
+// the results of the whole streams to the caller's arrays and applies
+// stream_finish's rule to the indexed ones - every piece is this stream's,
+// reports OK and filled its room; a stream that fails it is decoded whole by
+// a second, gated launch over the caller's arrays (modes 0 for it, 3 for
+// every other stream), which names the error.
+// ---------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_index_plan(IndexArgs x)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        x.gate[1] = 0; // streams delivered by pieces
+        x.gate[2] = 0; // ... handed back
+    }
+    if (i >= x.n)
+        return;
+    const bool indexed = bi_stream_indexed(
+        (const uint8_t *)x.in_ptrs[i], x.in_lens[i], x.out_caps[i], x.index,
+        x.first[i], x.first[i + 1], x.entries);
+    x.modes[i] = 3; // of the launch behind: k_index_finish says who needs it
+    x.c_in[i] = x.in_ptrs[i];
+    x.c_inlen[i] = x.in_lens[i];
+    x.c_out[i] = x.out_ptrs[i];
+    x.c_cap[i] = x.out_caps[i];
+    x.c_outlen[i] = 0;
+    x.c_err[i].kind = SNAPMI_OK;
+    x.c_mode[i] = indexed ? 3 : 0;
+    if (indexed)
+        x.gate[0] = x.seq; // (every writer stores the same value)
+}
+
+__global__ __launch_bounds__(256) void k_index_pieces(IndexArgs x)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= x.entries)
+        return;
+    // a slot that is no piece: not the launch's (mode 3)
+    const void *in = nullptr;
+    void *out = nullptr;
+    uint64_t in_len = 0, room = 0;
+    uint32_t owner = 0xFFFFFFFFu;
+    uint8_t mode = 3;
+    if (x.gate[0] == x.seq) { // (else no stream is indexed)
+        const uint32_t s = bi_find_stream(x.first, x.n, e);
+        const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
+        // (first[] is the caller's too: the search may land anywhere)
+        if (x.c_mode[s] == 3 && f0 <= e && e + 1 < f1 && f1 <= x.entries) {
+            uint64_t dlen = 0;
+            const uint8_t *sin = (const uint8_t *)x.in_ptrs[s];
+            if (bi_header(sin, x.in_lens[s], &dlen)) {
+                const BiPiece p = bi_piece(x.index + f0, dlen, e - f0);
+                in = sin + p.in_off;
+                in_len = p.in_len;
+                out = (uint8_t *)x.out_ptrs[s] + p.out_off;
+                room = p.out_len;
+                owner = s;
+                mode = 2;
+            }
+        }
+    }
+    const uint64_t k = (uint64_t)x.n + e;
+    x.c_in[k] = in;
+    x.c_inlen[k] = in_len;
+    x.c_out[k] = out;
+    x.c_cap[k] = room;
+    x.c_outlen[k] = 0;
+    x.c_err[k].kind = SNAPMI_OK;
+    x.c_owner[e] = owner;
+    x.c_mode[k] = mode;
+}
+
+// a wavefront per stream
+__global__ __launch_bounds__(256) void k_index_finish(IndexArgs x)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
+                       (threadIdx.x >> 6);
+    if (i >= x.n)
+        return;
+    if (x.c_mode[i] != 3) { // decoded whole, as slot i: its results home
+        if (lane == 0) {
+            x.out_lens[i] = x.c_outlen[i];
+            if (x.errs)
+                x.errs[i] = x.c_err[i];
+        }
+        return;
+    }
+    const uint64_t f0 = x.first[i], f1 = x.first[i + 1];
+    bool bad = false;
+    for (uint64_t e = f0 + lane; e + 1 < f1; e += 64) {
+        const uint64_t k = (uint64_t)x.n + e;
+        if (x.c_owner[e] != (uint32_t)i || x.c_mode[k] != 2 ||
+            x.c_err[k].kind != SNAPMI_OK || x.c_outlen[k] != x.c_cap[k])
+            bad = true;
+    }
+    const bool any_bad = __ballot(bad) != 0;
+    if (lane != 0)
+        return;
+    if (any_bad) {
+        x.modes[i] = 0;    // the launch behind decodes it whole
+        x.gate[3] = x.seq; // ... and has something to do
+        atomicAdd(&x.gate[2], 1ull);
+        return;
+    }
+    uint64_t dlen = 0;
+    bi_header((const uint8_t *)x.in_ptrs[i], x.in_lens[i], &dlen);
+    x.out_lens[i] = dlen;
+    set_error(x.errs, i, SNAPMI_OK, 0, 0, 0);
+    atomicAdd(&x.gate[1], 1ull);
+}
+
 } // namespace snapmi

@@ -9,6 +9,7 @@
 #include "snapmi_tiny.hpp"
 #include "snapmi_profile.hpp"
 #include "snapmi_streamplan.hpp"
+#include "snapmi_blockindex.hpp"
 
 namespace snapmi {
 
@@ -305,6 +306,53 @@ __global__ void k_long_plan(const void *const *in_ptrs, const uint64_t *in_lens,
                             void *const *out_ptrs, const uint64_t *out_caps,
                             uint32_t n, uint64_t min_len, uint8_t *modes,
                             LongItem *list, uint32_t cap, uint32_t *count);
+
+// snapmi_decompress_batch_indexed (snapmi_blockindex.hpp): the batch, the
+// caller's index and the one descriptor list the batch decoder runs over -
+// slot i < n: stream i, slot n + e: index entry e as a piece.
+struct IndexArgs {
+    const void *const *in_ptrs;
+    const uint64_t *in_lens;
+    void *const *out_ptrs;
+    const uint64_t *out_caps;
+    uint64_t *out_lens;
+    snapmi_error *errs;    // [n] or nullptr
+    const uint64_t *first; // [n + 1]
+    const uint64_t *index; // [entries]
+    uint64_t entries;
+    uint32_t n;
+    // [n], of the launch behind the list over the caller's own arrays: 0 =
+    // an indexed stream whose pieces did not come out whole, 3 = any other
+    uint8_t *modes;
+    // [n + entries]
+    const void **c_in;
+    uint64_t *c_inlen;
+    void **c_out;
+    uint64_t *c_cap;
+    uint64_t *c_outlen;
+    snapmi_error *c_err;
+    uint8_t *c_mode;
+    uint32_t *c_owner; // [entries] the stream entry e is a piece of
+    // [0] = seq once a stream of this call is indexed, [1] streams delivered
+    // by pieces, [2] handed back, [3] = seq once one was handed back (what
+    // the launch behind waits for)
+    unsigned long long *gate;
+    unsigned long long seq;
+};
+__global__ void k_index_plan(IndexArgs x);
+__global__ void k_index_pieces(IndexArgs x);
+__global__ void k_index_finish(IndexArgs x);
+// snapmi_compress_batch_indexed: first[], then the entries
+__global__ void k_index_first(const uint64_t *in_lens, uint32_t n,
+                              uint64_t *first);
+__global__ void k_index_first_a(const uint64_t *in_lens, uint32_t n,
+                                uint64_t *first, uint64_t *part);
+__global__ void k_index_first_b(uint32_t n, uint64_t *first, uint64_t *part,
+                                uint32_t nparts);
+__global__ void k_index_first_c(uint32_t n, uint64_t *first,
+                                const uint64_t *part);
+__global__ void k_block_index(CompressArgs a, const uint64_t *first,
+                              uint64_t *index, uint64_t entries);
 
 __global__ void k_plan_decompress(DecompressArgs a);
 __global__ void k_plan_decompress_a(DecompressArgs a);

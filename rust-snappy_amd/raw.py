@@ -106,7 +106,8 @@ class Context:
         """snapmi_ctx_get_info: "scratch_bytes", "token_scratch_bytes",
         "token_pool_pages", "token_pool_pct_now", "token_pages_asked",
         "token_blocks_spilled", "host_batch_slices", "host_batch_h2d_bytes",
-        "host_batch_d2h_bytes", "host_batch_listed_slices"
+        "host_batch_d2h_bytes", "host_batch_listed_slices",
+        "index_streams_pieced", "index_streams_fallback"
         (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
@@ -318,29 +319,62 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def block_index_entries(lens):
+    """snapmi_block_index_entries: entries the block index of streams of
+    these input lengths takes, sum(ceil(len / 65536) + 1)."""
+    a = (C.c_uint64 * len(lens))(*[int(x) for x in lens])
+    return int(_lib.load().snapmi_block_index_entries(a, len(lens)))
+
+
 def compress_batch(ctx, in_ptrs, in_lens, out_ptrs, out_caps, out_lens,
-                   errs=None, host_in_lens=None):
+                   errs=None, host_in_lens=None, index_first=None, index=None,
+                   index_cap=None):
     """snapmi_compress_batch.  in_ptrs/out_ptrs: int64 CUDA tensors of device
     addresses; in_lens/out_caps/out_lens: uint64-as-int64 CUDA tensors;
     errs: optional uint8 CUDA tensor of 32*n bytes; host_in_lens: optional
-    CPU int64 tensor (or None -> fetched from the device)."""
+    CPU int64 tensor (or None -> fetched from the device).
+    With index_first (int64 CUDA tensor [n + 1]) and index (int64 CUDA tensor
+    of index_cap entries, default its size): snapmi_compress_batch_indexed,
+    which also writes the streams' block index."""
     n = in_ptrs.numel()
     h = None
     if host_in_lens is not None:
         h = C.c_void_p(host_in_lens.data_ptr())
-    rc = _lib.of(ctx).snapmi_compress_batch(
-        ctx._h, _ptr(in_ptrs), _ptr(in_lens), h, _ptr(out_ptrs),
-        _ptr(out_caps), _ptr(out_lens), _ptr(errs), n)
+    if index_first is not None or index is not None:
+        if index_cap is None:
+            index_cap = index.numel() if index is not None else 0
+        rc = _lib.of(ctx).snapmi_compress_batch_indexed(
+            ctx._h, _ptr(in_ptrs), _ptr(in_lens), h, _ptr(out_ptrs),
+            _ptr(out_caps), _ptr(out_lens), _ptr(errs), n, _ptr(index_first),
+            _ptr(index), int(index_cap))
+    else:
+        rc = _lib.of(ctx).snapmi_compress_batch(
+            ctx._h, _ptr(in_ptrs), _ptr(in_lens), h, _ptr(out_ptrs),
+            _ptr(out_caps), _ptr(out_lens), _ptr(errs), n)
     if rc:
         _raise(ctx, rc)
 
 
 def decompress_batch(ctx, in_ptrs, in_lens, out_ptrs, out_caps, out_lens,
-                     errs=None):
+                     errs=None, index_first=None, index=None,
+                     index_entries=None):
+    """snapmi_decompress_batch; with index_first / index (int64 CUDA tensors
+    as compress_batch wrote them; index_entries: the host's copy of
+    index_first[n], default the size of index):
+    snapmi_decompress_batch_indexed - the same results, the long streams on
+    a wavefront per 64 KiB block, enqueue-only."""
     n = in_ptrs.numel()
-    rc = _lib.of(ctx).snapmi_decompress_batch(
-        ctx._h, _ptr(in_ptrs), _ptr(in_lens), _ptr(out_ptrs), _ptr(out_caps),
-        _ptr(out_lens), _ptr(errs), n)
+    if index_first is not None or index is not None:
+        if index_entries is None:
+            index_entries = index.numel() if index is not None else 0
+        rc = _lib.of(ctx).snapmi_decompress_batch_indexed(
+            ctx._h, _ptr(in_ptrs), _ptr(in_lens), _ptr(out_ptrs),
+            _ptr(out_caps), _ptr(out_lens), _ptr(errs), n, _ptr(index_first),
+            _ptr(index), int(index_entries))
+    else:
+        rc = _lib.of(ctx).snapmi_decompress_batch(
+            ctx._h, _ptr(in_ptrs), _ptr(in_lens), _ptr(out_ptrs),
+            _ptr(out_caps), _ptr(out_lens), _ptr(errs), n)
     if rc:
         _raise(ctx, rc)
 

@@ -1233,6 +1233,109 @@ def raw_index(args, ctx, dev):
     return res
 
 
+def raw_ranges(args, ctx, dev):
+    """Range reads through the block index
+    (snapmi_decompress_ranges_indexed) on 256 streams of 1 MiB of text with
+    the index compress wrote: one 4 KiB range per stream, one aligned 64 KiB
+    block per stream, every stream whole as one range - each against
+    snapmi_decompress_batch_indexed of the same streams (slicing its output
+    is free) - and, to say where a small read's time goes, one lone 4 KiB
+    range and 256 empty ranges; in this process on one context, five
+    alternating repeats of
+    --steps calls each (medians, and the spread max - min over the repeats).
+    Writes profiles/raw_ranges.json (--sets 4k,...: only these shapes, for a
+    kernel trace; nothing is written)."""
+    import random
+    import statistics
+    import oracle_lib as O
+    from rust_snappy_amd import batch, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+    n, size = 256, 1 << 20
+    datas = []
+    for _ in range(n):
+        o = rng.randrange(len(text) - size)
+        datas.append(text[o:o + size])
+    src = batch.StreamBatch.from_bytes(datas, dev)
+    comp, first, index = batch.compress(ctx, src, want_index=True)
+    entries = index.numel()
+    back = batch.StreamBatch.empty([size] * n, dev)
+    blens = torch.zeros(n, dtype=torch.int64, device=dev)
+    berrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+
+    def dec_indexed():
+        raw.decompress_batch(ctx, comp.d_ptrs, comp.d_lens, back.d_ptrs,
+                             back.d_lens, blens, berrs, index_first=first,
+                             index=index, index_entries=entries)
+    shapes = {
+        "4k": [(i, rng.randrange(size - 4096), 4096) for i in range(n)],
+        "block_64k": [(i, 65536 * rng.randrange(16), 65536)
+                      for i in range(n)],
+        "whole": [(i, 0, size) for i in range(n)],
+        # what a call costs whatever it reads: ONE 4 KiB range (one piece on
+        # one wavefront behind the call's chain of launches), and 256 empty
+        # ranges (the scan and the plan alone: nothing is decoded)
+        "one_4k": [(n // 2, 300000, 4096)],
+        "none": [(i, 0, 0) for i in range(n)]}
+    if args.sets:  # (for a kernel trace of one shape; no record is written)
+        shapes = {k: v for k, v in shapes.items()
+                  if k in args.sets.split(",")}
+    repeats = 5
+    res = {"config": "raw_ranges: range reads through the block index vs "
+                     "snapmi_decompress_batch_indexed of the same 256 "
+                     "streams of 1 MiB of text",
+           "steps": args.steps, "repeats": repeats, "streams": n,
+           "bytes": n * size, "index_entries": entries}
+    timers = {}
+    if not args.sets:
+        timers["dec_indexed"] = lambda: time_it(dec_indexed, args.steps, ctx)
+    for key, ranges in shapes.items():
+        offs, lens = [r[1] for r in ranges], [r[2] for r in ranges]
+        dst = batch.StreamBatch.empty(lens, dev)
+        d_stream = torch.tensor([r[0] for r in ranges],
+                                dtype=torch.int32).to(dev)
+        d_off = torch.tensor(offs, dtype=torch.int64).to(dev)
+        d_len = torch.tensor(lens, dtype=torch.int64).to(dev)
+        m = len(ranges)
+        got = torch.zeros(m, dtype=torch.int64, device=dev)
+        errs = torch.zeros(32 * m, dtype=torch.uint8, device=dev)
+
+        def read(d_stream=d_stream, d_off=d_off, d_len=d_len, offs=offs,
+                 lens=lens, dst=dst, got=got, errs=errs):
+            raw.decompress_ranges_indexed(
+                ctx, comp.d_ptrs, comp.d_lens, first, index, d_stream, d_off,
+                d_len, offs, lens, dst.d_ptrs, got, errs,
+                index_entries=entries)
+        read()
+        ctx.synchronize()
+        assert all(e[0] == 0 for e in batch.read_errors(errs))
+        assert got.cpu().tolist() == lens
+        for r in (0, m // 2, m - 1):
+            s, o, ln = ranges[r]
+            assert dst.stream_bytes(r, ln) == datas[s][o:o + ln]
+        res[key] = {"pieces": ctx.info("range_pieces"),
+                    "bytes": sum(lens)}
+        timers["ranges_" + key] = (lambda read=read:
+                                   time_it(read, args.steps, ctx))
+    t = {k: [] for k in timers}
+    for _ in range(repeats):
+        for k, fn in timers.items():
+            t[k].append(fn() * 1e3)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    res["ms_median"] = {k: round(v, 4) for k, v in med.items()}
+    res["ms_spread"] = {k: round(max(v) - min(v), 4) for k, v in t.items()}
+    res["ms_repeats"] = {k: [round(x, 4) for x in v] for k, v in t.items()}
+    if not args.sets:
+        for key in shapes:
+            res[key]["over_dec_indexed"] = round(
+                med["ranges_" + key] / med["dec_indexed"], 3)
+        (ROOT / "profiles" / "raw_ranges.json").write_text(
+            json.dumps(res) + "\n")
+    return res
+
+
 class HostArena:
     """buffers of the given sizes, 64 bytes apart at least, in one
     pageable array or one snapmi_host_alloc allocation"""
@@ -1622,7 +1725,8 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--only", default="")
     ap.add_argument("--sets", default="",
-                    help="frames_host_batch: only these data sets (a,b,...)")
+                    help="frames_host_batch: only these data sets (a,b,...); "
+                         "raw_ranges: only these shapes, nothing recorded")
     ap.add_argument("--plan", default="",
                     help="name:gib,... - run these configs at these sizes, "
                          "one JSON line each with a \"name\" key; a config "
@@ -1649,7 +1753,8 @@ def main():
              "adapters": adapters, "stream": stream, "cfg4": cfg4,
              "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
              "frames_batch": frames_batch, "host_batch": host_batch,
-             "frames_host_batch": frames_host_batch, "raw_index": raw_index}
+             "frames_host_batch": frames_host_batch, "raw_index": raw_index,
+             "raw_ranges": raw_ranges}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1671,12 +1776,14 @@ def main():
                      ("frames_batch", frames_batch),
                      ("host_batch", host_batch),
                      ("frames_host_batch", frames_host_batch),
-                     ("raw_index", raw_index)):
+                     ("raw_index", raw_index),
+                     ("raw_ranges", raw_ranges)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
                                                          "frames_host_batch",
-                                                         "raw_index")):
+                                                         "raw_index",
+                                                         "raw_ranges")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

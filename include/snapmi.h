@@ -268,6 +268,10 @@ SNAPMI_API const char *snapmi_version(void);
  *                          / snapmi_decompress_batch_host (default 16 MiB, at
  *                          least 64 KiB): what bounds their device and pinned
  *                          staging, three slices of it being in flight
+ *   "range_scratch_bytes"  bytes of 64 KiB rooms snapmi_decompress_ranges_indexed
+ *                          may hold for the edge blocks of its ranges at once
+ *                          (default 1 GiB, at least 128 KiB; a bound on
+ *                          memory, not a tuned number)
  * The knobs of the test suite and of the experiment drivers are declared in
  * snapmi_test.h (snapmi_ctx_set_test_option).
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
@@ -321,6 +325,11 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *   "index_streams_fallback"  streams of it whose index passed, whose pieces
  *                           did not come out whole and that the batch's own
  *                           launch decoded instead (both wait for the call)
+ *   "range_pieces"          pieces the ranges of the last
+ *                           snapmi_decompress_ranges_indexed took
+ *                           (snapmi_range_pieces of the host's copies), and
+ *   "range_ranges_ok" / "range_ranges_failed"  ranges of it that succeeded /
+ *                           failed (these two wait for the call)
  * SNAPMI_E_ARGUMENT for a name that is not in this list. */
 SNAPMI_API int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name,
                                    int64_t *value);
@@ -519,6 +528,94 @@ SNAPMI_API int snapmi_decompress_batch_indexed(
     void *const *d_out_ptrs, const uint64_t *d_out_caps, uint64_t *d_out_lens,
     snapmi_error *d_errs, size_t n, const uint64_t *d_index_first /* [n+1] */,
     const uint64_t *d_index, uint64_t index_entries);
+
+/*
+ * Range reads through the block index: bytes [off, off + len) of a stream's
+ * OUTPUT, decoding only the 64 KiB blocks the range touches.
+ *
+ * snapmi_range_pieces: pieces the ranges take, the sum over r of the 64 KiB
+ * blocks that [off_r, off_r + len_r) touches (0 for len_r == 0 and for a
+ * range whose end passes 2^64; the sum saturates at 2^64 - 1).  Host code.
+ *
+ * snapmi_decompress_ranges_indexed: range r asks for output bytes
+ * [off, off + len) of stream s = d_range_stream[r] of the n streams
+ * (d_in_ptrs, d_in_lens) with the index (d_index_first, d_index,
+ * index_entries) snapmi_compress_batch_indexed wrote; they go to
+ * d_range_out[r][0, len).  h_range_off / h_range_len are the host's copies of
+ * d_range_off / d_range_len and size every launch and every buffer, as
+ * h_in_lens does for compress; both are required (NULL: SNAPMI_E_ARGUMENT,
+ * nothing is enqueued).  The device reads the d_* arrays only and never
+ * trusts that they equal the host's copies.
+ *   Piece.  Block k of a stream whose header announces dlen is input
+ *     [entry k, entry k + 1) into output [k * 65536, min((k + 1) * 65536,
+ *     dlen)), decoded like an independent stream that must fill exactly its
+ *     room - the piece of snapmi_decompress_batch_indexed.
+ *   A range succeeds when every block it touches is such a piece, reports OK
+ *     and filled its room: d_range_got[r] = len, the error kind is 0 and the
+ *     bytes are [off, off + len) of what snapmi_decompress_batch gives for the
+ *     whole stream.  That holds for every stream whose 64 KiB blocks are
+ *     self-contained: this encoder's, the reference's, libsnappy's.
+ *   Blocks the range does not touch are neither read nor judged: a stream
+ *     that is corrupt elsewhere still serves the range.
+ *   A range fails with d_range_got[r] = 0; d_range_out[r][0, len) is then
+ *     unspecified.  Nothing outside it is ever written, whatever the index,
+ *     d_index_first and the range arrays hold, and a failure never touches
+ *     another range (with the one exception named under "slots").  Why:
+ *       s >= n                         SNAPMI_E_ARGUMENT {s, n}
+ *       the header does not parse      the error snapmi_decompress_len_batch
+ *                                      gives the stream
+ *       off + len wraps or > dlen      SNAPMI_E_ARGUMENT {off, len, dlen}
+ *       slots                          the device arrays ask for more pieces
+ *         (or edge rooms) than the host's copies sized: SNAPMI_E_ARGUMENT
+ *         {first slot, pieces asked, pieces sized}.  Slots are handed out in
+ *         range order from what the DEVICE arrays ask for, so the ranges that
+ *         no longer fit are the last ones of the group the liar is in; every
+ *         range whose slots fit is exact.
+ *       no usable index                SNAPMI_E_ARGUMENT {s, block}: the
+ *         stream's entries must lie inside [0, index_entries), number
+ *         ceil(dlen / 65536) + 1, begin with the varint's length and end
+ *         with the compressed length (block: the first block the range
+ *         touches), and entry k < entry k + 1 <= compressed length for every
+ *         touched block k (block: the first that fails).  A one-block stream
+ *         with its 2 entries is usable here, unlike under the batch rule.
+ *       a piece fails or is not full   (a copy that reaches across the block
+ *         boundary, an entry in the middle of an element, a corrupt byte) the
+ *         error of the first such piece in block order, kind and fields a, b,
+ *         c those of snapmi_decompress_batch on the stream
+ *         varint(room) || piece bytes with capacity room (a piece whose
+ *         elements end short of its room is SNAPMI_HEADER_MISMATCH {room,
+ *         produced}: no piece reports OK without having filled its room).
+ *         The remedy is to decode the stream whole.
+ *   len == 0 with off <= dlen is OK: got 0, no piece.  m == 0 enqueues
+ *   nothing.  m, and n + index_entries + pieces, stay below 2^31
+ *   (SNAPMI_E_ARGUMENT).
+ * A touched block that lies wholly inside the range is decoded straight into
+ * d_range_out[r]; an EDGE block - cut by the range; told from the range alone,
+ * so a stream's short last block counts unless the range ends on a multiple
+ * of 65536 - is decoded into a 64 KiB room of context scratch, from where
+ * k_range_finish copies the wanted span.  Option "range_scratch_bytes"
+ * (default 1 GiB, at least 128 KiB) caps the rooms alive at once: the host
+ * cuts the ranges into consecutive groups whose edge blocks fit, the groups
+ * run back to back on the stream and reuse the rooms.  The default is a bound
+ * on memory, not a tuned number.
+ * The call only enqueues - no look at the batch, no wait - and can be
+ * captured into a hipGraph once the context's scratch has grown to the call's
+ * size (a buffer that grows waits for the stream; all are reserved before the
+ * first launch).  Info "range_pieces" (= snapmi_range_pieces of the host's
+ * copies), "range_ranges_ok" and "range_ranges_failed" describe the last
+ * call; reading the last two waits for it.
+ */
+SNAPMI_API uint64_t snapmi_range_pieces(const uint64_t *h_range_off,
+                                        const uint64_t *h_range_len, size_t m);
+SNAPMI_API int snapmi_decompress_ranges_indexed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    size_t n, const uint64_t *d_index_first /* [n+1] */,
+    const uint64_t *d_index, uint64_t index_entries,
+    const uint32_t *d_range_stream, const uint64_t *d_range_off,
+    const uint64_t *d_range_len, const uint64_t *h_range_off,
+    const uint64_t *h_range_len /* host copies */, void *const *d_range_out,
+    uint64_t *d_range_got, snapmi_error *d_range_errs /* may be NULL */,
+    size_t m);
 
 /*
  * ONE long raw stream, device resident, decoded by many wavefronts.

@@ -77,6 +77,10 @@ SYMBOLS = [
      [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, C.c_uint64]),
     ("snapmi_decompress_batch_indexed", C.c_int,
      [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, C.c_uint64]),
+    ("snapmi_range_pieces", C.c_uint64, [_P, _P, _SZ]),
+    ("snapmi_decompress_ranges_indexed", C.c_int,
+     [_P, _P, _P, _SZ, _P, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P,
+      _SZ]),
     ("snapmi_decompress_len_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),
     ("snapmi_decompress_stream", C.c_int,
      [_P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),

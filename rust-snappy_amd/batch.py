@@ -125,3 +125,53 @@ def decompress(ctx, src: StreamBatch, caps=None, index=None):
                              dst.d_lens, out_lens, errs)
     ctx.synchronize()
     return dst, out_lens.cpu().numpy(), read_errors(errs)
+
+
+def _i64(values):
+    """Python ints below 2^64 as the int64 tensor of the same bits."""
+    return torch.from_numpy(
+        np.asarray([int(v) & (2**64 - 1) for v in values],
+                   dtype=np.uint64).view(np.int64).copy())
+
+
+def read_ranges(ctx, src: StreamBatch, index, ranges):
+    """Range reads of compressed streams: ranges is a list of (stream, off,
+    len) into the streams' OUTPUT; index the (index_first, index) pair
+    compress(want_index=True) returned.  Only the 64 KiB blocks a range
+    touches are decoded (snapmi_decompress_ranges_indexed).  Returns (bytes
+    per range - b"" for one that failed -, per-range errors as (kind, a, b,
+    c)).  The call's limits hold: the blocks of all ranges together, as
+    asked, stay below 2^31 (raw.range_pieces)."""
+    dev = src.data.device
+    index_first, index_tensor = index
+    m = len(ranges)
+    if m == 0:
+        return [], []
+    # (as the call sees them: a stream number of 32 bits, offsets and
+    # lengths of 64)
+    streams = [int(r[0]) & 0xFFFFFFFF for r in ranges]
+    offs = [int(r[1]) & (2**64 - 1) for r in ranges]
+    lens = [int(r[2]) & (2**64 - 1) for r in ranges]
+    # a buffer for every range that fits the length its stream announces:
+    # the call fails every other range (no such stream, a header that does
+    # not parse, off + len beyond the stream) without writing a byte for it,
+    # so a wrong length costs its own range an error and no memory
+    dlens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+    raw.decompress_len_batch(ctx, src.d_ptrs, src.d_lens, dlens)
+    ctx.synchronize()
+    dlens = [int(d) & (2**64 - 1) for d in dlens.cpu().tolist()]
+    dst = StreamBatch.empty(
+        [n if s < src.n and o + n <= dlens[s] else 0
+         for s, o, n in zip(streams, offs, lens)], dev)
+    d_stream = torch.tensor(streams,
+                            dtype=torch.int64).to(torch.int32).to(dev)
+    got = torch.zeros(m, dtype=torch.int64, device=dev)
+    errs = torch.zeros(32 * m, dtype=torch.uint8, device=dev)
+    raw.decompress_ranges_indexed(
+        ctx, src.d_ptrs, src.d_lens, index_first, index_tensor, d_stream,
+        _i64(offs).to(dev), _i64(lens).to(dev), offs, lens, dst.d_ptrs, got,
+        errs, index_entries=index_tensor.numel())
+    ctx.synchronize()
+    got = got.cpu().numpy()
+    return ([dst.stream_bytes(r, got[r]) for r in range(m)],
+            read_errors(errs))

@@ -291,7 +291,8 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
                       &ctx->lane_epochs, &ctx->sd_tables, &ctx->sd_desc,
                       &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs,
                       &ctx->bl_order, &ctx->ix_modes, &ctx->ix_desc,
-                      &ctx->ix_gate})
+                      &ctx->ix_gate, &ctx->rg_desc, &ctx->rg_meta,
+                      &ctx->rg_part, &ctx->rg_room, &ctx->rg_stat})
         if (b->p)
             (void)hipFree(b->p);
     for (auto &ev : ctx->ev)
@@ -399,6 +400,8 @@ int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
         ctx->host_decode_slice_chunks = (uint64_t)value;
     else if (strcmp(name, "host_batch_slice") == 0 && value >= (1 << 16))
         ctx->host_batch_slice = (uint64_t)value;
+    else if (strcmp(name, "range_scratch_bytes") == 0 && value >= (128 << 10))
+        ctx->range_scratch_bytes = (uint64_t)value;
     else if (strcmp(name, "decode_kernel") == 0 &&
              (value == 0 || (value == 2 && kDec2) || value == 3))
         ctx->decode_kernel = ctx->lds_store_order_ok ? (int)value : 0;
@@ -835,7 +838,9 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
               &ctx->sched,
               &ctx->lane_epochs, &ctx->sd_tables, &ctx->sd_desc,
               &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs, &ctx->bl_order,
-              &ctx->ix_modes, &ctx->ix_desc, &ctx->ix_gate})
+              &ctx->ix_modes, &ctx->ix_desc, &ctx->ix_gate,
+              &ctx->rg_desc, &ctx->rg_meta, &ctx->rg_part, &ctx->rg_room,
+              &ctx->rg_stat})
             sum += b->cap;
         *value = (int64_t)sum;
     } else if (strcmp(name, "token_scratch_bytes") == 0) {
@@ -863,6 +868,19 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                                    hipMemcpyDeviceToHost));
         }
         *value = (int64_t)(name[14] == 'p' ? w[1] : w[2]);
+    } else if (strcmp(name, "range_pieces") == 0) {
+        *value = (int64_t)ctx->rg_pieces;
+    } else if (strcmp(name, "range_ranges_ok") == 0 ||
+               strcmp(name, "range_ranges_failed") == 0) {
+        // of the last snapmi_decompress_ranges_indexed: wait for it
+        unsigned long long w[2] = {0, 0};
+        if (ctx->rg_stats_live && ctx->rg_stat.p) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(w, ctx->rg_stat.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        *value = (int64_t)(name[13] == 'o' ? w[0] : w[1]);
     } else if (strcmp(name, "host_batch_slices") == 0) {
         *value = (int64_t)ctx->hb_slices;
     } else if (strcmp(name, "host_batch_h2d_bytes") == 0) {
@@ -2183,6 +2201,156 @@ int snapmi_decompress_batch_indexed(snapmi_ctx *ctx,
     return launch_decompress(ctx, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
                              d_out_lens, d_errs, x.modes, n, x.gate + 3, x.seq,
                              nullptr, nullptr, /*wide_only=*/true);
+}
+
+// Range reads through the block index (snapmi_blockindex.hpp; the kernels:
+// k_range_* in snapmi_decompress.hip).  Enqueue-only: the host copies of the
+// ranges size every launch and every buffer, and cut the ranges into groups
+// whose edge rooms fit "range_scratch_bytes"; the groups follow each other on
+// the stream and reuse the rooms and the descriptor list.
+uint64_t snapmi_range_pieces(const uint64_t *h_range_off,
+                             const uint64_t *h_range_len, size_t m)
+{
+    uint64_t pieces = 0;
+    for (size_t r = 0; h_range_off && h_range_len && r < m; r++) {
+        uint64_t k0;
+        const uint64_t c =
+            snapmi::bi_range_blocks(h_range_off[r], h_range_len[r], &k0);
+        pieces = pieces + c < pieces ? ~0ull : pieces + c; // (saturates)
+    }
+    return pieces;
+}
+
+int snapmi_decompress_ranges_indexed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    size_t n, const uint64_t *d_index_first, const uint64_t *d_index,
+    uint64_t index_entries, const uint32_t *d_range_stream,
+    const uint64_t *d_range_off, const uint64_t *d_range_len,
+    const uint64_t *h_range_off, const uint64_t *h_range_len,
+    void *const *d_range_out, uint64_t *d_range_got,
+    snapmi_error *d_range_errs, size_t m)
+{
+    if (!ctx)
+        return SNAPMI_E_ARGUMENT;
+    if (m == 0)
+        return SNAPMI_OK;
+    if (!h_range_off || !h_range_len || !d_range_stream || !d_range_off ||
+        !d_range_len || !d_range_out || !d_range_got ||
+        (n && (!d_in_ptrs || !d_in_lens || !d_index_first)) ||
+        (index_entries && !d_index) || m > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "decompress_ranges_indexed: bad args");
+    const uint64_t P = snapmi_range_pieces(h_range_off, h_range_len, m);
+    if (P > 0x7FFFFFFFu || (uint64_t)n + index_entries + P > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "decompress_ranges_indexed: n + index_entries + "
+                        "pieces must stay below 2^31");
+    // the groups: consecutive ranges whose edge rooms fit the scratch (a
+    // range has at most two: the floor of the option holds any one range)
+    struct Group {
+        uint32_t r0, mg;
+        uint64_t pieces, rooms;
+    };
+    const uint64_t room_cap = ctx->range_scratch_bytes / kBiBlock;
+    std::vector<Group> groups;
+    Group g{0, 0, 0, 0};
+    uint64_t max_pieces = 0, max_rooms = 0;
+    for (size_t r = 0; r < m; r++) {
+        uint64_t k0;
+        const uint64_t c = bi_range_blocks(h_range_off[r], h_range_len[r], &k0);
+        const uint32_t e = bi_range_edges(h_range_off[r], h_range_len[r]);
+        if (g.mg && g.rooms + e > room_cap) {
+            groups.push_back(g);
+            g = Group{(uint32_t)r, 0, 0, 0};
+        }
+        g.mg++;
+        g.pieces += c;
+        g.rooms += e;
+        if (r + 1 == m)
+            groups.push_back(g);
+    }
+    for (const Group &q : groups) {
+        max_pieces = q.pieces > max_pieces ? q.pieces : max_pieces;
+        max_rooms = q.rooms > max_rooms ? q.rooms : max_rooms;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ctx->rg_stats_live = false;
+    ctx->rg_pieces = P;
+    int rc;
+    // (everything the call's launches need, before the first of them: a
+    // buffer that grows waits for the stream)
+    const size_t per_piece = 40 + sizeof(snapmi_error) + 1;
+    const size_t parts_max = (m + 1023) / 1024;
+    if ((rc = reserve(ctx, ctx->rg_desc, max_pieces * per_piece + 64)) ||
+        (rc = reserve(ctx, ctx->rg_meta, m * 17 + 64)) ||
+        (rc = reserve(ctx, ctx->rg_part, parts_max * 16 + 64)) ||
+        (rc = reserve(ctx, ctx->rg_room, max_rooms * kBiBlock + 64)) ||
+        (rc = reserve(ctx, ctx->rg_stat, 64)) ||
+        (rc = reserve(ctx, ctx->order,
+                      (max_pieces + 72) * sizeof(uint32_t))))
+        return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->rg_stat.p, 0, 64, s));
+    ctx->rg_stats_live = true;
+    RangeArgs x;
+    x.in_ptrs = d_in_ptrs;
+    x.in_lens = d_in_lens;
+    x.first = d_index_first;
+    x.index = d_index;
+    x.entries = index_entries;
+    x.n = (uint32_t)n;
+    x.r_stream = d_range_stream;
+    x.r_off = d_range_off;
+    x.r_len = d_range_len;
+    x.r_out = d_range_out;
+    x.r_got = d_range_got;
+    x.r_errs = d_range_errs;
+    x.slot = (uint64_t *)ctx->rg_meta.p;
+    x.eslot = x.slot + m;
+    x.state = (uint8_t *)(x.eslot + m);
+    x.part = (uint64_t *)ctx->rg_part.p;
+    x.room = (uint8_t *)ctx->rg_room.p;
+    x.stat = (unsigned long long *)ctx->rg_stat.p;
+    for (const Group &q : groups) {
+        const size_t T = (size_t)q.pieces;
+        uint8_t *d = (uint8_t *)ctx->rg_desc.p;
+        x.r0 = q.r0;
+        x.mg = q.mg;
+        x.pieces = q.pieces;
+        x.rooms = q.rooms;
+        x.c_in = (const void **)d;
+        x.c_inlen = (uint64_t *)(d + T * 8);
+        x.c_out = (void **)(d + T * 16);
+        x.c_cap = (uint64_t *)(d + T * 24);
+        x.c_outlen = (uint64_t *)(d + T * 32);
+        x.c_err = (snapmi_error *)(d + T * 40);
+        x.c_mode = d + T * (40 + sizeof(snapmi_error));
+        const uint32_t parts = (q.mg + 1023) / 1024;
+        hipLaunchKernelGGL(k_range_scan_a, dim3(parts), dim3(1024), 0, s, x);
+        LAUNCH_CHECK(k_range_scan_a);
+        hipLaunchKernelGGL(k_range_scan_b, dim3(1), dim3(1024), 0, s, x,
+                           parts);
+        LAUNCH_CHECK(k_range_scan_b);
+        hipLaunchKernelGGL(k_range_scan_c, dim3(parts), dim3(1024), 0, s, x);
+        LAUNCH_CHECK(k_range_scan_c);
+        hipLaunchKernelGGL(k_range_plan, dim3((q.mg + 255) / 256), dim3(256),
+                           0, s, x);
+        LAUNCH_CHECK(k_range_plan);
+        if (T) {
+            hipLaunchKernelGGL(k_range_pieces,
+                               dim3((uint32_t)((T + 255) / 256)), dim3(256),
+                               0, s, x);
+            LAUNCH_CHECK(k_range_pieces);
+            if ((rc = launch_decompress(ctx, x.c_in, x.c_inlen, x.c_out,
+                                        x.c_cap, x.c_outlen, x.c_err,
+                                        x.c_mode, T)))
+                return rc;
+            hipLaunchKernelGGL(k_range_finish, dim3((q.mg + 3) / 4),
+                               dim3(256), 0, s, x);
+            LAUNCH_CHECK(k_range_finish);
+        }
+    }
+    return SNAPMI_OK;
 }
 
 // One stream as a batch of one, enqueue-only (the scalar entry points wait

@@ -126,4 +126,116 @@ SNAPMI_BI_HD inline uint32_t bi_find_stream(const uint64_t *first, uint32_t n,
     return lo;
 }
 
+// ---------------------------------------------------------------------
+// Range reads (snapmi_decompress_ranges_indexed): range [off, off + len) of a
+// stream's OUTPUT, delivered by the pieces of the blocks it touches.
+// ---------------------------------------------------------------------
+// Blocks the range touches: *k0 the first, the return value their number - 0
+// for an empty range and for one whose end passes 2^64 (which no stream holds:
+// the call fails it).
+SNAPMI_BI_HD inline uint64_t bi_range_blocks(uint64_t off, uint64_t len,
+                                             uint64_t *k0)
+{
+    *k0 = off / kBiBlock;
+    if (len == 0 || off + len < off)
+        return 0;
+    return (off + len - 1) / kBiBlock - *k0 + 1;
+}
+
+// Is touched block k an EDGE block - cut by the range, decoded into a room of
+// scratch and copied from there - or does [k * 64 KiB, (k + 1) * 64 KiB) lie
+// wholly inside the range, so that its piece decodes straight into the
+// caller's buffer?  Told from the range alone (the host sizes the scratch
+// without the streams): a stream's short last block is an edge block unless
+// the range ends on a multiple of 64 KiB.
+SNAPMI_BI_HD inline bool bi_range_edge(uint64_t off, uint64_t len, uint64_t k)
+{
+    return k * kBiBlock < off || off + len - k * kBiBlock < kBiBlock;
+}
+
+// Edge blocks of the range: 0, 1 or 2 (only the first and the last touched
+// block can be cut).
+SNAPMI_BI_HD inline uint32_t bi_range_edges(uint64_t off, uint64_t len)
+{
+    uint64_t k0;
+    const uint64_t cnt = bi_range_blocks(off, len, &k0);
+    if (cnt == 0)
+        return 0;
+    const uint32_t head = bi_range_edge(off, len, k0) ? 1 : 0;
+    if (cnt == 1)
+        return head;
+    return head + (bi_range_edge(off, len, k0 + cnt - 1) ? 1 : 0);
+}
+
+// The room of edge block k among the range's edge rooms: 0 for the first
+// touched block, and for the last one 1 when the first is an edge block too.
+SNAPMI_BI_HD inline uint32_t bi_range_edge_slot(uint64_t off, uint64_t len,
+                                                uint64_t k)
+{
+    const uint64_t k0 = off / kBiBlock;
+    return k != k0 && bi_range_edge(off, len, k0) ? 1 : 0;
+}
+
+// The LOCAL index rule of a range read, in two parts.  The stream's part: a
+// stream in[0, in_len) whose header (hdr bytes) announces dlen and which owns
+// index[first, next) of an index of index_entries entries is usable when its
+// entries lie inside the index and number bi_entries(dlen), entry 0 is the
+// header's length and the last entry is in_len.  (A one-block stream with its
+// 2 entries passes, unlike under bi_stream_indexed.)
+SNAPMI_BI_HD inline bool bi_range_stream_usable(uint64_t in_len, uint32_t hdr,
+                                                uint64_t dlen,
+                                                const uint64_t *index,
+                                                uint64_t first, uint64_t next,
+                                                uint64_t index_entries)
+{
+    if (next > index_entries || first > next ||
+        next - first != bi_entries(dlen))
+        return false;
+    return index[first] == hdr && index[next - 1] == in_len;
+}
+
+// The block's part, for every touched block k of a usable stream with entries
+// e[]: e[k] < e[k + 1] <= in_len.  Blocks the range does not touch are not
+// looked at.
+SNAPMI_BI_HD inline bool bi_range_block_usable(const uint64_t *e,
+                                               uint64_t in_len, uint64_t k)
+{
+    return e[k] < e[k + 1] && e[k + 1] <= in_len;
+}
+
+// The first touched block that fails the block's part, or ~0 when none does.
+SNAPMI_BI_HD inline uint64_t bi_range_first_bad_block(const uint64_t *e,
+                                                      uint64_t in_len,
+                                                      uint64_t off,
+                                                      uint64_t len)
+{
+    uint64_t k0;
+    const uint64_t cnt = bi_range_blocks(off, len, &k0);
+    for (uint64_t k = k0; k < k0 + cnt; k++)
+        if (!bi_range_block_usable(e, in_len, k))
+            return k;
+    return ~0ull;
+}
+
+// What an edge block hands to the caller: bytes [from, from + n) of its room
+// go to byte `to` of the range's buffer.
+struct BiSpan {
+    uint64_t from, to, n;
+};
+
+SNAPMI_BI_HD inline BiSpan bi_range_span(uint64_t off, uint64_t len,
+                                         uint64_t k)
+{
+    const uint64_t lo = k * kBiBlock > off ? k * kBiBlock : off;
+    // (the block's end may pass 2^64 only where the range's cannot)
+    const uint64_t hi = off + len - k * kBiBlock < kBiBlock
+                            ? off + len
+                            : (k + 1) * kBiBlock;
+    BiSpan s;
+    s.from = lo - k * kBiBlock;
+    s.to = lo - off;
+    s.n = hi - lo;
+    return s;
+}
+
 } // namespace snapmi

@@ -212,6 +212,14 @@ struct snapmi_ctx {
     snapmi::DevBuf ix_modes, ix_desc, ix_gate;
     uint64_t ix_seq = 0;
     bool ix_stats_live = false;
+    // snapmi_decompress_ranges_indexed: the piece descriptors of one group,
+    // per-range slots and verdicts, the scans' partial sums, the edge rooms
+    // (at most range_scratch_bytes of them) and the two counters of its
+    // kernels; pieces the last call's ranges took; whether it ran them
+    snapmi::DevBuf rg_desc, rg_meta, rg_part, rg_room, rg_stat;
+    uint64_t range_scratch_bytes = 1ull << 30;
+    uint64_t rg_pieces = 0;
+    bool rg_stats_live = false;
     // segment size of the long-stream scan: 0 = by size (1 KiB under 256 MiB
     // of long streams, 4 KiB from there), 10 / 12 forced (test option)
     uint32_t stream_seg_log2 = 0;

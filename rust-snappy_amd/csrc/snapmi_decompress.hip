@@ -2877,4 +2877,349 @@ __global__ __launch_bounds__(256) void k_index_finish(IndexArgs x)
     atomicAdd(&x.gate[1], 1ull);
 }
 
+// ---------------------------------------------------------------------
+// snapmi_decompress_ranges_indexed: bytes [off, off + len) of a stream's
+// output from the pieces of the blocks the range touches, nothing else of the
+// stream being read (snapmi_blockindex.hpp has the rules).  The host cuts the
+// ranges into consecutive groups whose edge rooms fit the scratch and runs,
+// per group: the scan (a) (b) (c) of what the DEVICE arrays ask for - pieces
+// and edge rooms per range, so every range knows its slots -, k_range_plan
+// (a thread per range: its verdict), k_range_pieces (a thread per piece slot:
+// a descriptor in mode 2, straight into the caller's buffer for a block that
+// lies wholly inside the range, into a room for an edge block; mode 3 for
+// a slot that is nobody's), one launch of the batch decoder over the list,
+// and k_range_finish (a wavefront per range: all pieces OK and full, the
+// wanted span of the rooms copied out, got and err).  A piece writes exactly
+// its room and a room or a block inside the buffer is all it is ever given,
+// so nothing outside [r_out[r], + r_len[r]) and the scratch is written
+// whatever the index, first[] and the range arrays hold; slots are bounded by
+// what the HOST sized (pieces, rooms), which bounds every list and the
+// scratch.
+// ---------------------------------------------------------------------
+namespace {
+// exclusive scan of (x, y) over the workgroup, totals in all[2]
+__device__ __forceinline__ void range_scan2(uint64_t &x, uint64_t &y,
+                                            uint64_t (*wave_tot)[2],
+                                            uint64_t *all)
+{
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint64_t sx = x, sy = y;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint64_t tx = __shfl_up(sx, o), ty = __shfl_up(sy, o);
+        if (lane >= o) {
+            sx += tx;
+            sy += ty;
+        }
+    }
+    if (lane == 63) {
+        wave_tot[w][0] = sx;
+        wave_tot[w][1] = sy;
+    }
+    __syncthreads();
+    uint64_t bx = 0, by = 0, tx = 0, ty = 0;
+    for (uint32_t j = 0; j < (blockDim.x >> 6); j++) {
+        if (j < w) {
+            bx += wave_tot[j][0];
+            by += wave_tot[j][1];
+        }
+        tx += wave_tot[j][0];
+        ty += wave_tot[j][1];
+    }
+    __syncthreads();
+    all[0] = tx;
+    all[1] = ty;
+    x = bx + sx - x;
+    y = by + sy - y;
+}
+
+// what range r of the device arrays asks for (the count clamped: the sums of
+// m < 2^31 of them cannot wrap)
+__device__ __forceinline__ uint64_t range_count(const RangeArgs &x, uint64_t r,
+                                                uint64_t *k0, uint32_t *edges)
+{
+    const uint64_t off = x.r_off[r], len = x.r_len[r];
+    const uint64_t cnt = bi_range_blocks(off, len, k0);
+    *edges = bi_range_edges(off, len);
+    return cnt < kRangeCountClamp ? cnt : kRangeCountClamp;
+}
+
+// ... and the slots it is given in the scans: none when it asks for more
+// than the whole group was sized for - it fails wherever it stands, and the
+// ranges behind it keep their places
+__device__ __forceinline__ void range_slots(const RangeArgs &x, uint64_t r,
+                                            uint64_t *cnt, uint64_t *edges)
+{
+    uint64_t k0;
+    uint32_t e;
+    const uint64_t c = range_count(x, r, &k0, &e);
+    const bool fits = c <= x.pieces && e <= x.rooms;
+    *cnt = fits ? c : 0;
+    *edges = fits ? e : 0;
+}
+
+__device__ __forceinline__ void range_fail(const RangeArgs &x, uint64_t r,
+                                           int kind, uint64_t a, uint64_t b,
+                                           uint64_t c)
+{
+    x.r_got[r] = 0;
+    set_error(x.r_errs, r, kind, a, b, c);
+    x.state[r] = 0;
+    if (kind != SNAPMI_OK)
+        atomicAdd(&x.stat[1], 1ull);
+    else
+        atomicAdd(&x.stat[0], 1ull);
+}
+} // namespace
+
+__global__ __launch_bounds__(1024) void k_range_scan_a(RangeArgs x)
+{
+    __shared__ uint64_t wave_tot[16][2];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t c = 0, e = 0;
+    if (i < x.mg)
+        range_slots(x, (uint64_t)x.r0 + i, &c, &e);
+    uint64_t all[2];
+    range_scan2(c, e, wave_tot, all);
+    if (i < x.mg) {
+        x.slot[x.r0 + i] = c;
+        x.eslot[x.r0 + i] = e;
+    }
+    if (threadIdx.x == 0) {
+        x.part[2 * blockIdx.x] = all[0];
+        x.part[2 * blockIdx.x + 1] = all[1];
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_range_scan_b(RangeArgs x,
+                                                       uint32_t nparts)
+{
+    __shared__ uint64_t wave_tot[16][2];
+    uint64_t carry[2] = {0, 0};
+    for (uint32_t base = 0; base < nparts; base += blockDim.x) {
+        const uint32_t j = base + threadIdx.x;
+        uint64_t c = j < nparts ? x.part[2 * j] : 0;
+        uint64_t e = j < nparts ? x.part[2 * j + 1] : 0;
+        uint64_t all[2];
+        range_scan2(c, e, wave_tot, all);
+        if (j < nparts) {
+            x.part[2 * j] = carry[0] + c;
+            x.part[2 * j + 1] = carry[1] + e;
+        }
+        carry[0] += all[0];
+        carry[1] += all[1];
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_range_scan_c(RangeArgs x)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < x.mg) {
+        x.slot[x.r0 + i] += x.part[2 * blockIdx.x];
+        x.eslot[x.r0 + i] += x.part[2 * blockIdx.x + 1];
+    }
+}
+
+// a thread per range: everything that can be said without its pieces
+__global__ __launch_bounds__(256) void k_range_plan(RangeArgs x)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= x.mg)
+        return;
+    const uint64_t r = (uint64_t)x.r0 + i;
+    const uint32_t s = x.r_stream[r];
+    const uint64_t off = x.r_off[r], len = x.r_len[r];
+    if (s >= x.n) {
+        range_fail(x, r, SNAPMI_E_ARGUMENT, s, x.n, 0);
+        return;
+    }
+    const uint64_t in_len = x.in_lens[s];
+    uint32_t hdr = 0;
+    uint64_t dlen = 0;
+    // (an empty stream announces nothing, as for snapmi_decompress_len_batch)
+    if (in_len != 0) {
+        snapmi_error he;
+        if (read_header((gcptr)x.in_ptrs[s], in_len, &hdr, &dlen, &he, 0) !=
+            SNAPMI_OK) {
+            range_fail(x, r, he.kind, he.a, he.b, he.c);
+            return;
+        }
+    }
+    if (off + len < off || off + len > dlen) {
+        range_fail(x, r, SNAPMI_E_ARGUMENT, off, len, dlen);
+        return;
+    }
+    if (len == 0) {
+        range_fail(x, r, SNAPMI_OK, 0, 0, 0); // (nothing to fetch: done)
+        return;
+    }
+    // its slots, inside what the host sized
+    uint64_t k0;
+    uint32_t edges;
+    const uint64_t cnt = range_count(x, r, &k0, &edges);
+    if (cnt > x.pieces || edges > x.rooms || x.slot[r] > x.pieces ||
+        cnt > x.pieces - x.slot[r] ||
+        x.eslot[r] > x.rooms || edges > x.rooms - x.eslot[r]) {
+        range_fail(x, r, SNAPMI_E_ARGUMENT, x.slot[r], cnt, x.pieces);
+        return;
+    }
+    if (!bi_range_stream_usable(in_len, hdr, dlen, x.index, x.first[s],
+                                x.first[s + 1], x.entries)) {
+        range_fail(x, r, SNAPMI_E_ARGUMENT, s, k0, 0);
+        return;
+    }
+    x.state[r] = 1;
+}
+
+// a thread per piece slot of the group
+__global__ __launch_bounds__(256) void k_range_pieces(RangeArgs x)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= x.pieces)
+        return;
+    // the range whose slots hold j: the last one of the group that starts at
+    // or in front of it (a range without pieces starts where the next does)
+    uint32_t lo = 0, hi = x.mg;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (x.slot[x.r0 + mid] <= j)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const uint64_t r = (uint64_t)x.r0 + lo;
+    const void *in = nullptr;
+    void *out = nullptr;
+    uint64_t in_len = 0, room = 0;
+    uint8_t mode = 3; // nobody's, or a failed range's: not the launch's
+    snapmi_error err;
+    err.kind = SNAPMI_OK;
+    err.reserved = 0;
+    err.a = err.b = err.c = 0;
+    if (x.state[r] == 1 && x.slot[r] <= j) {
+        const uint64_t off = x.r_off[r], len = x.r_len[r];
+        uint64_t k0;
+        uint32_t edges;
+        const uint64_t cnt = range_count(x, r, &k0, &edges);
+        if (j - x.slot[r] < cnt) {
+            // (state 1: the stream exists, its header parses, the range lies
+            // inside it, its entries inside the index)
+            const uint32_t s = x.r_stream[r];
+            const uint64_t k = k0 + (j - x.slot[r]);
+            const uint8_t *sin = (const uint8_t *)x.in_ptrs[s];
+            const uint64_t s_len = x.in_lens[s];
+            const uint64_t *e = x.index + x.first[s];
+            uint64_t dlen = 0;
+            bi_header(sin, s_len, &dlen);
+            if (!bi_range_block_usable(e, s_len, k)) {
+                err.kind = SNAPMI_E_ARGUMENT;
+                err.a = s;
+                err.b = k;
+            } else {
+                const BiPiece p = bi_piece(e, dlen, k);
+                in = sin + p.in_off;
+                in_len = p.in_len;
+                room = p.out_len;
+                if (bi_range_edge(off, len, k))
+                    out = x.room + (x.eslot[r] +
+                                    bi_range_edge_slot(off, len, k)) *
+                                       kBiBlock;
+                else
+                    out = (uint8_t *)x.r_out[r] + (k * kBiBlock - off);
+                mode = 2;
+            }
+        }
+    }
+    x.c_in[j] = in;
+    x.c_inlen[j] = in_len;
+    x.c_out[j] = out;
+    x.c_cap[j] = room;
+    x.c_outlen[j] = 0;
+    x.c_err[j] = err;
+    x.c_mode[j] = mode;
+}
+
+// a wavefront per range
+__global__ __launch_bounds__(256) void k_range_finish(RangeArgs x)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
+                       (threadIdx.x >> 6);
+    if (i >= x.mg)
+        return;
+    const uint64_t r = (uint64_t)x.r0 + i;
+    if (x.state[r] != 1) // k_range_plan wrote its got and err
+        return;
+    const uint64_t off = x.r_off[r], len = x.r_len[r];
+    uint64_t k0;
+    uint32_t edges;
+    const uint64_t cnt = range_count(x, r, &k0, &edges);
+    const uint64_t j0 = x.slot[r];
+    // the first piece, in block order, that is not OK and full
+    uint64_t bad = ~0ull;
+    for (uint64_t t = lane; t < cnt && bad == ~0ull; t += 64) {
+        const uint64_t j = j0 + t;
+        if (x.c_mode[j] != 2 || x.c_err[j].kind != SNAPMI_OK ||
+            x.c_outlen[j] != x.c_cap[j])
+            bad = j;
+    }
+    for (uint32_t o = 32; o; o >>= 1) {
+        const uint64_t t = __shfl_xor(bad, o);
+        bad = t < bad ? t : bad;
+    }
+    if (bad != ~0ull) {
+        if (lane == 0) {
+            const snapmi_error e = x.c_err[bad];
+            x.r_got[r] = 0;
+            if (e.kind != SNAPMI_OK)
+                set_error(x.r_errs, r, e.kind, e.a, e.b, e.c);
+            // not reached, kept as the guard of an invariant: every decoder
+            // takes a mode-2 piece's room for the announced length, writes
+            // out_lens = room only beside OK and reports HEADER_MISMATCH
+            // {room, produced} when the elements end short of it, so a piece
+            // that reports OK is full - and a state-1 range's slots are all
+            // mode 2 or carry k_range_pieces' own error
+            else
+                set_error(x.r_errs, r, SNAPMI_E_ARGUMENT,
+                          x.r_stream[r], k0 + (bad - j0), 0);
+            atomicAdd(&x.stat[1], 1ull);
+        }
+        return;
+    }
+    // the wanted span of the edge rooms: bytes up to the destination's next
+    // 16-byte boundary, 16-byte stores fed by unaligned 16-byte loads, bytes
+    typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+    uint8_t *const dst0 = (uint8_t *)x.r_out[r];
+    for (uint32_t q = 0; q < 2; q++) {
+        const uint64_t k = q == 0 ? k0 : k0 + cnt - 1;
+        if ((q == 1 && cnt == 1) || !bi_range_edge(off, len, k))
+            continue;
+        const BiSpan sp = bi_range_span(off, len, k);
+        const uint8_t *from =
+            x.room +
+            (x.eslot[r] + bi_range_edge_slot(off, len, k)) * kBiBlock +
+            sp.from;
+        uint8_t *to = dst0 + sp.to;
+        const uint32_t n = (uint32_t)sp.n; // <= 64 KiB
+        uint32_t head = (uint32_t)((16 - ((uintptr_t)to & 15)) & 15);
+        if (head > n)
+            head = n;
+        if (lane < head)
+            to[lane] = from[lane];
+        const uint32_t body = (n - head) & ~15u;
+        for (uint32_t b = 16 * lane; b < body; b += 16 * 64) {
+            u32x4 v;
+            __builtin_memcpy(&v, from + head + b, 16);
+            *(g_u32x4 *)(to + head + b) = v;
+        }
+        const uint32_t tail = n - head - body;
+        if (lane < tail)
+            to[head + body + lane] = from[head + body + lane];
+    }
+    if (lane == 0) {
+        x.r_got[r] = len;
+        set_error(x.r_errs, r, SNAPMI_OK, 0, 0, 0);
+        atomicAdd(&x.stat[0], 1ull);
+    }
+}
+
 } // namespace snapmi

@@ -342,6 +342,51 @@ struct IndexArgs {
 __global__ void k_index_plan(IndexArgs x);
 __global__ void k_index_pieces(IndexArgs x);
 __global__ void k_index_finish(IndexArgs x);
+// snapmi_decompress_ranges_indexed (snapmi_blockindex.hpp): the streams, their
+// index, the ranges, and ONE GROUP of consecutive ranges [r0, r0 + mg) whose
+// pieces (host: `pieces`) and edge rooms (host: `rooms`) this round of
+// launches runs.  Slot j < pieces of the descriptor list is the j-th touched
+// block of the group in range order.
+struct RangeArgs {
+    const void *const *in_ptrs;
+    const uint64_t *in_lens;
+    const uint64_t *first; // [n + 1]
+    const uint64_t *index; // [entries]
+    uint64_t entries;
+    uint32_t n;
+    const uint32_t *r_stream; // [m], as are the next five
+    const uint64_t *r_off;
+    const uint64_t *r_len;
+    void *const *r_out;
+    uint64_t *r_got;
+    snapmi_error *r_errs; // or nullptr
+    uint32_t r0, mg;
+    uint64_t pieces, rooms; // what the host sized for this group
+    // [m]: first piece slot and first edge room of the range inside its group
+    // (exclusive scans of what the DEVICE arrays ask for), and its verdict:
+    // 0 failed or empty (got and err are written), 1 its pieces decide
+    uint64_t *slot, *eslot;
+    uint8_t *state;
+    uint64_t *part; // [2 * parts]: the scans' workgroup totals
+    uint8_t *room;  // [rooms * 64 KiB]
+    // [pieces]
+    const void **c_in;
+    uint64_t *c_inlen;
+    void **c_out;
+    uint64_t *c_cap;
+    uint64_t *c_outlen;
+    snapmi_error *c_err;
+    uint8_t *c_mode;
+    unsigned long long *stat; // [0] ranges that succeeded, [1] that failed
+};
+// pieces a range may ask for in the scan: more than any call holds
+constexpr uint64_t kRangeCountClamp = 1ull << 32;
+__global__ void k_range_scan_a(RangeArgs x);
+__global__ void k_range_scan_b(RangeArgs x, uint32_t nparts);
+__global__ void k_range_scan_c(RangeArgs x);
+__global__ void k_range_plan(RangeArgs x);
+__global__ void k_range_pieces(RangeArgs x);
+__global__ void k_range_finish(RangeArgs x);
 // snapmi_compress_batch_indexed: first[], then the entries
 __global__ void k_index_first(const uint64_t *in_lens, uint32_t n,
                               uint64_t *first);

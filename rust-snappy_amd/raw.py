@@ -107,8 +107,8 @@ class Context:
         "token_pool_pages", "token_pool_pct_now", "token_pages_asked",
         "token_blocks_spilled", "host_batch_slices", "host_batch_h2d_bytes",
         "host_batch_d2h_bytes", "host_batch_listed_slices",
-        "index_streams_pieced", "index_streams_fallback"
-        (include/snapmi.h)."""
+        "index_streams_pieced", "index_streams_fallback", "range_pieces",
+        "range_ranges_ok", "range_ranges_failed" (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:
@@ -375,6 +375,45 @@ def decompress_batch(ctx, in_ptrs, in_lens, out_ptrs, out_caps, out_lens,
         rc = _lib.of(ctx).snapmi_decompress_batch(
             ctx._h, _ptr(in_ptrs), _ptr(in_lens), _ptr(out_ptrs),
             _ptr(out_caps), _ptr(out_lens), _ptr(errs), n)
+    if rc:
+        _raise(ctx, rc)
+
+
+def _u64_array(values):
+    return (C.c_uint64 * len(values))(*[int(x) & (2**64 - 1) for x in values])
+
+
+def range_pieces(offs, lens):
+    """snapmi_range_pieces: pieces the ranges [off, off + len) take, the sum
+    of the 64 KiB blocks each touches."""
+    assert len(offs) == len(lens)
+    return int(_lib.load().snapmi_range_pieces(
+        _u64_array(offs), _u64_array(lens), len(offs)))
+
+
+def decompress_ranges_indexed(ctx, in_ptrs, in_lens, index_first, index,
+                              range_stream, range_off, range_len,
+                              host_range_off, host_range_len, range_out,
+                              range_got, range_errs=None, index_entries=None):
+    """snapmi_decompress_ranges_indexed: output bytes [off, off + len) of
+    stream range_stream[r] into the buffer at range_out[r], decoding only the
+    blocks the range touches.  in_ptrs / in_lens / index_first / index: the
+    streams and their block index as compress_batch wrote them (int64 CUDA
+    tensors); range_stream: int32 CUDA tensor; range_off / range_len /
+    range_out / range_got: uint64-as-int64 CUDA tensors [m]; host_range_off /
+    host_range_len: the host's copies, sequences of ints; range_errs: optional
+    uint8 CUDA tensor of 32*m bytes.  Enqueue-only."""
+    m = range_stream.numel()
+    assert len(host_range_off) == m and len(host_range_len) == m
+    if index_entries is None:
+        index_entries = index.numel() if index is not None else 0
+    rc = _lib.of(ctx).snapmi_decompress_ranges_indexed(
+        ctx._h, _ptr(in_ptrs), _ptr(in_lens),
+        in_ptrs.numel() if in_ptrs is not None else 0, _ptr(index_first),
+        _ptr(index), int(index_entries), _ptr(range_stream), _ptr(range_off),
+        _ptr(range_len), _u64_array(host_range_off),
+        _u64_array(host_range_len), _ptr(range_out), _ptr(range_got),
+        _ptr(range_errs), m)
     if rc:
         _raise(ctx, rc)
 

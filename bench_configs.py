@@ -1233,6 +1233,148 @@ def raw_index(args, ctx, dev):
     return res
 
 
+def raw_index_build(args, ctx, dev):
+    """Building the block index of streams that came without one
+    (snapmi_build_block_index) on raw_index's 256 streams of 1 MiB of text
+    and its mixed set of 512 streams of 100 B .. 1 MiB, compressed WITHOUT an
+    index: the build, snapmi_decompress_batch with batch_long_streams 1 (the
+    yardstick: the same scan plus the piece decode) and 0, and the indexed
+    decode through the built index - all in this process on one context, five
+    alternating repeats of --steps calls each (medians, and the spread max -
+    min over the repeats) - and build / (unindexed - indexed), the decodes
+    after which building has paid for itself.  The text set again with every
+    stream's last byte cut off (all CORRUPT: the scan gives up on every one
+    and the walker walks it to its end - the worst a batch can do to the
+    build).  With the test build of the library also the walker alone
+    (index_build_route 1).
+    Writes profiles/raw_index_build.json."""
+    import random
+    import statistics
+    import oracle_lib as O
+    from rust_snappy_amd import _lib, batch, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+
+    def piece(n):
+        o = rng.randrange(len(text) - n)
+        return text[o:o + n]
+    sets = {"text_256x1m": [piece(1 << 20) for _ in range(256)],
+            "mixed_512_100b_1m": [piece(int(100 * (10486 ** rng.random())))
+                                  for _ in range(512)]}
+    has_test = hasattr(_lib.of(ctx), "snapmi_ctx_set_test_option")
+    repeats = 5
+    res = {"config": "raw_index_build: snapmi_build_block_index vs "
+                     "snapmi_decompress_batch (batch_long_streams 1 / 0) and "
+                     "the indexed decode through the built index",
+           "steps": args.steps, "repeats": repeats, "test_build": has_test}
+    for key, datas in sets.items():
+        n = len(datas)
+        nbytes = sum(len(d) for d in datas)
+        src = batch.StreamBatch.from_bytes(datas, dev)
+        comp, clens, errs = batch.compress(ctx, src)   # no index
+        assert all(e[0] == 0 for e in errs)
+        comp = batch.StreamBatch(comp.data, comp.offsets, clens)
+        h_in = [int(x) for x in clens]
+        h_out = [len(d) for d in datas]
+        entries = raw.block_index_entries(h_out)
+        first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        index = torch.zeros(entries, dtype=torch.int64, device=dev)
+        status = torch.zeros(n, dtype=torch.uint8, device=dev)
+        back = batch.StreamBatch.empty(h_out, dev)
+        blens = torch.zeros(n, dtype=torch.int64, device=dev)
+        berrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+
+        def build(src=comp, h_in=h_in):
+            raw.build_block_index(ctx, src.d_ptrs, src.d_lens, h_in, h_out,
+                                  first, index, status, index_cap=entries)
+
+        def dec_indexed():
+            raw.decompress_batch(ctx, comp.d_ptrs, comp.d_lens, back.d_ptrs,
+                                 back.d_lens, blens, berrs,
+                                 index_first=first, index=index,
+                                 index_entries=entries)
+
+        def dec_plain(long_streams):
+            def run():
+                raw.decompress_batch(ctx, comp.d_ptrs, comp.d_lens,
+                                     back.d_ptrs, back.d_lens, blens, berrs)
+
+            def timed():
+                ctx.set_option("batch_long_streams", long_streams)
+                try:
+                    return time_it(run, args.steps, ctx)
+                finally:
+                    ctx.set_option("batch_long_streams", 1)
+            return timed
+        # the built index is what compress would have written
+        _, want_first, want_index = batch.compress(ctx, src, want_index=True)
+        build()
+        ctx.synchronize()
+        assert torch.equal(first, want_first) and torch.equal(index, want_index)
+        assert bool((status == 1).all())
+        walked = ctx.info("index_build_walked")
+        dec_indexed()
+        pieced = ctx.info("index_streams_pieced")
+        assert all(e[0] == 0 for e in batch.read_errors(berrs))
+        for i in (0, n // 2, n - 1):
+            assert back.stream_bytes(i, int(blens[i])) == datas[i]
+        timers = {"build": lambda: time_it(build, args.steps, ctx),
+                  "dec_long_streams_1": dec_plain(1),
+                  "dec_long_streams_0": dec_plain(0),
+                  "dec_indexed": lambda: time_it(dec_indexed, args.steps, ctx)}
+        extra = {}
+        if key == "text_256x1m":
+            # every stream cut by a byte: CORRUPT, by the walker, to its end
+            cut = batch.StreamBatch(comp.data, comp.offsets,
+                                    [x - 1 for x in h_in])
+            cut_in = [x - 1 for x in h_in]
+
+            def build_cut():
+                build(cut, cut_in)
+            build_cut()
+            ctx.synchronize()
+            extra["cut_walked"] = ctx.info("index_build_walked")
+            assert ctx.info("index_build_corrupt") == n
+            timers["build_all_corrupt"] = lambda: time_it(build_cut,
+                                                          args.steps, ctx)
+            if has_test:
+                def walker_alone():
+                    ctx.set_test_option("index_build_route", 1)
+                    try:
+                        return time_it(build, args.steps, ctx)
+                    finally:
+                        ctx.set_test_option("index_build_route", 0)
+                timers["walker_alone"] = walker_alone
+        t = {k: [] for k in timers}
+        for _ in range(repeats):
+            for k, fn in timers.items():
+                t[k].append(fn() * 1e3)
+        build()   # (the last timed build may have been the cut one)
+        ctx.synchronize()
+        assert torch.equal(index, want_index)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        gain1 = med["dec_long_streams_1"] - med["dec_indexed"]
+        gain0 = med["dec_long_streams_0"] - med["dec_indexed"]
+        res[key] = {
+            "streams": n, "bytes": nbytes, "compressed_bytes": sum(h_in),
+            "index_entries": entries, "index_build_walked": walked,
+            "index_streams_pieced": pieced, **extra,
+            "ms_median": {k: round(v, 4) for k, v in med.items()},
+            "ms_spread": {k: round(max(v) - min(v), 4) for k, v in t.items()},
+            "ms_repeats": {k: [round(x, 4) for x in v] for k, v in t.items()},
+            "build_over_dec_long_streams_1": round(
+                med["build"] / med["dec_long_streams_1"], 3),
+            "decodes_to_pay_vs_long_streams_1":
+                round(med["build"] / gain1, 2) if gain1 > 0 else None,
+            "decodes_to_pay_vs_long_streams_0":
+                round(med["build"] / gain0, 2) if gain0 > 0 else None}
+    (ROOT / "profiles" / "raw_index_build.json").write_text(
+        json.dumps(res) + "\n")
+    return res
+
+
 def raw_ranges(args, ctx, dev):
     """Range reads through the block index
     (snapmi_decompress_ranges_indexed) on 256 streams of 1 MiB of text with
@@ -1754,7 +1896,7 @@ def main():
              "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
              "frames_batch": frames_batch, "host_batch": host_batch,
              "frames_host_batch": frames_host_batch, "raw_index": raw_index,
-             "raw_ranges": raw_ranges}
+             "raw_ranges": raw_ranges, "raw_index_build": raw_index_build}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1777,13 +1919,15 @@ def main():
                      ("host_batch", host_batch),
                      ("frames_host_batch", frames_host_batch),
                      ("raw_index", raw_index),
-                     ("raw_ranges", raw_ranges)):
+                     ("raw_ranges", raw_ranges),
+                     ("raw_index_build", raw_index_build)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
                                                          "frames_host_batch",
                                                          "raw_index",
-                                                         "raw_ranges")):
+                                                         "raw_ranges",
+                                                         "raw_index_build")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

@@ -330,6 +330,11 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *                           (snapmi_range_pieces of the host's copies), and
  *   "range_ranges_ok" / "range_ranges_failed"  ranges of it that succeeded /
  *                           failed (these two wait for the call)
+ *   "index_build_built" / "index_build_unaligned" / "index_build_corrupt" /
+ *   "index_build_missized"  streams of the last snapmi_build_block_index by
+ *                           verdict, and
+ *   "index_build_walked"    streams of it the sequential walker handled (all
+ *                           five wait for the call)
  * SNAPMI_E_ARGUMENT for a name that is not in this list. */
 SNAPMI_API int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name,
                                    int64_t *value);
@@ -616,6 +621,83 @@ SNAPMI_API int snapmi_decompress_ranges_indexed(
     const uint64_t *h_range_len /* host copies */, void *const *d_range_out,
     uint64_t *d_range_got, snapmi_error *d_range_errs /* may be NULL */,
     size_t m);
+
+/*
+ * The block index of streams that came WITHOUT one - written by the
+ * reference, by libsnappy, by snapmi_compress_batch, read from a file - built
+ * on the device from the streams alone, so that
+ * snapmi_decompress_batch_indexed and snapmi_decompress_ranges_indexed serve
+ * data that exists.  Nothing is decoded and no output buffer is needed.
+ *
+ * The rule (bi_build in csrc/snapmi_blockindex.hpp is its one definition).
+ * A stream of at most one block (its header announces dlen <= 65536) is not
+ * walked: a header that parses gives the entries {header bytes, compressed
+ * length} - which the range call accepts - and SNAPMI_INDEX_BUILT; dlen == 0
+ * has the one entry {header bytes}, and only when the stream is nothing but
+ * its header (else SNAPMI_INDEX_CORRUPT).  A longer stream is walked from
+ * element to element behind the varint, reading tag bytes and literal length
+ * bytes only.  Copy offsets are NOT looked at: the builder finds boundaries
+ * and gives no verdict on whether the stream decodes - the decoders distrust
+ * every index, and a stream that fails there is found there, as today.
+ *   SNAPMI_INDEX_BUILT (1)      every element fits inside the stream, the
+ *     chain ends exactly at its end having produced exactly dlen, and for
+ *     every k in 1 .. blocks - 1 an element starts where exactly k * 65536
+ *     bytes have been produced.  Entries: the layout
+ *     snapmi_compress_batch_indexed writes - the varint's length, those
+ *     elements' offsets, the compressed length.
+ *   SNAPMI_INDEX_UNALIGNED (2)  the chain is whole as above, but an element
+ *     straddles a multiple of 65536.  All the stream's entries are 0.
+ *   SNAPMI_INDEX_CORRUPT (3)    the header does not parse, an element does
+ *     not fit, or the chain ends anywhere but at (compressed length, dlen).
+ *     All entries 0.
+ *   SNAPMI_INDEX_MISSIZED (4)   d_in_lens[i], or the length the header
+ *     announces, is not what the host's copy said.  All entries 0.
+ * Entries that are all 0 pass neither call's rule: such a stream is decoded
+ * whole by snapmi_decompress_batch_indexed, and a range on it fails with "no
+ * usable index".
+ *
+ * Host copies.  h_in_lens is the host's copy of d_in_lens, h_out_lens[i] the
+ * length stream i's header announces (from snapmi_decompress_len_batch, or
+ * the caller's metadata).  Both are required (NULL: SNAPMI_E_ARGUMENT,
+ * nothing is enqueued).  They size the index, the scratch and every launch, as
+ * h_range_off / h_range_len do for the range call; the device never trusts
+ * them, and a stream they are wrong about is MISSIZED and keeps the
+ * ceil(h_out_lens[i] / 65536) + 1 entries the host gave it, all 0.
+ * Layout.  d_index_first [n + 1] is the prefix sum of those counts;
+ * snapmi_block_index_entries(h_out_lens, n) is their total, the index_entries
+ * the decode calls want.  index_cap below it is SNAPMI_E_ARGUMENT, and
+ * nothing is enqueued or written.  d_status [n] (may be NULL) gets the
+ * verdicts.
+ * Bounds.  Entries at or behind d_index_first[n] are never written; nothing
+ * outside d_index_first[0, n], d_index[0, entries) and d_status[0, n) is
+ * written whatever the streams hold; no input byte at or behind h_in_lens[i]
+ * is read; n + entries stays below 2^31 (SNAPMI_E_ARGUMENT); n == 0 writes
+ * d_index_first[0] = 0 only.
+ * Ordering.  Everything runs on the context's stream.  The call waits on the
+ * host in two cases only: a scratch buffer has to grow (before the first
+ * launch, as in every call of this section), or its own pinned staging is
+ * still being read by a copy of an earlier call - it then waits for the event
+ * of that copy, not for the stream.  Capture into a hipGraph is not promised.
+ * There is no limit of 16 384 streams or 4 096 long ones: the streams of two
+ * blocks and more are cut into groups whose descriptors and scan tables are
+ * bounded whatever n is; the groups follow each other on the stream.
+ * Info "index_build_built", "index_build_unaligned", "index_build_corrupt",
+ * "index_build_missized" count the last call's verdicts and
+ * "index_build_walked" the streams its sequential walker handled (those the
+ * parallel scan gave up on); reading them waits for the call.
+ */
+enum snapmi_index_status {
+    SNAPMI_INDEX_BUILT = 1,
+    SNAPMI_INDEX_UNALIGNED = 2,
+    SNAPMI_INDEX_CORRUPT = 3,
+    SNAPMI_INDEX_MISSIZED = 4
+};
+SNAPMI_API int snapmi_build_block_index(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    const uint64_t *h_in_lens, const uint64_t *h_out_lens /* host copies */,
+    size_t n, uint64_t *d_index_first /* out, [n+1] */,
+    uint64_t *d_index /* out */, uint64_t index_cap,
+    uint8_t *d_status /* out, [n]; may be NULL */);
 
 /*
  * ONE long raw stream, device resident, decoded by many wavefronts.

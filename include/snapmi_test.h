@@ -69,6 +69,14 @@ extern "C" {
  *                          snapmi_frame_decompress_batch_host whose streams
  *                          are all well-formed is decoded from the host's
  *                          chunk list; 0: the device always walks
+ *   "index_build_route"    snapmi_build_block_index: 0 (default) streams of
+ *                          two blocks and more go through the parallel scan
+ *                          and those it gives up on to the sequential walker;
+ *                          1: all of them to the walker; 2: the scan alone,
+ *                          and what it gives up on is reported CORRUPT (shows
+ *                          a test which streams fell through)
+ *   "index_build_group_streams"  most streams in one group of its scan route
+ *                          (1 .. 4096, default 4096)
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
  */
 SNAPMI_API int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,

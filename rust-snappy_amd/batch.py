@@ -127,6 +127,34 @@ def decompress(ctx, src: StreamBatch, caps=None, index=None):
     return dst, out_lens.cpu().numpy(), read_errors(errs)
 
 
+def build_index(ctx, src: StreamBatch, out_lens=None):
+    """The block index of streams that came without one - the reference's,
+    libsnappy's, an earlier compress() - built on the device
+    (snapmi_build_block_index).  out_lens: the lengths the streams' headers
+    announce, when the caller has them (default: asked of the device with
+    snapmi_decompress_len_batch; a header that does not parse counts as 0).
+    Returns (index_first, index, status): the pair decompress(index=...) and
+    read_ranges take, and the per-stream verdicts (raw.INDEX_*) as a list.  A
+    stream that is not INDEX_BUILT has all its entries 0: it is decoded whole,
+    and a range on it has no usable index."""
+    dev = src.data.device
+    if out_lens is None:
+        lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+        raw.decompress_len_batch(ctx, src.d_ptrs, src.d_lens, lens)
+        ctx.synchronize()
+        out_lens = lens.cpu().tolist()
+    out_lens = [int(d) & (2**64 - 1) for d in out_lens]
+    entries = raw.block_index_entries(out_lens)
+    index_first = torch.zeros(src.n + 1, dtype=torch.int64, device=dev)
+    index = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+    status = torch.zeros(max(src.n, 1), dtype=torch.uint8, device=dev)
+    raw.build_block_index(ctx, src.d_ptrs, src.d_lens,
+                          [int(x) for x in src.lens], out_lens, index_first,
+                          index, status, index_cap=entries)
+    ctx.synchronize()
+    return index_first, index[:entries], status[:src.n].cpu().tolist()
+
+
 def _i64(values):
     """Python ints below 2^64 as the int64 tensor of the same bits."""
     return torch.from_numpy(

@@ -269,7 +269,8 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
         (void)hipStreamSynchronize(ctx->stream);
     host_pipe_destroy(ctx);
     for (void *p : {ctx->pin_in, ctx->pin_out, ctx->pin_desc, ctx->pin_bl,
-                    ctx->pin_bl2})
+                    ctx->pin_bl2, ctx->pin_ib, ctx->pin_ibg[0],
+                    ctx->pin_ibg[1]})
         if (p)
             (void)hipHostFree(p);
     if (ctx->h_mail)
@@ -292,9 +293,13 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
                       &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs,
                       &ctx->bl_order, &ctx->ix_modes, &ctx->ix_desc,
                       &ctx->ix_gate, &ctx->rg_desc, &ctx->rg_meta,
-                      &ctx->rg_part, &ctx->rg_room, &ctx->rg_stat})
+                      &ctx->rg_part, &ctx->rg_room, &ctx->rg_stat,
+                      &ctx->ib_meta, &ctx->ib_stat})
         if (b->p)
             (void)hipFree(b->p);
+    for (hipEvent_t ev : {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1]})
+        if (ev)
+            (void)hipEventDestroy(ev);
     for (auto &ev : ctx->ev)
         if (ev)
             (void)hipEventDestroy(ev);
@@ -453,6 +458,12 @@ int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
     } else if (strcmp(name, "lane_epoch_preset") == 0 && value >= -1 &&
              value <= 0xFFFF)
         ctx->lane_epoch_preset = value;
+    else if (strcmp(name, "index_build_route") == 0 && value >= 0 &&
+             value <= 2)
+        ctx->index_build_route = (uint32_t)value;
+    else if (strcmp(name, "index_build_group_streams") == 0 && value >= 1 &&
+             value <= 4096)
+        ctx->index_build_group_streams = (uint32_t)value;
     else if (strcmp(name, "stream_seg_log2") == 0 &&
              (value == 0 || value == 10 || value == 12))
         ctx->stream_seg_log2 = (uint32_t)value; // 0: by size
@@ -840,7 +851,7 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
               &ctx->bl_modes, &ctx->bl_list, &ctx->bl_descs, &ctx->bl_order,
               &ctx->ix_modes, &ctx->ix_desc, &ctx->ix_gate,
               &ctx->rg_desc, &ctx->rg_meta, &ctx->rg_part, &ctx->rg_room,
-              &ctx->rg_stat})
+              &ctx->rg_stat, &ctx->ib_meta, &ctx->ib_stat})
             sum += b->cap;
         *value = (int64_t)sum;
     } else if (strcmp(name, "token_scratch_bytes") == 0) {
@@ -881,6 +892,23 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                                    hipMemcpyDeviceToHost));
         }
         *value = (int64_t)(name[13] == 'o' ? w[0] : w[1]);
+    } else if (strncmp(name, "index_build_", 12) == 0 &&
+               (strcmp(name + 12, "built") == 0 ||
+                strcmp(name + 12, "unaligned") == 0 ||
+                strcmp(name + 12, "corrupt") == 0 ||
+                strcmp(name + 12, "missized") == 0 ||
+                strcmp(name + 12, "walked") == 0)) {
+        // of the last snapmi_build_block_index: wait for it
+        unsigned long long w[5] = {0, 0, 0, 0, 0};
+        if (ctx->ib_stats_live && ctx->ib_stat.p) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(w, ctx->ib_stat.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        const char c = name[12];
+        *value = (int64_t)w[c == 'b' ? 0 : c == 'u' ? 1 : c == 'c' ? 2
+                            : c == 'm' ? 3 : 4];
     } else if (strcmp(name, "host_batch_slices") == 0) {
         *value = (int64_t)ctx->hb_slices;
     } else if (strcmp(name, "host_batch_h2d_bytes") == 0) {
@@ -1841,6 +1869,11 @@ static size_t long_stream_min()
 
 constexpr size_t kBatchLongMaxN = 16384;
 constexpr uint32_t kBatchLongMaxL = 4096;
+static_assert(kBiBuilt == SNAPMI_INDEX_BUILT &&
+                  kBiUnaligned == SNAPMI_INDEX_UNALIGNED &&
+                  kBiCorrupt == SNAPMI_INDEX_CORRUPT &&
+                  kBiMissized == SNAPMI_INDEX_MISSIZED,
+              "snapmi_blockindex.hpp restates the verdicts of snapmi.h");
 static_assert(sizeof(snapmi_error) == kStreamErrBytes,
               "snapmi_streamplan.hpp sizes the piece descriptors with it");
 
@@ -1903,10 +1936,12 @@ static void stream_pointers(snapmi_ctx *ctx, const StreamPlan &p,
 }
 
 // The streams of plan `p`, whose descriptor block (descriptors, then the
-// workgroup prefixes) the device holds at `dev`, from their headers to their
-// piece descriptors: head, scan, the levels, chain, cuts, pieces.
-static int launch_stream_chain(snapmi_ctx *ctx, const StreamPlan &p,
-                               const void *dev)
+// workgroup prefixes) the device holds at `dev`, from their headers to the
+// element boundaries at every 64 KiB of output: head, scan, the levels,
+// chain, cuts.  (snapmi_build_block_index stops here: it keeps cuts[] and
+// decodes nothing.)
+static int launch_stream_cuts(snapmi_ctx *ctx, const StreamPlan &p,
+                              const void *dev)
 {
     hipStream_t s = ctx->stream;
     const uint32_t L = p.n;
@@ -1940,8 +1975,22 @@ static int launch_stream_chain(snapmi_ctx *ctx, const StreamPlan &p,
     hipLaunchKernelGGL(k_bstream_cuts, dim3(p.grid[kPCuts]), dim3(64), 0, s,
                        B(kPCuts));
     LAUNCH_CHECK(k_bstream_cuts);
+    return SNAPMI_OK;
+}
+
+// ... and on to their piece descriptors: the same, then pieces.
+static int launch_stream_chain(snapmi_ctx *ctx, const StreamPlan &p,
+                               const void *dev)
+{
+    if (int rc = launch_stream_cuts(ctx, p, dev))
+        return rc;
+    BatchStreams b;
+    b.descs = (const StreamArgs *)dev;
+    b.pre = (const uint32_t *)((const uint8_t *)dev + p.pre_off) +
+            (size_t)kPPieces * (p.n + 1);
+    b.n = p.n;
     hipLaunchKernelGGL(k_bstream_pieces, dim3(p.grid[kPPieces]), dim3(256), 0,
-                       s, B(kPPieces));
+                       ctx->stream, b);
     LAUNCH_CHECK(k_bstream_pieces);
     return SNAPMI_OK;
 }
@@ -2349,6 +2398,247 @@ int snapmi_decompress_ranges_indexed(
                                dim3(256), 0, s, x);
             LAUNCH_CHECK(k_range_finish);
         }
+    }
+    return SNAPMI_OK;
+}
+
+// The block index of streams that came without one (bi_build of
+// snapmi_blockindex.hpp; the kernels: k_index_build_*, k_index_walk in
+// snapmi_decompress.hip).  The host's copies of the lengths size the index,
+// the scratch and every launch; what the device finds out - which streams are
+// missized, which the scan gave up on - reaches the launches behind it
+// through device memory (the states, the walk list and its count).
+// Pending streams (two blocks and more by the host's copy) are cut into
+// groups of at most index_build_group_streams streams and kBuildGroupBytes of
+// input - a longer stream is a group of its own - so that the descriptors and
+// the scan's tables are bounded whatever n is; the groups run back to back on
+// the stream and reuse the tables.
+int snapmi_build_block_index(snapmi_ctx *ctx, const void *const *d_in_ptrs,
+                             const uint64_t *d_in_lens,
+                             const uint64_t *h_in_lens,
+                             const uint64_t *h_out_lens, size_t n,
+                             uint64_t *d_index_first, uint64_t *d_index,
+                             uint64_t index_cap, uint8_t *d_status)
+{
+    if (!ctx)
+        return SNAPMI_E_ARGUMENT;
+    if (!d_index_first || n > 0x7FFFFFFFu ||
+        (n && (!d_in_ptrs || !d_in_lens || !h_in_lens || !h_out_lens)))
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "build_block_index: bad args");
+    const uint64_t entries = snapmi_block_index_entries(h_out_lens, n);
+    if (entries > index_cap || (entries && !d_index))
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "build_block_index: the index takes %llu entries, "
+                        "index_cap is %llu",
+                        (unsigned long long)entries,
+                        (unsigned long long)index_cap);
+    if ((uint64_t)n + entries > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "build_block_index: n + entries must stay below 2^31");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ctx->ib_stats_live = false;
+    if (n == 0) {
+        HIP_TRY(ctx, hipMemsetAsync(d_index_first, 0, sizeof(uint64_t), s));
+        return SNAPMI_OK;
+    }
+    // a pending stream longer than this is the walker's: no valid stream is
+    // (a length of 2^32 - 1 compresses to less than 2^33 bytes), and the
+    // scan's plan (plan_streams: fits) holds everything below it
+    constexpr uint64_t kScanMaxLen = 1ull << 36;
+    constexpr uint64_t kBuildGroupBytes = 256ull << 20;
+    const uint32_t route = ctx->index_build_route;
+
+    // ---- the groups of the scan route, planned on the host ----------------
+    struct Group {
+        StreamPlan p;
+        size_t j0; // its first stream in slots / idx
+    };
+    std::vector<StreamSlot> slots;
+    std::vector<uint32_t> idx;
+    std::vector<Group> groups;
+    std::vector<std::vector<uint32_t>> pres;
+    size_t pending = 0;
+    if (route != 1) {
+        size_t j0 = 0;
+        uint64_t bytes = 0;
+        auto flush = [&]() {
+            if (slots.size() == j0)
+                return;
+            const uint32_t mg = (uint32_t)(slots.size() - j0);
+            pres.emplace_back((size_t)kPre * (mg + 1));
+            Group g;
+            g.j0 = j0;
+            g.p = plan_streams(slots.data() + j0, mg, false,
+                               ctx->stream_seg_log2, ctx->stream_scan_segs,
+                               sizeof(StreamArgs), pres.back().data());
+            groups.push_back(g);
+            j0 = slots.size();
+            bytes = 0;
+        };
+        for (size_t i = 0; i < n; i++) {
+            if (h_out_lens[i] <= kBiBlock)
+                continue;
+            pending++;
+            if (h_in_lens[i] > kScanMaxLen)
+                continue;
+            if (slots.size() - j0 >= ctx->index_build_group_streams ||
+                (slots.size() > j0 && bytes + h_in_lens[i] > kBuildGroupBytes))
+                flush();
+            StreamSlot t = {};
+            t.in_len = h_in_lens[i];
+            t.bound = h_out_lens[i];
+            slots.push_back(t);
+            idx.push_back((uint32_t)i);
+            bytes += h_in_lens[i];
+        }
+        flush();
+    } else {
+        for (size_t i = 0; i < n; i++)
+            pending += h_out_lens[i] > kBiBlock;
+    }
+    size_t t_bytes = 0, g_bytes = 0;
+    for (const Group &g : groups) {
+        if (!g.p.fits)
+            return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                            "build_block_index: a stream too long to plan");
+        t_bytes = g.p.t_bytes > t_bytes ? g.p.t_bytes : t_bytes;
+        const size_t b = g.p.desc_bytes + (size_t)g.p.n * sizeof(uint32_t);
+        g_bytes = b > g_bytes ? b : g_bytes;
+    }
+
+    // ---- everything the launches need, before the first of them -----------
+    // device: h_in [n], h_out [n], first [n + 1], walk list [n] (u32),
+    // states [n]
+    const size_t plan_bytes = (3 * n + 1) * sizeof(uint64_t);
+    int rc;
+    if ((rc = reserve(ctx, ctx->ib_meta, plan_bytes + n * 5 + 64)) ||
+        (rc = reserve(ctx, ctx->ib_stat, 64)) ||
+        (groups.size() &&
+         ((rc = reserve(ctx, ctx->sd_tables, t_bytes)) ||
+          (rc = reserve(ctx, ctx->bl_descs, g_bytes + 64)))))
+        return rc;
+    for (hipEvent_t *ev : {&ctx->ev_ib, &ctx->ev_ibg[0], &ctx->ev_ibg[1]})
+        if (!*ev)
+            HIP_TRY(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    // (the staging of an earlier call may still be read by its copy: wait for
+    // that copy's event, not for the stream)
+    auto staging = [&](void **p, size_t *cap, size_t bytes, hipEvent_t ev,
+                       bool *live) -> int {
+        if (*live) {
+            HIP_TRY(ctx, hipEventSynchronize(ev));
+            *live = false;
+        }
+        return pin_reserve(ctx, p, cap, bytes);
+    };
+    if ((rc = staging(&ctx->pin_ib, &ctx->pin_ib_cap, plan_bytes, ctx->ev_ib,
+                      &ctx->ev_ib_live)))
+        return rc;
+    if (groups.size())
+        for (int q = 0; q < 2; q++)
+            if ((rc = pin_reserve(ctx, &ctx->pin_ibg[q], &ctx->pin_ibg_cap[q],
+                                  g_bytes)))
+                return rc;
+
+    // ---- the host's arrays and the prefix sum, to the device --------------
+    uint64_t *const hp = (uint64_t *)ctx->pin_ib;
+    memcpy(hp, h_in_lens, n * sizeof(uint64_t));
+    memcpy(hp + n, h_out_lens, n * sizeof(uint64_t));
+    uint64_t *const hfirst = hp + 2 * n;
+    hfirst[0] = 0;
+    for (size_t i = 0; i < n; i++)
+        hfirst[i + 1] = hfirst[i] + bi_entries(h_out_lens[i]);
+    uint64_t *const dp = (uint64_t *)ctx->ib_meta.p;
+    HIP_TRY(ctx, hipMemcpyAsync(dp, hp, plan_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_index_first, hfirst,
+                                (n + 1) * sizeof(uint64_t),
+                                hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_ib, s));
+    ctx->ev_ib_live = true;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ib_stat.p, 0, 64, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_index, 0, entries * sizeof(uint64_t), s));
+    ctx->ib_stats_live = true;
+
+    BuildArgs x;
+    x.in_ptrs = d_in_ptrs;
+    x.in_lens = d_in_lens;
+    x.h_in = dp;
+    x.h_out = dp + n;
+    x.first = dp + 2 * n;
+    x.index = d_index;
+    x.status = d_status;
+    x.n = (uint32_t)n;
+    x.walk = (uint32_t *)(dp + 3 * n + 1);
+    x.state = (uint8_t *)(x.walk + n);
+    x.stat = (unsigned long long *)ctx->ib_stat.p;
+    x.route = route;
+    x.scan_max_len = kScanMaxLen;
+    hipLaunchKernelGGL(k_index_build_plan, dim3((uint32_t)((n + 255) / 256)),
+                       dim3(256), 0, s, x);
+    LAUNCH_CHECK(k_index_build_plan);
+
+    // ---- the scan route, group by group -----------------------------------
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        const Group &g = groups[gi];
+        const StreamPlan &p = g.p;
+        const uint32_t mg = p.n;
+        const int q = (int)(ctx->ib_groups++ & 1);
+        if (ctx->ev_ibg_live[q]) {
+            HIP_TRY(ctx, hipEventSynchronize(ctx->ev_ibg[q]));
+            ctx->ev_ibg_live[q] = false;
+        }
+        StreamArgs *const descs = (StreamArgs *)ctx->pin_ibg[q];
+        for (uint32_t j = 0; j < mg; j++) {
+            StreamArgs &a = descs[j];
+            const StreamSlot &t = slots[g.j0 + j];
+            memset(&a, 0, sizeof a);
+            a.in = nullptr; // (k_index_build_adopt)
+            a.in_len = t.in_len;
+            // no output exists: stream_head only asks that dlen fits
+            a.out = nullptr;
+            a.out_cap = t.bound;
+            stream_pointers(ctx, p, t, a);
+            a.c_in = nullptr; // no piece descriptors: nothing is decoded
+            a.c_inlen = nullptr;
+            a.c_out = nullptr;
+            a.c_cap = nullptr;
+            a.c_outlen = nullptr;
+            a.c_err = nullptr;
+            a.c_mode = nullptr;
+        }
+        uint8_t *const blk = (uint8_t *)descs;
+        memcpy(blk + p.pre_off, pres[gi].data(),
+               pres[gi].size() * sizeof(uint32_t));
+        memcpy(blk + p.desc_bytes, idx.data() + g.j0, mg * sizeof(uint32_t));
+        const size_t bytes = p.desc_bytes + (size_t)mg * sizeof(uint32_t);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->bl_descs.p, descs, bytes,
+                                    hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_ibg[q], s));
+        ctx->ev_ibg_live[q] = true;
+        HIP_TRY(ctx, hipMemsetAsync((uint8_t *)ctx->sd_tables.p + p.e_off,
+                                    0xFF, p.e_bytes, s));
+        BuildGroup bg;
+        bg.descs = (StreamArgs *)ctx->bl_descs.p;
+        bg.idx = (const uint32_t *)((const uint8_t *)ctx->bl_descs.p +
+                                    p.desc_bytes);
+        bg.mg = mg;
+        hipLaunchKernelGGL(k_index_build_adopt, dim3((mg + 255) / 256),
+                           dim3(256), 0, s, x, bg);
+        LAUNCH_CHECK(k_index_build_adopt);
+        if ((rc = launch_stream_cuts(ctx, p, ctx->bl_descs.p)))
+            return rc;
+        hipLaunchKernelGGL(k_index_build_entries, dim3((mg + 3) / 4),
+                           dim3(256), 0, s, x, bg);
+        LAUNCH_CHECK(k_index_build_entries);
+    }
+
+    // ---- the sequential route: what the list holds by now -----------------
+    if (pending && route != 2) {
+        const size_t cap = (size_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 8;
+        hipLaunchKernelGGL(k_index_walk,
+                           dim3((uint32_t)(pending < cap ? pending : cap)),
+                           dim3(64), 0, s, x);
+        LAUNCH_CHECK(k_index_walk);
     }
     return SNAPMI_OK;
 }

@@ -8,6 +8,9 @@
 //                     given pass the rule (a hint is never trusted: anything
 //                     else is an ordinary stream of the batch launch)
 //   bi_piece          input and output range of piece k of an indexed stream
+//   bi_range_*        the rules of a range read (snapmi_decompress_ranges_indexed)
+//   bi_build          the index of a stream that came without one: the
+//                     sequential definition of snapmi_build_block_index
 //
 // Layout: stream i owns index[first[i], first[i + 1]): blocks + 1 entries,
 // blocks = ceil(len / 64 KiB); entry j is the offset, inside the stream's
@@ -236,6 +239,136 @@ SNAPMI_BI_HD inline BiSpan bi_range_span(uint64_t off, uint64_t len,
     s.to = lo - off;
     s.n = hi - lo;
     return s;
+}
+
+// ---------------------------------------------------------------------
+// Building the index of a stream that came without one
+// (snapmi_build_block_index): a walk from element to element that notes where
+// the chain stands when exactly k * 64 KiB have been produced.  bi_build is
+// the definition; the kernels (the scan's cuts and k_index_walk in
+// snapmi_decompress.hip) must reproduce it.
+//
+// The walk reads tag bytes and literal length bytes only.  Copy offsets are
+// not looked at: the builder finds boundaries, it does not say whether the
+// stream decodes - the decoders distrust every index anyway.
+// ---------------------------------------------------------------------
+constexpr int kBiBuilt = 1;     // SNAPMI_INDEX_BUILT: entries as compress writes them
+constexpr int kBiUnaligned = 2; // ... _UNALIGNED: whole, but an element straddles a boundary
+constexpr int kBiCorrupt = 3;   // ... _CORRUPT: no header, or the chain does not end at (in_len, dlen)
+constexpr int kBiMissized = 4;  // ... _MISSIZED: not the lengths the host's copies said
+
+// hop over the element at p (elem_step of snapmi_decompress.hip, over any
+// source of bytes: at(i) is byte i of the stream); false if it does not fit
+template <class At>
+SNAPMI_BI_HD inline bool bi_elem_step(At &&at, uint64_t in_len, uint64_t &p,
+                                      uint64_t &out)
+{
+    const uint32_t tag = at(p);
+    const uint32_t type = tag & 3;
+    if (type == 0) {
+        const uint32_t n6 = tag >> 2;
+        uint64_t len = n6 + 1, hd = 1;
+        if (n6 >= 60) {
+            const uint32_t nb = n6 - 59;
+            if (p + 1 + nb > in_len)
+                return false;
+            uint32_t v = 0;
+            for (uint32_t k = 0; k < nb; k++)
+                v |= (uint32_t)at(p + 1 + k) << (8 * k);
+            len = (uint64_t)v + 1;
+            hd = 1 + nb;
+        }
+        if (in_len - (p + hd) < len)
+            return false;
+        p += hd + len;
+        out += len;
+    } else {
+        const uint32_t cnb = type == 1 ? 1 : (type == 2 ? 2 : 4);
+        if (p + 1 + cnb > in_len)
+            return false;
+        p += 1 + cnb;
+        out += type == 1 ? 4 + ((tag >> 2) & 7) : 1 + (tag >> 2);
+    }
+    return true;
+}
+
+// The walk of a stream of two blocks and more whose header (hdr bytes) has
+// been read: put(k, p) for every interior k (0 < k < blocks) at which an
+// element starts at p with exactly k * 64 KiB produced, in ascending k.
+// kBiBuilt when the chain is whole - every element fits, it ends at in_len
+// with dlen produced - and every interior k was put; kBiUnaligned when it is
+// whole and an element straddles a boundary; else kBiCorrupt.  (What was put
+// before a verdict other than kBiBuilt is the caller's to take back.)
+template <class At, class Put>
+SNAPMI_BI_HD inline int bi_walk(At &&at, uint64_t in_len, uint32_t hdr,
+                                uint64_t dlen, Put &&put)
+{
+    const uint64_t blocks = bi_blocks(dlen);
+    uint64_t p = hdr, out = 0, k = 1;
+    bool aligned = true;
+    while (p < in_len) {
+        if (k < blocks && out > k * kBiBlock) { // the last element straddled
+            aligned = false;
+            k = (out + kBiBlock - 1) / kBiBlock;
+        }
+        if (k < blocks && out == k * kBiBlock) {
+            if (aligned)
+                put(k, p);
+            k++;
+        }
+        // (out <= dlen < 2^32 here: the sums below cannot wrap)
+        if (!bi_elem_step(at, in_len, p, out) || out > dlen)
+            return kBiCorrupt;
+    }
+    if (p != in_len || out != dlen)
+        return kBiCorrupt;
+    // (every interior boundary lies below dlen: one that was not stood on
+    // was straddled - by the last element, if k is still behind)
+    return aligned && k >= blocks ? kBiBuilt : kBiUnaligned;
+}
+
+// The index of the stream in[0, in_len), which the caller says announces
+// dlen, into e[bi_entries(dlen)].  kBiBuilt: e[] is what
+// snapmi_compress_batch_indexed writes - the varint's length, the offset of
+// the element that starts where exactly k * 64 KiB have been produced for
+// every interior k, in_len.  Any other verdict: all entries 0, which fails
+// both bi_stream_indexed and bi_range_stream_usable - such a stream is
+// decoded whole, and a range on it has no usable index.
+// A stream of at most one block (dlen <= 64 KiB) is not walked: a header that
+// parses gives {hdr, in_len} - which bi_range_stream_usable accepts - and
+// kBiBuilt; dlen == 0 has the one entry {hdr}, and only when in_len == hdr
+// (else kBiCorrupt).
+SNAPMI_BI_HD inline int bi_build(const uint8_t *in, uint64_t in_len,
+                                 uint64_t dlen, uint64_t *e)
+{
+    const uint64_t n = bi_entries(dlen);
+    for (uint64_t j = 0; j < n; j++)
+        e[j] = 0;
+    uint64_t announced = 0;
+    const uint32_t hdr = bi_header(in, in_len, &announced);
+    if (hdr == 0)
+        return kBiCorrupt;
+    if (announced != dlen)
+        return kBiMissized;
+    if (dlen == 0) {
+        if (in_len != hdr)
+            return kBiCorrupt;
+        e[0] = hdr;
+        return kBiBuilt;
+    }
+    if (dlen > kBiBlock) {
+        const int st = bi_walk([in](uint64_t i) { return (uint32_t)in[i]; },
+                               in_len, hdr, dlen,
+                               [e](uint64_t k, uint64_t p) { e[k] = p; });
+        if (st != kBiBuilt) {
+            for (uint64_t j = 0; j < n; j++)
+                e[j] = 0;
+            return st;
+        }
+    }
+    e[0] = hdr;
+    e[n - 1] = in_len;
+    return kBiBuilt;
 }
 
 } // namespace snapmi

@@ -220,6 +220,23 @@ struct snapmi_ctx {
     uint64_t range_scratch_bytes = 1ull << 30;
     uint64_t rg_pieces = 0;
     bool rg_stats_live = false;
+    // snapmi_build_block_index: the device's copies of the host's arrays, the
+    // streams' states and the walk list; its five counters; the pinned staging
+    // of those copies and of one group's descriptors (two slots, taken in
+    // turn), each with the event of the copy that last read it - the call
+    // waits for that event, never for the stream, before it writes there
+    // again; groups so far; whether the last call ran its kernels
+    snapmi::DevBuf ib_meta, ib_stat;
+    void *pin_ib = nullptr, *pin_ibg[2] = {nullptr, nullptr};
+    size_t pin_ib_cap = 0, pin_ibg_cap[2] = {0, 0};
+    hipEvent_t ev_ib = nullptr, ev_ibg[2] = {nullptr, nullptr};
+    bool ev_ib_live = false, ev_ibg_live[2] = {false, false};
+    uint64_t ib_groups = 0;
+    bool ib_stats_live = false;
+    // test options: "index_build_route" (BuildArgs::route) and the most
+    // streams a group of the scan route holds
+    uint32_t index_build_route = 0;
+    uint32_t index_build_group_streams = 4096;
     // segment size of the long-stream scan: 0 = by size (1 KiB under 256 MiB
     // of long streams, 4 KiB from there), 10 / 12 forced (test option)
     uint32_t stream_seg_log2 = 0;

@@ -35,6 +35,9 @@
 //       element boundaries at every 64 KiB of output (cuts), and the pieces
 //       between them through k_decompress_streams3; all long streams of a
 //       small batch in the same launches, a lone stream as a batch of one.
+//   k_index_build_* + k_index_walk   no decode at all: the block index of
+//       streams that came without one (snapmi_build_block_index), from the
+//       same scan's cuts, and by a sequential walk where the scan gives up.
 //
 // DESIGN.md section 4.2 has the history (byte-per-lane kernel of round 1,
 // gone; 354 -> 16 ms at cfg2) and what bounds each of them.
@@ -3219,6 +3222,192 @@ __global__ __launch_bounds__(256) void k_range_finish(RangeArgs x)
         x.r_got[r] = len;
         set_error(x.r_errs, r, SNAPMI_OK, 0, 0, 0);
         atomicAdd(&x.stat[0], 1ull);
+    }
+}
+
+// ---------------------------------------------------------------------
+// snapmi_build_block_index: bi_build (snapmi_blockindex.hpp) for every stream
+// of a batch that came without an index.  The host's copies of the lengths
+// size the index, the scratch and every launch; the device checks them and
+// trusts them for nothing else.
+//   k_index_build_plan     a thread per stream: the caller's length and the
+//       header against the host's copies (MISSIZED), the entries of a stream
+//       of at most one block; a stream of two blocks and more stays pending
+//       (state 0) - or goes straight to the walk list (route 1, or too long
+//       for the scan's plan).  The index is all 0 when it runs.
+//   per group of pending streams: k_index_build_adopt hands the descriptors
+//       the host laid out their input pointers (a stream that is no longer
+//       pending gets an empty input: stream_head leaves it alone with
+//       meta[2] = 1 and no kernel behind it reads a byte), k_bstream_head ..
+//       k_bstream_cuts as for the decoder, and k_index_build_entries (a
+//       wavefront per stream) turns cuts[] into entries: BUILT when every
+//       interior cut stands exactly on its boundary, UNALIGNED when one
+//       stands behind it; a stream the scan gave up on (meta[2] != 0) joins
+//       the walk list.
+//   k_index_walk           a wavefront per listed stream runs bi_walk.  The
+//       list and its count are device memory: the launch reads them, the host
+//       never does.
+// Every writer of entries writes inside [first[i], first[i + 1]) of its own
+// stream, whose count is bi_entries(h_out[i]): what the host sized.
+// ---------------------------------------------------------------------
+namespace {
+__device__ __forceinline__ void build_verdict(const BuildArgs &x, uint32_t i,
+                                              int st)
+{
+    x.state[i] = (uint8_t)st;
+    if (x.status)
+        x.status[i] = (uint8_t)st;
+    atomicAdd(&x.stat[st - 1], 1ull);
+}
+__device__ __forceinline__ void build_to_walker(const BuildArgs &x, uint32_t i)
+{
+    // (at most one entry per stream: the list holds n)
+    const unsigned long long slot = atomicAdd(&x.stat[4], 1ull);
+    x.walk[slot] = i;
+}
+} // namespace
+
+__global__ __launch_bounds__(256) void k_index_build_plan(BuildArgs x)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= x.n)
+        return;
+    const uint32_t i = (uint32_t)t;
+    const uint64_t in_len = x.h_in[i], dlen = x.h_out[i];
+    if (x.in_lens[i] != in_len) {
+        build_verdict(x, i, kBiMissized);
+        return;
+    }
+    const uint8_t *in = (const uint8_t *)x.in_ptrs[i];
+    uint64_t announced = 0;
+    const uint32_t hdr = bi_header(in, in_len, &announced);
+    if (hdr && announced != dlen) {
+        build_verdict(x, i, kBiMissized);
+        return;
+    }
+    if (dlen > kBiBlock) {
+        // (a header that does not parse included: its walk says CORRUPT)
+        x.state[i] = 0;
+        if (x.route == 2 && in_len > x.scan_max_len)
+            build_verdict(x, i, kBiCorrupt); // (no walker under route 2)
+        else if (x.route == 1 || in_len > x.scan_max_len)
+            build_to_walker(x, i);
+        return;
+    }
+    if (hdr == 0 || (dlen == 0 && in_len != hdr)) {
+        build_verdict(x, i, kBiCorrupt);
+        return;
+    }
+    uint64_t *e = x.index + x.first[i];
+    e[0] = hdr;
+    if (dlen)
+        e[1] = in_len;
+    build_verdict(x, i, kBiBuilt);
+}
+
+__global__ __launch_bounds__(256) void k_index_build_adopt(BuildArgs x,
+                                                           BuildGroup g)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= g.mg)
+        return;
+    const uint32_t i = g.idx[j];
+    const bool pending = x.state[i] == 0;
+    g.descs[j].in = pending ? (const uint8_t *)x.in_ptrs[i] : nullptr;
+    if (!pending)
+        g.descs[j].in_len = 0;
+}
+
+// a wavefront per stream of the group
+__global__ __launch_bounds__(256) void k_index_build_entries(BuildArgs x,
+                                                             BuildGroup g)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (j >= g.mg)
+        return;
+    const uint32_t i = g.idx[j];
+    if (x.state[i] != 0)
+        return;
+    const StreamArgs &a = g.descs[j];
+    if (a.meta[2] != 0) { // the scan gave up
+        if (lane == 0) {
+            if (x.route == 2)
+                build_verdict(x, i, kBiCorrupt);
+            else
+                build_to_walker(x, i);
+        }
+        return;
+    }
+    // (stream_head: meta[1] == h_out[i], meta[3] its blocks)
+    const uint64_t K = bi_blocks(x.h_out[i]);
+    bool off = false;
+    for (uint64_t k = 1 + lane; k < K; k += 64)
+        off = off || a.cuts[2 * k + 1] != k * kBiBlock;
+    const bool unaligned = __ballot(off) != 0;
+    if (!unaligned) {
+        uint64_t *e = x.index + x.first[i];
+        for (uint64_t k = 1 + lane; k < K; k += 64)
+            e[k] = a.cuts[2 * k];
+        if (lane == 0) {
+            e[0] = a.meta[0];
+            e[K] = x.h_in[i];
+        }
+    }
+    if (lane == 0)
+        build_verdict(x, i, unaligned ? kBiUnaligned : kBiBuilt);
+}
+
+// ---------------------------------------------------------------------
+// k_index_walk: bi_walk by one wavefront per listed stream, every lane the
+// same walk on wave-uniform values (scalar work; lane 0 stores).  The chain
+// is sequential - a hop needs the tag the hop before it led to - so the
+// wavefront is as fast as one dependent chain.
+// Measured on 256 streams of 1 MiB of text, walker alone (~221 000 hops a
+// stream, profiles/raw_index_build_walker.txt): 67.41 ms hopping through
+// memory, 67.55 ms with the input staged through 1 KiB windows in LDS (64
+// lanes x 16 bytes per refill, ds_read_u8 per hop) - 305 ns a hop either
+// way.  What a hop waits for is not its load (neighbouring tags share a cache
+// line) but the ~70 dependent scalar instructions and ten branches around it,
+// issued by a lone wavefront.  The windows bought nothing and are gone; what
+// would is fewer instructions per hop (k_bstream_scan's table of tags) or
+// its parallel entries, i.e. the scan route, which takes these streams first.
+// ---------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_index_walk(BuildArgs x)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint64_t count = x.stat[4];
+    for (uint64_t w = blockIdx.x; w < count; w += gridDim.x) {
+        const uint32_t i = x.walk[w];
+        const gcptr in = (gcptr)x.in_ptrs[i];
+        const uint64_t in_len = x.h_in[i], dlen = x.h_out[i];
+        uint64_t *e = x.index + x.first[i];
+        const uint64_t cnt = bi_entries(dlen);
+        uint64_t announced = 0;
+        const uint32_t hdr = uni(
+            bi_header((const uint8_t *)x.in_ptrs[i], in_len, &announced));
+        int st = kBiCorrupt;
+        if (hdr != 0 && announced != dlen)
+            st = kBiMissized; // (k_index_build_plan has seen to it)
+        else if (hdr != 0)
+            st = bi_walk([in](uint64_t pos) { return uni(in[pos]); }, in_len,
+                         hdr, dlen, [e, lane](uint64_t k, uint64_t p) {
+                             if (lane == 0)
+                                 e[k] = p;
+                         });
+        if (st == kBiBuilt) {
+            if (lane == 0) {
+                e[0] = hdr;
+                e[cnt - 1] = in_len;
+            }
+        } else {
+            // (what the walk put before it knew)
+            __syncthreads();
+            for (uint64_t k = lane; k < cnt; k += 64)
+                e[k] = 0;
+        }
+        if (lane == 0)
+            build_verdict(x, i, st);
     }
 }
 

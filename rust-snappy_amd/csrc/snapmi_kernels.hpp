@@ -387,6 +387,46 @@ __global__ void k_range_scan_c(RangeArgs x);
 __global__ void k_range_plan(RangeArgs x);
 __global__ void k_range_pieces(RangeArgs x);
 __global__ void k_range_finish(RangeArgs x);
+// snapmi_build_block_index (bi_build of snapmi_blockindex.hpp on the device):
+// the batch, the device's copies of the host's arrays - which size the index
+// and every launch and are trusted for nothing else -, and what the kernels
+// hand each other.
+struct BuildArgs {
+    const void *const *in_ptrs;
+    const uint64_t *in_lens; // the caller's
+    const uint64_t *h_in;    // [n] copies of h_in_lens, h_out_lens
+    const uint64_t *h_out;
+    const uint64_t *first;   // [n + 1] the prefix sum the host made
+    uint64_t *index;         // [first[n]], all 0 when k_index_build_plan runs
+    uint8_t *status;         // [n] or nullptr
+    uint32_t n;
+    // [n]: 0 = a stream of two blocks and more that awaits its walk (scan or
+    // k_index_walk), else its verdict
+    uint8_t *state;
+    // the streams k_index_walk walks, and the counters: [0..3] streams built,
+    // unaligned, corrupt, missized; [4] streams in `walk`
+    uint32_t *walk;
+    unsigned long long *stat;
+    // 0: pending streams are the scan's, those it gives up on the walker's;
+    // 1: all pending streams are the walker's; 2: the scan alone, what it
+    // gives up on is corrupt (test option "index_build_route")
+    uint32_t route;
+    // a pending stream longer than this is the walker's under every route
+    // (the scan's plan does not hold it)
+    uint64_t scan_max_len;
+};
+// one group of pending streams on the scan route: descriptors [mg] (as
+// launch_stream_chain takes them) and the batch's stream of each
+struct BuildGroup {
+    StreamArgs *descs;
+    const uint32_t *idx;
+    uint32_t mg;
+};
+__global__ void k_index_build_plan(BuildArgs x);
+__global__ void k_index_build_adopt(BuildArgs x, BuildGroup g);
+__global__ void k_index_build_entries(BuildArgs x, BuildGroup g);
+__global__ void k_index_walk(BuildArgs x);
+
 // snapmi_compress_batch_indexed: first[], then the entries
 __global__ void k_index_first(const uint64_t *in_lens, uint32_t n,
                               uint64_t *first);

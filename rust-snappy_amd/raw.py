@@ -108,7 +108,9 @@ class Context:
         "token_blocks_spilled", "host_batch_slices", "host_batch_h2d_bytes",
         "host_batch_d2h_bytes", "host_batch_listed_slices",
         "index_streams_pieced", "index_streams_fallback", "range_pieces",
-        "range_ranges_ok", "range_ranges_failed" (include/snapmi.h)."""
+        "range_ranges_ok", "range_ranges_failed", "index_build_built",
+        "index_build_unaligned", "index_build_corrupt",
+        "index_build_missized", "index_build_walked" (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:
@@ -414,6 +416,31 @@ def decompress_ranges_indexed(ctx, in_ptrs, in_lens, index_first, index,
         _ptr(range_len), _u64_array(host_range_off),
         _u64_array(host_range_len), _ptr(range_out), _ptr(range_got),
         _ptr(range_errs), m)
+    if rc:
+        _raise(ctx, rc)
+
+
+INDEX_BUILT, INDEX_UNALIGNED, INDEX_CORRUPT, INDEX_MISSIZED = 1, 2, 3, 4
+
+
+def build_block_index(ctx, in_ptrs, in_lens, host_in_lens, host_out_lens,
+                      index_first, index, status=None, index_cap=None):
+    """snapmi_build_block_index: the block index of streams that came without
+    one, into index_first (int64 CUDA tensor [n + 1]) and index (int64 CUDA
+    tensor of index_cap entries, default its size; block_index_entries(
+    host_out_lens) are needed).  in_ptrs / in_lens: the streams (int64 CUDA
+    tensors); host_in_lens / host_out_lens: the host's copies of in_lens and
+    of the lengths the headers announce, sequences of ints; status: optional
+    uint8 CUDA tensor [n] of INDEX_* verdicts.  Enqueues on the context's
+    stream."""
+    n = in_ptrs.numel() if in_ptrs is not None else 0
+    assert len(host_in_lens) == n and len(host_out_lens) == n
+    if index_cap is None:
+        index_cap = index.numel() if index is not None else 0
+    rc = _lib.of(ctx).snapmi_build_block_index(
+        ctx._h, _ptr(in_ptrs), _ptr(in_lens), _u64_array(host_in_lens),
+        _u64_array(host_out_lens), n, _ptr(index_first), _ptr(index),
+        int(index_cap), _ptr(status))
     if rc:
         _raise(ctx, rc)
 

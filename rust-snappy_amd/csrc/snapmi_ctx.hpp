@@ -1,5 +1,5 @@
 // snapmi_ctx.hpp -- private: the context object and helpers shared by the
-// host-side translation units (snapmi_api.hip, snapmi_frame.hip).
+// host-side translation units.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,9 +13,16 @@
 
 namespace snapmi {
 
-struct DevBuf {
+struct DevBuf { // device scratch (grow-only)
     void *p = nullptr;
     size_t cap = 0;
+    bool listed = false; // in snapmi_ctx::dev_bufs (reserve)
+};
+
+struct PinBuf { // pinned, device-mapped host memory (grow-only)
+    void *p = nullptr;
+    size_t cap = 0;
+    bool listed = false; // in snapmi_ctx::pin_bufs (pin_reserve)
 };
 
 } // namespace snapmi
@@ -28,9 +35,12 @@ struct snapmi_ctx {
     // 256 bytes of pinned, device-mapped host memory: kernels post small
     // results here (no copy-engine round trip behind a bulk copy)
     volatile uint32_t *h_mail = nullptr;
+    // what reserve / pin_reserve have given memory to, each once:
+    // snapmi_ctx_destroy frees these, "scratch_bytes" sums the first
+    std::vector<snapmi::DevBuf *> dev_bufs;
+    std::vector<snapmi::PinBuf *> pin_bufs;
     // pinned host staging of the scalar (host-pointer) entry points
-    void *pin_in = nullptr, *pin_out = nullptr, *pin_desc = nullptr;
-    size_t pin_in_cap = 0, pin_out_cap = 0, pin_desc_cap = 0;
+    snapmi::PinBuf pin_in, pin_out, pin_desc;
     // slices of the host-buffer frame calls: input bytes per encode slice,
     // data chunks per decode slice
     // (measured, profiles/r3_host_pipeline.txt: the match finder's latency
@@ -69,8 +79,8 @@ struct snapmi_ctx {
     snapmi::DevBuf tokens, tok_pages, tok_stage, ntok, lane_tables,
         lane_epochs;
     // lane_tables made of physical chunks (hipMemCreate) mapped into one
-    // address range (place_lane_tables, snapmi_api.hip): the chunks and the
-    // bytes of the range; empty / 0 when lane_tables.p came from hipMalloc
+    // address range (place_lane_tables, snapmi_lanetables.hip): the chunks and
+    // the bytes of the range; empty / 0 when lane_tables.p came from hipMalloc
     std::vector<hipMemGenericAllocationHandle_t> lane_chunks;
     size_t lane_chunk_bytes = 0, lane_va_bytes = 0;
     uint32_t lane_chunk_count = 0, lane_per_chunk = 0; // lane -> table map
@@ -202,9 +212,8 @@ struct snapmi_ctx {
     // staging of the list and of the batch's descriptors
     int batch_long_streams = 1;
     snapmi::DevBuf bl_modes, bl_list, bl_descs, bl_order;
-    void *pin_bl = nullptr;
-    size_t pin_bl_cap = 0;
-    void *pin_bl2 = nullptr; // descriptors of the long streams of a batch
+    snapmi::PinBuf pin_bl;
+    snapmi::PinBuf pin_bl2; // descriptors of the long streams of a batch
     // snapmi_decompress_batch_indexed: the modes of the launch behind, the
     // descriptor list (a slot per stream and per index entry), and the gate /
     // counter words of its kernels
@@ -227,8 +236,7 @@ struct snapmi_ctx {
     // waits for that event, never for the stream, before it writes there
     // again; groups so far; whether the last call ran its kernels
     snapmi::DevBuf ib_meta, ib_stat;
-    void *pin_ib = nullptr, *pin_ibg[2] = {nullptr, nullptr};
-    size_t pin_ib_cap = 0, pin_ibg_cap[2] = {0, 0};
+    snapmi::PinBuf pin_ib, pin_ibg[2];
     hipEvent_t ev_ib = nullptr, ev_ibg[2] = {nullptr, nullptr};
     bool ev_ib_live = false, ev_ibg_live[2] = {false, false};
     uint64_t ib_groups = 0;
@@ -241,7 +249,6 @@ struct snapmi_ctx {
     // of long streams, 4 KiB from there), 10 / 12 forced (test option)
     uint32_t stream_seg_log2 = 0;
     uint32_t stream_scan_segs = 0; // test option: 0 = by size
-    size_t pin_bl2_cap = 0;
     // frame layer scratch (snapmi_frame.hip)
     snapmi::DevBuf fr_tables, fr_desc, fr_meta, fr_scan, fr_slots, fr_chunk_off;
     // snapmi_frame_decompress_batch: per-stream and per-chunk scratch
@@ -262,7 +269,7 @@ struct snapmi_ctx {
     uint32_t lane_waves_per_cu = 6; // 24 KiB of LDS per wave
     uint32_t lane_max_waves = 0;    // test knob: cap on lane-kernel waves (0 = none)
     // placements of the lane tables that are timed before one is kept
-    // (place_lane_tables in snapmi_api.hip: spread over the budget, then
+    // (place_lane_tables in snapmi_lanetables.hip: spread over the budget, then
     // packed behind that, then spread again; a candidate costs one hipMalloc
     // and a 3 ms probe, and the driver wipes what a loser gives back)
     uint32_t lane_table_tries = 2;
@@ -316,6 +323,9 @@ inline int fail_ctx(snapmi_ctx *ctx, int kind, const char *fmt, ...)
 // (slack: an eighth more than asked for, so that batches that grow a little
 // do not reallocate every time - or none, for the token pool, whose size is a
 // stated share of the input)
+// A buffer is listed in the context the first time it is given memory and
+// stays listed, freed or grown: the context's own DevBufs only (a slot of the
+// host pipeline has slot_reserve).
 inline int reserve(snapmi_ctx *ctx, DevBuf &b, size_t bytes,
                    bool slack = true)
 {
@@ -327,40 +337,14 @@ inline int reserve(snapmi_ctx *ctx, DevBuf &b, size_t bytes,
         b.p = nullptr;
         b.cap = 0;
     }
+    if (!b.listed) {
+        ctx->dev_bufs.push_back(&b);
+        b.listed = true;
+    }
     size_t want = bytes + (slack ? bytes / 8 : 0) + 256;
     HIP_TRY(ctx, hipMalloc(&b.p, want));
     b.cap = want;
     return SNAPMI_OK;
 }
 
-} // namespace snapmi
-
-// internal launchers (snapmi_api.hip), shared with the frame layer
-namespace snapmi {
-void host_pipe_destroy(snapmi_ctx *ctx); // snapmi_frame.hip
-// raw compress of n streams; blocks/slots = launch geometry computed from
-// the (host-known) stream lengths
-int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
-                    const uint64_t *d_in_lens, void *const *d_out_ptrs,
-                    const uint64_t *d_out_caps, uint64_t *d_out_lens,
-                    snapmi_error *d_errs, size_t n, uint64_t blocks,
-                    uint64_t slots, uint32_t small_classes = 0xF,
-                    uint64_t cnt8 = 0, uint64_t block_bytes = 0,
-                    // the block index (snapmi_blockindex.hpp), or nullptr
-                    uint64_t *d_index_first = nullptr,
-                    uint64_t *d_index = nullptr, uint64_t index_entries = 0);
-// raw decompress; d_modes optional (1 = stored chunk, plain copy)
-int launch_decompress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
-                      const uint64_t *d_in_lens, void *const *d_out_ptrs,
-                      const uint64_t *d_out_caps, uint64_t *d_out_lens,
-                      snapmi_error *d_errs, const uint8_t *d_modes, size_t n,
-                      const unsigned long long *d_gate = nullptr,
-                      unsigned long long gate_value = 0,
-                      // a launch beside the context's stream: its stream and
-                      // its own dispatch-order scratch (no timing events)
-                      hipStream_t side = nullptr, DevBuf *side_order = nullptr,
-                      // no stream of the launch is of the lane-per-stream
-                      // classes (under 512 bytes of output): their kernels
-                      // are not launched
-                      bool wide_only = false);
 } // namespace snapmi

@@ -14,15 +14,11 @@
 #pragma once
 
 #include "snapmi_ctx.hpp"
+#include "snapmi_launch.hpp" // the launchers the frame layer calls
 
 namespace snapmi {
 
 constexpr int kSlots = 3;
-
-struct PinBuf { // pinned, device-mapped host memory (grow-only)
-    void *p = nullptr;
-    size_t cap = 0;
-};
 
 struct PipeSlot {
     DevBuf in, out, desc; // desc: u64 len | snapmi_error | index...

@@ -1,7 +1,7 @@
 // snapmi - the host's arithmetic of the token path: how a batch's blocks are
 // cut into launches and how many pages its token pool gets.  Plain functions
 // of numbers (no HIP), so that tests/test_pool_cpu.py can check them on the
-// CPU; snapmi_api.hip is their only user in the library.
+// CPU; snapmi_launch.hip is their only user in the library.
 #pragma once
 #include <cstdint>
 
@@ -9,7 +9,7 @@ namespace snapmi {
 
 // tokens per page, exceptions per page, and the most pages a block can fill
 // (snapmi_kernels.hpp has the same numbers for the device; a static_assert in
-// snapmi_api.hip ties them)
+// snapmi_launch.hip ties them)
 constexpr uint32_t kPoolTokPage = 512, kPoolExcPage = 256;
 constexpr uint32_t kPoolPagesPerBlock = 33 + 4;
 

@@ -2,12 +2,15 @@
 // pieces: the k_bstream_* kernels) for one raw stream or the long streams of
 // a small batch: geometry, workgroups, and where every table and descriptor
 // lies in the scratch.  Plain functions, no HIP, so that
-// tests/test_streamplan_cpu.py can pin them on the CPU.  snapmi_api.hip
-// (snapmi_decompress_stream, decompress_batch_long) is the only user in the
-// library; the kernels see the constants through snapmi_kernels.hpp.
+// tests/test_streamplan_cpu.py can pin them on the CPU.  Its users in the
+// library: snapmi_longstream.hip (snapmi_decompress_stream,
+// decompress_batch_long) and snapmi_index.hip (snapmi_build_block_index); the
+// kernels see the constants through snapmi_kernels.hpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+
+#include "snapmi_piecelist.hpp"
 
 namespace snapmi {
 
@@ -33,7 +36,6 @@ constexpr uint32_t kScanFill = 1024;
 constexpr uint32_t kStreamChunk = 65536;  // output bytes per piece: the
                                           // encoders' block size, so pieces
                                           // of their streams are independent
-constexpr size_t kStreamErrBytes = 32;    // sizeof(snapmi_error)
 
 // Segment size of the scan of long streams (k_bstream_scan and the levels
 // above it): 4 KiB when there is enough of them to fill the chip with walks
@@ -110,6 +112,7 @@ struct StreamPlan {
     // 0xFF fill of e_bytes from e_off), then per stream s1, s2, s3, cuts
     size_t e_off, e_bytes, t_bytes;
     // sd_desc: the piece descriptors of all streams, an array per field
+    // (snapmi_piecelist.hpp)
     size_t pieces;
     size_t c_in, c_inlen, c_out, c_cap, c_outlen, c_err, c_mode, d_bytes;
     // descriptor block: n descriptors of desc_size bytes, then the prefixes
@@ -189,15 +192,15 @@ inline StreamPlan plan_streams(StreamSlot *slot, uint32_t n, bool lone,
         pre[k * st + n] = p.grid[k];
     p.t_bytes = t + 64;
 
-    const size_t P = p.pieces;
-    p.c_in = 0;
-    p.c_inlen = P * 8;
-    p.c_out = P * 16;
-    p.c_cap = P * 24;
-    p.c_outlen = P * 32;
-    p.c_err = P * 40;
-    p.c_mode = P * (40 + kStreamErrBytes);
-    p.d_bytes = P * (40 + kStreamErrBytes + 1) + 64;
+    const PieceOffsets o = piece_offsets(p.pieces);
+    p.c_in = o.c_in;
+    p.c_inlen = o.c_inlen;
+    p.c_out = o.c_out;
+    p.c_cap = o.c_cap;
+    p.c_outlen = o.c_outlen;
+    p.c_err = o.c_err;
+    p.c_mode = o.c_mode;
+    p.d_bytes = o.total;
 
     p.pre_off = (size_t)n * desc_size;
     p.desc_bytes = p.pre_off + (size_t)kPre * st * sizeof(uint32_t);

@@ -141,7 +141,7 @@ def test_combined_calls_give_every_caller_the_oracles_bytes(built):
 @pytest.mark.parametrize("lib", ["test", "product"])
 def test_single_launch_path_of_small_calls(built, lib):
     """A lone snappy_compress / snappy_uncompress of under 256 bytes runs as
-    ONE kernel over pinned host memory (seam_tiny, snapmi_api.hip): every
+    ONE kernel over pinned host memory (seam_tiny, snapmi_seam.hip): every
     input length 1..255 over three alphabets compresses to the oracle's bytes
     and comes back; every small error KAT of the reference's decoder
     (test/tests.rs:345-466) is refused with SNAPPY_INVALID_INPUT; a short

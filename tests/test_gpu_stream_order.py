@@ -551,6 +551,110 @@ def test_pipelined_decompress_stream(request, ctx):
         pipe.close()
 
 
+def test_scratch_bytes_counts_every_call_and_contexts_close(built):
+    """"scratch_bytes" sums what the context has given memory to, and
+    snapmi_ctx_destroy frees exactly that.  On a fresh context, one call each
+    of indexed decode, range reads, the device index build and a batch with a
+    long stream: after each the figure has risen by at least what the call
+    must hold, from the shapes alone -
+      indexed decode  T * 73 + E * 4: a descriptor slot (40 + 32 + 1 bytes)
+                      per stream and per index entry, an owner word per entry;
+      range reads     a 64 KiB room per cut block of a range;
+      index build     (3n + 1) * 8 + 5n: the lengths both ways and first[],
+                      the walk list and the states;
+      long stream     2n modes, and a descriptor slot for each of the long
+                      stream's dlen / 64 KiB + 2 pieces.
+    Every result against the oracle; then the context closes, and two more
+    are made and closed."""
+    import indexbuild_ref as IB
+    import long_streams as LS
+    import rangeindex_ref as RR
+    import rust_snappy_amd as R
+    from rust_snappy_amd import raw
+    datas = [data("text", 3 * 65536, salt) for salt in (1, 2, 3)]
+    n = len(datas)
+    batch = DBatch([comp(d)[0] for d in datas], [len(d) for d in datas],
+                   [comp(d)[1] for d in datas])
+    E, T = batch.entries, n + batch.entries
+    assert E == 4 * n and batch.passing() == [0, 1, 2]
+    c = R.raw.Context(0)
+    try:
+        trace = [c.info("scratch_bytes")]
+        # ---- indexed decode
+        u = DBufs(batch, 31)
+        torch.cuda.synchronize()
+        u.enqueue(c)
+        c.synchronize()
+        trace.append(c.info("scratch_bytes"))
+        u.check("indexed decode")
+        assert c.info("index_streams_pieced") == n
+        assert trace[1] - trace[0] >= T * 73 + E * 4, trace
+
+        # ---- range reads: both edges of every range inside a block
+        ranges = [(0, 100, 70000), (1, 65537, 131070), (2, 65535, 65538)]
+        offs, lens = [r[1] for r in ranges], [r[2] for r in ranges]
+        rooms = sum(RR.edges(o, ln) for o, ln in zip(offs, lens))
+        assert rooms == 2 * len(ranges)
+        out = Slab(lens, 32)
+        got = torch.full((3,), -7, dtype=torch.int64, device="cuda")
+        rerrs = torch.full((96,), 0x77, dtype=torch.uint8, device="cuda")
+        d_stream = torch.tensor([r[0] for r in ranges],
+                                dtype=torch.int32).cuda()
+        d_off, d_len = u64(offs), u64(lens)
+        torch.cuda.synchronize()
+        raw.decompress_ranges_indexed(c, u.src.d_ptrs, u.in_lens, u.first,
+                                      u.index, d_stream, d_off, d_len, offs,
+                                      lens, out.d_ptrs, got, rerrs,
+                                      index_entries=E)
+        c.synchronize()
+        trace.append(c.info("scratch_bytes"))
+        out.assert_guards("range reads")
+        assert got.cpu().tolist() == lens and read_errs(rerrs) == [OK] * 3
+        for i, (s, o, ln) in enumerate(ranges):
+            assert out.bytes(i, ln) == datas[s][o:o + ln], i
+        assert c.info("range_ranges_ok") == 3
+        assert trace[2] - trace[1] >= rooms * 65536, trace
+
+        # ---- the index of the same streams, built on the device
+        h_in, h_out = [len(s) for s in batch.comps], batch.caps
+        first = torch.full((n + 1,), -7, dtype=torch.int64, device="cuda")
+        index = torch.full((E,), -7, dtype=torch.int64, device="cuda")
+        status = torch.full((n,), 0x77, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        raw.build_block_index(c, u.src.d_ptrs, u.in_lens, h_in, h_out, first,
+                              index, status)
+        c.synchronize()
+        trace.append(c.info("scratch_bytes"))
+        want = [IB.build(s, d) for s, d in zip(batch.comps, batch.caps)]
+        assert status.cpu().tolist() == [w[0] for w in want] == [IB.BUILT] * n
+        assert first.cpu().tolist() == batch.first
+        assert index.cpu().tolist() == batch.flat == \
+            [e for w in want for e in w[1]]
+        assert trace[3] - trace[2] >= (3 * n + 1) * 8 + 5 * n, trace
+
+        # ---- a small batch with one long stream (200 KiB of text)
+        st = LS.mixed(20261019, 3, {"text": 1}, tail_len=8192)
+        assert st.dlen == 200 << 10
+        assert LS.long_stream_rule(st.in_len, st.dlen)
+        shorts = [comp(data("text", k, 4))[0] for k in (300, 4096, 8193)]
+        lb = DBatch([st.bytes()] + shorts, [st.dlen, 300, 4096, 8193])
+        assert lb.want[0][2] == st.expected()
+        v = DBufs(lb, 33)
+        torch.cuda.synchronize()
+        v.enqueue(c)
+        c.synchronize()
+        trace.append(c.info("scratch_bytes"))
+        v.check("long stream in a batch")
+        pieces = st.dlen // 65536 + 2
+        assert trace[4] - trace[3] >= 2 * len(lb.comps) + pieces * 73, trace
+    finally:
+        c.close()
+    for _ in range(2):
+        again = R.raw.Context(0)
+        assert again.info("scratch_bytes") == trace[0]  # (the ticket alone)
+        again.close()
+
+
 # ------------------------------------------------ 4. the caller's stream
 def make_context(library, stream):
     import rust_snappy_amd as R

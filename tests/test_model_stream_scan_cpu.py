@@ -15,7 +15,7 @@ import oracle_lib as O
 
 # (segment bytes, segments per scan wavefront): what a 2 GiB stream gets, what
 # the streams of a small call get (stream_seg_log2 / stream_scan_segs in
-# snapmi_api.hip), and sizes in between
+# snapmi_streamplan.hpp), and sizes in between
 GEOMETRIES = [(4096, 64), (1024, 64), (1024, 16), (1024, 8), (4096, 32)]
 
 

@@ -1478,6 +1478,145 @@ def raw_ranges(args, ctx, dev):
     return res
 
 
+def raw_writes(args, ctx, dev):
+    """Range writes through the block index (snapmi_write_ranges_indexed) on
+    256 streams of 1 MiB of text with the index compress wrote: one 4 KiB
+    write per stream, one aligned 64 KiB block per stream, sixteen 4 KiB
+    writes per stream (every block touched) - each beside the whole-stream
+    way to the same edit: snapmi_decompress_batch_indexed of the streams, a
+    device copy of the new bytes into the output, and
+    snapmi_compress_batch_indexed of the result; in this process on one
+    context, five alternating repeats of --steps calls each (medians, and the
+    spread max - min over the repeats).  Writes profiles/raw_writes.json
+    (--sets 4k,16x4k:write,...: only these shapes, only that way - for a
+    kernel trace; nothing is written)."""
+    import random
+    import statistics
+    import oracle_lib as O
+    from rust_snappy_amd import batch, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+    n, size = 256, 1 << 20
+    datas = []
+    for _ in range(n):
+        o = rng.randrange(len(text) - size)
+        datas.append(text[o:o + size])
+    src = batch.StreamBatch.from_bytes(datas, dev)
+    comp, first, index = batch.compress(ctx, src, want_index=True)
+    entries = index.numel()
+    h_size = torch.full((n,), size, dtype=torch.int64)
+    # the whole-stream way's buffers: the decoded streams, the streams
+    # compressed again, their index
+    back = batch.StreamBatch.empty([size] * n, dev)
+    blens = torch.zeros(n, dtype=torch.int64, device=dev)
+    berrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+    cap = raw.max_compress_len(size)
+    again = batch.StreamBatch.empty([cap] * n, dev)
+    alens = torch.zeros(n, dtype=torch.int64, device=dev)
+    afirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    aindex = torch.zeros(entries, dtype=torch.int64, device=dev)
+    # the write way's buffers
+    out = batch.StreamBatch.empty([cap] * n, dev)
+    olens = torch.zeros(n, dtype=torch.int64, device=dev)
+    oerrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+    oindex = torch.zeros(entries, dtype=torch.int64, device=dev)
+    shapes = {
+        "4k": [(i, rng.randrange(size - 4096), 4096) for i in range(n)],
+        "block_64k": [(i, 65536 * rng.randrange(16), 65536)
+                      for i in range(n)],
+        "16x4k": [(i, 65536 * k + rng.randrange(65536 - 4096), 4096)
+                  for i in range(n) for k in range(16)]}
+    # (--sets 4k:write / 4k:whole - for a kernel trace of one way to one
+    # shape; no record is written)
+    ways = ("write", "whole")
+    if args.sets:
+        picked = [x.partition(":") for x in args.sets.split(",")]
+        shapes = {k: v for k, v in shapes.items()
+                  if k in [x[0] for x in picked]}
+        ways = tuple(w for w in ways
+                     if any(x[2] in ("", w) for x in picked))
+    repeats = 5
+    res = {"config": "raw_writes: range writes through the block index vs "
+                     "decode whole + copy + compress whole of the same 256 "
+                     "streams of 1 MiB of text",
+           "steps": args.steps, "repeats": repeats, "streams": n,
+           "bytes": n * size, "index_entries": entries}
+    timers = {}
+    for key, writes in shapes.items():
+        m = len(writes)
+        # new bytes: text from elsewhere, one slab, a source per write
+        news = []
+        for _, _, ln in writes:
+            o = rng.randrange(len(text) - ln)
+            news.append(text[o:o + ln])
+        wsrc = batch.StreamBatch.from_bytes(news, dev)
+        w_stream = [w[0] for w in writes]
+        w_off, w_len = [w[1] for w in writes], [w[2] for w in writes]
+        w_ptrs = [int(p) for p in wsrc.d_ptrs.cpu().tolist()]
+        # (the whole-stream way's copy: one index_copy_ of all new bytes)
+        new_flat = torch.from_numpy(
+            np.frombuffer(b"".join(news), dtype=np.uint8).copy()).to(dev)
+        new_at = torch.cat([torch.arange(ln, dtype=torch.int64)
+                            + (int(back.offsets[s]) + o)
+                            for s, o, ln in writes]).to(dev)
+        side = torch.cuda.ExternalStream(ctx.stream) if ctx.stream \
+            else torch.cuda.default_stream(dev)
+
+        def write(w_stream=w_stream, w_off=w_off, w_len=w_len,
+                  w_ptrs=w_ptrs):
+            raw.write_ranges_indexed(
+                ctx, comp.d_ptrs, comp.d_lens, first, index, w_stream, w_off,
+                w_len, w_ptrs, out.d_ptrs, out.d_lens, olens, oerrs, oindex,
+                index_entries=entries)
+
+        def whole(new_flat=new_flat, new_at=new_at):
+            raw.decompress_batch(ctx, comp.d_ptrs, comp.d_lens, back.d_ptrs,
+                                 back.d_lens, blens, berrs, index_first=first,
+                                 index=index, index_entries=entries)
+            with torch.cuda.stream(side):  # (the context's stream)
+                back.data.index_copy_(0, new_at, new_flat)
+            raw.compress_batch(ctx, back.d_ptrs, back.d_lens, again.d_ptrs,
+                               again.d_lens, alens, None, host_in_lens=h_size,
+                               index_first=afirst, index=aindex,
+                               index_cap=entries)
+        write()
+        whole()
+        ctx.synchronize()
+        torch.cuda.synchronize()
+        assert all(e[0] == 0 for e in batch.read_errors(oerrs))
+        # both ways give the same streams and the same index
+        assert torch.equal(olens, alens) and torch.equal(oindex, aindex)
+        for i in (0, n // 2, n - 1):
+            assert out.stream_bytes(i, int(olens[i])) == \
+                again.stream_bytes(i, int(alens[i]))
+        res[key] = {"writes": m, "bytes": sum(w_len),
+                    "write_blocks": ctx.info("write_blocks"),
+                    "write_blocks_decoded": ctx.info("write_blocks_decoded")}
+        if "write" in ways:
+            timers["write_" + key] = (lambda write=write:
+                                      time_it(write, args.steps, ctx))
+        if "whole" in ways:
+            timers["whole_" + key] = (lambda whole=whole:
+                                      time_it(whole, args.steps, ctx))
+    t = {k: [] for k in timers}
+    for _ in range(repeats):
+        for k, fn in timers.items():
+            t[k].append(fn() * 1e3)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    res["ms_median"] = {k: round(v, 4) for k, v in med.items()}
+    res["ms_spread"] = {k: round(max(v) - min(v), 4) for k, v in t.items()}
+    res["ms_repeats"] = {k: [round(x, 4) for x in v] for k, v in t.items()}
+    if not args.sets:
+        for key in shapes:
+            res[key]["over_whole"] = round(
+                med["write_" + key] / med["whole_" + key], 3)
+        (ROOT / "profiles" / "raw_writes.json").write_text(
+            json.dumps(res) + "\n")
+    return res
+
+
 class HostArena:
     """buffers of the given sizes, 64 bytes apart at least, in one
     pageable array or one snapmi_host_alloc allocation"""
@@ -1868,7 +2007,8 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--sets", default="",
                     help="frames_host_batch: only these data sets (a,b,...); "
-                         "raw_ranges: only these shapes, nothing recorded")
+                         "raw_ranges, raw_writes: only these shapes, nothing "
+                         "recorded")
     ap.add_argument("--plan", default="",
                     help="name:gib,... - run these configs at these sizes, "
                          "one JSON line each with a \"name\" key; a config "
@@ -1896,7 +2036,8 @@ def main():
              "tiny": tiny, "sweep": sweep, "budget": budget, "seam": seam,
              "frames_batch": frames_batch, "host_batch": host_batch,
              "frames_host_batch": frames_host_batch, "raw_index": raw_index,
-             "raw_ranges": raw_ranges, "raw_index_build": raw_index_build}
+             "raw_ranges": raw_ranges, "raw_index_build": raw_index_build,
+             "raw_writes": raw_writes}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -1920,14 +2061,16 @@ def main():
                      ("frames_host_batch", frames_host_batch),
                      ("raw_index", raw_index),
                      ("raw_ranges", raw_ranges),
-                     ("raw_index_build", raw_index_build)):
+                     ("raw_index_build", raw_index_build),
+                     ("raw_writes", raw_writes)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
                                                          "frames_host_batch",
                                                          "raw_index",
                                                          "raw_ranges",
-                                                         "raw_index_build")):
+                                                         "raw_index_build",
+                                                         "raw_writes")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

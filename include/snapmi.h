@@ -272,6 +272,11 @@ SNAPMI_API const char *snapmi_version(void);
  *                          may hold for the edge blocks of its ranges at once
  *                          (default 1 GiB, at least 128 KiB; a bound on
  *                          memory, not a tuned number)
+ *   "write_scratch_bytes"  bytes of compress slots (76 496 a touched block) and
+ *                          64 KiB rooms (one an edge block)
+ *                          snapmi_write_ranges_indexed may hold at once
+ *                          (default 1 GiB, at least 142 032: one block's slot
+ *                          and room; a bound on memory, not a tuned number)
  * The knobs of the test suite and of the experiment drivers are declared in
  * snapmi_test.h (snapmi_ctx_set_test_option).
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
@@ -330,6 +335,12 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *                           (snapmi_range_pieces of the host's copies), and
  *   "range_ranges_ok" / "range_ranges_failed"  ranges of it that succeeded /
  *                           failed (these two wait for the call)
+ *   "write_blocks"          blocks the writes of the last
+ *                           snapmi_write_ranges_indexed touched
+ *                           (snapmi_write_blocks of its lists),
+ *   "write_blocks_decoded"  the edge blocks among them, which were decoded, and
+ *   "write_streams_ok" / "write_streams_failed"  touched streams of it that
+ *                           succeeded / failed (these two wait for the call)
  *   "index_build_built" / "index_build_unaligned" / "index_build_corrupt" /
  *   "index_build_missized"  streams of the last snapmi_build_block_index by
  *                           verdict, and
@@ -621,6 +632,101 @@ SNAPMI_API int snapmi_decompress_ranges_indexed(
     const uint64_t *h_range_len /* host copies */, void *const *d_range_out,
     uint64_t *d_range_got, snapmi_error *d_range_errs /* may be NULL */,
     size_t m);
+
+/*
+ * Range WRITES through the block index: bytes [off, off + len) of a stream's
+ * OUTPUT are replaced, and only the 64 KiB blocks the writes touch go through
+ * the codec.  Every encoder the index serves compresses each block on its
+ * own, so the compressed bytes of a block no write touches stay valid byte
+ * for byte: they are copied.
+ *
+ * snapmi_write_blocks: blocks the writes touch - a block that two
+ * neighbouring writes of a stream share counts once; a write of len == 0, or
+ * whose end passes 2^64, touches none; the sum saturates at 2^64 - 1.  Host
+ * code.
+ *
+ * snapmi_write_ranges_indexed: write w puts h_write_src[w][0, len) (DEVICE
+ * memory) at output bytes [off, off + len) of stream s = h_write_stream[w] of
+ * the n streams (d_in_ptrs, d_in_lens) with the index (d_index_first, d_index,
+ * index_entries).  A stream's length does not change, so neither does the
+ * number of its entries: d_new_index is laid out by d_index_first.
+ * The write lists are HOST arrays, read before the call returns; the device
+ * gets the host's own copy of them.  What the device distrusts is the
+ * streams, d_in_lens, d_index_first and the index.
+ *   Host checks (SNAPMI_E_ARGUMENT with snapmi_last_error; nothing is
+ *     enqueued, nothing written): a NULL pointer other than d_errs; writes not
+ *     sorted by (stream, off), or overlapping; stream >= n; off + len wraps;
+ *     m, or n + index_entries + snapmi_write_blocks(...), not below 2^31.  A
+ *     write of len == 0 is ignored altogether; m == 0, or every write empty,
+ *     enqueues nothing.
+ *   Touched blocks.  A block one write covers entirely - [k * 65536,
+ *     (k + 1) * 65536) lies inside it - is COVERED and compressed straight
+ *     from the write's bytes.  Any other touched block is an EDGE block: its
+ *     piece (see the range reads) is decoded into a 64 KiB room of scratch,
+ *     the writes' bytes are laid over it, and it is compressed from there.
+ *     Told from the writes alone: a stream's short last block is an edge
+ *     block unless the write ends on a multiple of 65536.
+ *   A stream no write names: nothing of d_out_ptrs[i] is written,
+ *     d_out_lens[i] = 0 and the error kind is 0 - no valid stream has 0
+ *     bytes, so 0 with OK means "keep the old one".  Its entries are copied.
+ *   A stream that succeeds: d_out_ptrs[i][0, d_out_lens[i]) is varint(dlen)
+ *     followed, for every block k, by what the compressor gives the patched
+ *     block (without a varint) when k is touched and by the old bytes
+ *     [entry k, entry k + 1) when it is not; the new entries are the varint's
+ *     length and the running sums.  Exactly [0, d_out_lens[i]) is written.
+ *     For a stream whose blocks are self-contained this is, bit for bit,
+ *     snapmi_compress_batch_indexed of the patched data.  Untouched blocks
+ *     are neither read as elements nor judged: for a foreign stream whose
+ *     untouched block copies from across its boundary, the result decodes to
+ *     whatever those bytes now decode to.
+ *   A stream that fails: d_out_lens[i] = 0, NOT ONE BYTE of its buffer is
+ *     written, and its old entries are copied to d_new_index - the new index
+ *     stays right for the stream the caller keeps.  Why, in this order:
+ *       the header does not parse      the error snapmi_decompress_len_batch
+ *                                      gives the stream
+ *       off + len > dlen               SNAPMI_E_ARGUMENT {off, len, dlen} of
+ *                                      the first such write
+ *       no usable index                the stream's rule of the range reads
+ *         (SNAPMI_E_ARGUMENT {s, 0}), and entry k < entry k + 1 <= compressed
+ *         length for EVERY block - each one is copied or replaced -
+ *         (SNAPMI_E_ARGUMENT {s, first bad block})
+ *       an edge block's piece fails or is not full   that piece's error as
+ *         snapmi_decompress_ranges_indexed reports it, for the first such
+ *         piece in block order
+ *       cap < new length               SNAPMI_BUFFER_TOO_SMALL {cap, new
+ *                                      length}; an exact cap passes
+ *   Whatever the streams, d_in_lens, d_index_first and the index hold,
+ *   nothing is written outside d_out_ptrs[i][0, cap_i), d_out_lens[0, n),
+ *   d_errs[0, n) and d_new_index[0, index_entries), no input byte at or
+ *   behind d_in_lens[i] and no entry at or behind index_entries is read.  If
+ *   d_index_first is not a prefix sum the entries of d_new_index are
+ *   unspecified, and each stream's own result still stands by its own rule.
+ * Outputs (the buffers, d_out_lens, d_errs, d_new_index) must not overlap the
+ * inputs, the old index or the writes' sources.
+ * Everything runs on the context's stream.  The host waits only for scratch
+ * that must grow, or for the event of its own earlier staging copy; capture
+ * into a hipGraph is not promised.  Scratch per touched block: a compress
+ * slot, and a room for an edge block; option "write_scratch_bytes" caps what
+ * is alive at once - the host cuts the touched streams into consecutive
+ * groups of whole streams that fit (a stream that exceeds it alone is a group
+ * of its own), the groups run back to back and reuse the scratch.  Info
+ * "write_blocks", "write_blocks_decoded", "write_streams_ok" and
+ * "write_streams_failed" describe the last call; reading the last two waits
+ * for it.
+ */
+SNAPMI_API uint64_t snapmi_write_blocks(const uint32_t *h_write_stream,
+                                        const uint64_t *h_write_off,
+                                        const uint64_t *h_write_len, size_t m);
+SNAPMI_API int snapmi_write_ranges_indexed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    size_t n, const uint64_t *d_index_first /* [n+1] */,
+    const uint64_t *d_index, uint64_t index_entries,
+    const uint32_t *h_write_stream, const uint64_t *h_write_off,
+    const uint64_t *h_write_len,
+    const void *const *h_write_src /* HOST array of DEVICE pointers */,
+    size_t m, void *const *d_out_ptrs, const uint64_t *d_out_caps,
+    uint64_t *d_out_lens, snapmi_error *d_errs /* may be NULL */,
+    uint64_t *d_new_index /* out, [index_entries] */);
 
 /*
  * The block index of streams that came WITHOUT one - written by the

@@ -81,6 +81,10 @@ SYMBOLS = [
     ("snapmi_decompress_ranges_indexed", C.c_int,
      [_P, _P, _P, _SZ, _P, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P,
       _SZ]),
+    ("snapmi_write_blocks", C.c_uint64, [_P, _P, _P, _SZ]),
+    ("snapmi_write_ranges_indexed", C.c_int,
+     [_P, _P, _P, _SZ, _P, _P, C.c_uint64, _P, _P, _P, _P, _SZ, _P, _P, _P,
+      _P, _P]),
     ("snapmi_build_block_index", C.c_int,
      [_P, _P, _P, _P, _P, _SZ, _P, _P, C.c_uint64, _P]),
     ("snapmi_decompress_len_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),

@@ -203,3 +203,57 @@ def read_ranges(ctx, src: StreamBatch, index, ranges):
     got = got.cpu().numpy()
     return ([dst.stream_bytes(r, got[r]) for r in range(m)],
             read_errors(errs))
+
+
+def write_ranges(ctx, src: StreamBatch, index, writes):
+    """Range writes of compressed streams: writes is a list of (stream, off,
+    bytes) into the streams' OUTPUT, sorted by (stream, off) and not
+    overlapping; index the (index_first, index) pair of the streams.  Only the
+    64 KiB blocks a write touches are decoded and compressed again, every
+    other block's compressed bytes are copied (snapmi_write_ranges_indexed).
+    Returns (the new StreamBatch - a stream no write names, or whose writes
+    failed, is the old one -, the new (index_first, index) pair, per-stream
+    errors as (kind, a, b, c))."""
+    dev = src.data.device
+    index_first, index_tensor = index
+    writes = [(int(s), int(o), bytes(b)) for s, o, b in writes]
+    if not any(len(b) for _, _, b in writes):
+        return src, index, [(0, 0, 0, 0)] * src.n
+    data = StreamBatch.from_bytes([b for _, _, b in writes], dev)
+    # a touched stream grows by at most what its touched blocks can: room for
+    # the worst case of each
+    touched = {}
+    for s, o, b in writes:
+        if b:
+            touched.setdefault(s, set()).update(
+                range(o // 65536, (o + len(b) - 1) // 65536 + 1))
+    caps = [int(src.lens[i]) + 5 + len(touched[i]) *
+            raw.max_compress_len(65536) if i in touched else 0
+            for i in range(src.n)]
+    dst = StreamBatch.empty(caps, dev)
+    out_lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+    errs = torch.zeros(32 * src.n, dtype=torch.uint8, device=dev)
+    new_index = torch.zeros_like(index_tensor)
+    raw.write_ranges_indexed(
+        ctx, src.d_ptrs, src.d_lens, index_first, index_tensor,
+        [w[0] for w in writes], [w[1] for w in writes],
+        [len(w[2]) for w in writes],
+        [int(p) for p in data.d_ptrs.cpu().tolist()], dst.d_ptrs, dst.d_lens,
+        out_lens, errs, new_index, index_entries=index_tensor.numel())
+    ctx.synchronize()
+    out_lens = out_lens.cpu().numpy()
+    # one slab of the streams to keep and the new ones
+    offs, lens, parts, pos = [], [], [], 0
+    for i in range(src.n):
+        from_, n = (dst, int(out_lens[i])) if out_lens[i] else \
+            (src, int(src.lens[i]))
+        o = int(from_.offsets[i])
+        parts.append(from_.data[o:o + n])
+        offs.append(pos)
+        lens.append(n)
+        pos += _align(max(n, 1))
+        pad = pos - offs[-1] - n
+        if pad:
+            parts.append(torch.zeros(pad, dtype=torch.uint8, device=dev))
+    merged = StreamBatch(torch.cat(parts), offs, lens)
+    return merged, (index_first, new_index), read_errors(errs)

@@ -254,7 +254,8 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
     for (DevBuf *b : ctx->dev_bufs)
         if (b->p)
             (void)hipFree(b->p);
-    for (hipEvent_t ev : {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1]})
+    for (hipEvent_t ev :
+         {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1], ctx->ev_wr})
         if (ev)
             (void)hipEventDestroy(ev);
     for (auto &ev : ctx->ev)
@@ -364,6 +365,10 @@ int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
         ctx->host_batch_slice = (uint64_t)value;
     else if (strcmp(name, "range_scratch_bytes") == 0 && value >= (128 << 10))
         ctx->range_scratch_bytes = (uint64_t)value;
+    // (the floor: one block's compress slot and its room)
+    else if (strcmp(name, "write_scratch_bytes") == 0 &&
+             value >= (int64_t)(kSlotBytes + kMaxBlock))
+        ctx->write_scratch_bytes = (uint64_t)value;
     else if (strcmp(name, "decode_kernel") == 0 &&
              (value == 0 || (value == 2 && kDec2) || value == 3))
         ctx->decode_kernel = ctx->lds_store_order_ok ? (int)value : 0;
@@ -681,6 +686,21 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                                    hipMemcpyDeviceToHost));
         }
         *value = (int64_t)(name[13] == 'o' ? w[0] : w[1]);
+    } else if (strcmp(name, "write_blocks") == 0) {
+        *value = (int64_t)ctx->wr_blocks;
+    } else if (strcmp(name, "write_blocks_decoded") == 0) {
+        *value = (int64_t)ctx->wr_decoded;
+    } else if (strcmp(name, "write_streams_ok") == 0 ||
+               strcmp(name, "write_streams_failed") == 0) {
+        // of the last snapmi_write_ranges_indexed: wait for it
+        unsigned long long w[2] = {0, 0};
+        if (ctx->wr_stats_live && ctx->wr_stat.p) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(w, ctx->wr_stat.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        *value = (int64_t)(name[14] == 'o' ? w[0] : w[1]);
     } else if (strncmp(name, "index_build_", 12) == 0 &&
                (strcmp(name + 12, "built") == 0 ||
                 strcmp(name + 12, "unaligned") == 0 ||

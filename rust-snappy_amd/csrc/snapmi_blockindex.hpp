@@ -9,6 +9,7 @@
 //                     else is an ordinary stream of the batch launch)
 //   bi_piece          input and output range of piece k of an indexed stream
 //   bi_range_*        the rules of a range read (snapmi_decompress_ranges_indexed)
+//   bi_write_*        the rules of a range write (snapmi_write_ranges_indexed)
 //   bi_build          the index of a stream that came without one: the
 //                     sequential definition of snapmi_build_block_index
 //
@@ -239,6 +240,166 @@ SNAPMI_BI_HD inline BiSpan bi_range_span(uint64_t off, uint64_t len,
     s.to = lo - off;
     s.n = hi - lo;
     return s;
+}
+
+// ---------------------------------------------------------------------
+// Range writes (snapmi_write_ranges_indexed): write [off, off + len) replaces
+// that part of a stream's OUTPUT.  The blocks the writes touch are decoded
+// (when a write cuts them), patched and compressed again; every other block
+// keeps its compressed bytes, which move by what the touched blocks in front
+// of them grew or shrank.
+// ---------------------------------------------------------------------
+// What is wrong with the host's write list, or 0.  Writes of len == 0 are not
+// looked at.  The others are sorted by (stream, off) and do not overlap;
+// stream < n; off + len does not wrap.
+constexpr int kBiWriteOk = 0, kBiWriteWraps = 1, kBiWriteNoStream = 2,
+              kBiWriteOrder = 3;
+
+SNAPMI_BI_HD inline int bi_write_check(const uint32_t *stream,
+                                       const uint64_t *off,
+                                       const uint64_t *len, size_t m,
+                                       uint64_t n, size_t *bad)
+{
+    bool any = false;
+    uint32_t ps = 0;
+    uint64_t pend = 0; // end of the last write looked at
+    for (size_t w = 0; w < m; w++) {
+        if (len[w] == 0)
+            continue;
+        *bad = w;
+        if (off[w] + len[w] < off[w])
+            return kBiWriteWraps;
+        if (stream[w] >= n)
+            return kBiWriteNoStream;
+        if (any && (stream[w] < ps || (stream[w] == ps && off[w] < pend)))
+            return kBiWriteOrder;
+        any = true;
+        ps = stream[w];
+        pend = off[w] + len[w];
+    }
+    return kBiWriteOk;
+}
+
+// The touched blocks of a checked write list, write by write: a walk that
+// remembers the last block of the write in front, which the next write of the
+// same stream may share - a shared block counts once, for the first of them.
+struct BiWriteWalk {
+    bool any = false;
+    uint32_t stream = 0;
+    uint64_t last = 0;
+};
+
+// Blocks the (non-empty) write adds to the list: *k0 the first, the return
+// value their number (0: its only block is the one the write in front ended
+// in).
+SNAPMI_BI_HD inline uint64_t bi_write_touch(BiWriteWalk &w, uint32_t stream,
+                                            uint64_t off, uint64_t len,
+                                            uint64_t *k0)
+{
+    uint64_t k;
+    uint64_t c = bi_range_blocks(off, len, &k);
+    if (c == 0) {
+        *k0 = k;
+        return 0;
+    }
+    const uint64_t last = k + c - 1;
+    if (w.any && w.stream == stream && w.last == k) {
+        k++;
+        c--;
+    }
+    w.any = true;
+    w.stream = stream;
+    w.last = last;
+    *k0 = k;
+    return c;
+}
+
+// Is touched block k, whose FIRST write is [off, off + len), an EDGE block -
+// decoded into a room, patched there and compressed from there - or COVERED:
+// [k * 64 KiB, (k + 1) * 64 KiB) lies inside the write, which is then the
+// block's only one, and the block is compressed straight from the write's
+// bytes?  Told from the writes alone, as bi_range_edge: a stream's short last
+// block is an edge block unless the write ends on a multiple of 64 KiB.  (A
+// block that two writes share is cut by both of them.)
+SNAPMI_BI_HD inline bool bi_write_edge(uint64_t off, uint64_t len, uint64_t k)
+{
+    return bi_range_edge(off, len, k);
+}
+
+// What a write puts into touched block k: bytes [to, to + n) of its source go
+// to byte `from` of the block (bi_range_span with the copy turned round).
+SNAPMI_BI_HD inline BiSpan bi_write_span(uint64_t off, uint64_t len,
+                                         uint64_t k)
+{
+    return bi_range_span(off, len, k);
+}
+
+// The index rule of a write: bi_range_stream_usable, and the block's part for
+// EVERY block of the stream - each one is copied or replaced.  The first
+// block that fails it, or ~0.
+SNAPMI_BI_HD inline uint64_t bi_write_first_bad_block(const uint64_t *e,
+                                                      uint64_t in_len,
+                                                      uint64_t blocks)
+{
+    for (uint64_t k = 0; k < blocks; k++)
+        if (!bi_range_block_usable(e, in_len, k))
+            return k;
+    return ~0ull;
+}
+
+// The splice, by definition: the stream's new entries from its old ones e[]
+// (blocks + 1 of them), the ascending list tk[nt] of its touched blocks and
+// their new compressed sizes tsize[nt] (without a varint); hdr_new is the
+// length of varint(dlen).  Returns the new length (the last new entry).
+SNAPMI_BI_HD inline uint64_t bi_write_splice(const uint64_t *e,
+                                             uint64_t blocks,
+                                             const uint64_t *tk,
+                                             const uint64_t *tsize,
+                                             uint64_t nt, uint32_t hdr_new,
+                                             uint64_t *e_new)
+{
+    uint64_t pos = hdr_new, t = 0;
+    for (uint64_t k = 0; k < blocks; k++) {
+        e_new[k] = pos;
+        if (t < nt && tk[t] == k)
+            pos += tsize[t++];
+        else
+            pos += e[k + 1] - e[k];
+    }
+    e_new[blocks] = pos;
+    return pos;
+}
+
+// ... and as the kernels compute it, an entry at a time: a block moves by
+// what the touched blocks in front of it changed.  tcum[j] is the sum, over
+// the touched blocks tk[0 .. j), of (new size - old size), modulo 2^64;
+// tcum[nt] the stream's total.
+SNAPMI_BI_HD inline uint64_t bi_write_below(const uint64_t *tk, uint64_t nt,
+                                            uint64_t k)
+{
+    uint64_t lo = 0, hi = nt; // touched blocks below k
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (tk[mid] < k)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+SNAPMI_BI_HD inline uint64_t bi_write_entry(const uint64_t *e, uint64_t k,
+                                            const uint64_t *tk,
+                                            const uint64_t *tcum, uint64_t nt,
+                                            uint32_t hdr_old, uint32_t hdr_new)
+{
+    return e[k] + hdr_new - hdr_old + tcum[bi_write_below(tk, nt, k)];
+}
+
+// The last verdict: the new stream fits its buffer (an exact cap passes).
+SNAPMI_BI_HD inline bool bi_write_fits(uint64_t cap, uint64_t new_len)
+{
+    return new_len <= cap;
 }
 
 // ---------------------------------------------------------------------

@@ -241,6 +241,21 @@ struct snapmi_ctx {
     bool ev_ib_live = false, ev_ibg_live[2] = {false, false};
     uint64_t ib_groups = 0;
     bool ib_stats_live = false;
+    // snapmi_write_ranges_indexed: the device's copy of the host's write
+    // lists, the touched streams' states and the touched blocks' sums, the
+    // one-block streams of a group's compress launch, its compress slots, edge
+    // rooms (slots and rooms together at most write_scratch_bytes a group,
+    // unless one stream takes more) and piece descriptors, the two counters;
+    // the pinned staging of the lists with the event of the copy that last
+    // read it; touched blocks and edge blocks of the last call; whether it
+    // ran its kernels
+    snapmi::DevBuf wr_meta, wr_state, wr_z, wr_slot, wr_room, wr_desc, wr_stat;
+    snapmi::PinBuf pin_wr;
+    hipEvent_t ev_wr = nullptr;
+    bool ev_wr_live = false;
+    uint64_t write_scratch_bytes = 1ull << 30;
+    uint64_t wr_blocks = 0, wr_decoded = 0;
+    bool wr_stats_live = false;
     // test options: "index_build_route" (BuildArgs::route) and the most
     // streams a group of the scan route holds
     uint32_t index_build_route = 0;

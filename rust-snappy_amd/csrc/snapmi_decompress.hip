@@ -3411,4 +3411,374 @@ __global__ __launch_bounds__(64) void k_index_walk(BuildArgs x)
     }
 }
 
+// ---------------------------------------------------------------------
+// snapmi_write_ranges_indexed: bytes [off, off + len) of a stream's output
+// replaced, only the touched blocks going through the codec
+// (snapmi_blockindex.hpp has the rules, WriteArgs the lists).  The host cuts
+// the touched streams into groups whose compress slots and edge rooms fit the
+// scratch and runs, per group: k_write_plan (a wavefront per touched stream:
+// header, writes against dlen, the index rule over EVERY block), k_write_blocks
+// (a thread per touched block: the piece of an edge block into its room, and
+// the block as a one-block stream of the compress launch - from its room, or
+// straight from the write that covers it), the batch decoder over the pieces,
+// k_write_patch (a wavefront per edge block: the writes' bytes over the
+// room), the batch compressor over the blocks, k_write_sizes (a workgroup per
+// touched stream: its pieces OK and full, the running sum of what its touched
+// blocks grew, the cap, out_lens and errs), k_write_jobs (the splice jobs of
+// the streams that passed, one per block) and k_write_splice (the copies).
+// Behind the last group k_write_index writes the new index.
+// The output of a stream is written by k_write_sizes (the varint) and
+// k_write_splice alone, both only for a stream in state 2: new length <= cap
+// is known by then, and the jobs' destinations [new entry k, new entry k + 1)
+// tile [varint, new length).  The write lists are the host's own; what the
+// device reads of the caller's - in_lens, first[], the index - is checked in
+// k_write_plan before anything is addressed with it: a stream in state 1 has
+// its entries inside the index and e[k] < e[k + 1] <= in_len for every block.
+// ---------------------------------------------------------------------
+namespace {
+__device__ __forceinline__ void write_fail(const WriteArgs &x, uint32_t t,
+                                           uint32_t s, int kind, uint64_t a,
+                                           uint64_t b, uint64_t c)
+{
+    x.out_lens[s] = 0;
+    set_error(x.errs, s, kind, a, b, c);
+    x.st_state[t] = 0;
+    atomicAdd(&x.stat[1], 1ull);
+}
+
+__device__ __forceinline__ uint64_t wave_min64(uint64_t v)
+{
+    for (uint32_t o = 32; o; o >>= 1) {
+        const uint64_t t = __shfl_xor(v, o);
+        v = t < v ? t : v;
+    }
+    return v;
+}
+} // namespace
+
+// a thread per stream: "no write names it" until a later kernel says more
+__global__ __launch_bounds__(256) void k_write_init(WriteArgs x)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= x.n)
+        return;
+    x.out_lens[i] = 0;
+    set_error(x.errs, i, SNAPMI_OK, 0, 0, 0);
+}
+
+// a wavefront per touched stream of the group
+__global__ __launch_bounds__(256) void k_write_plan(WriteArgs x)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
+                       (threadIdx.x >> 6);
+    if (i >= x.tg)
+        return;
+    const uint32_t t = x.t0 + (uint32_t)i;
+    const uint32_t s = x.ts_stream[t];
+    const uint64_t in_len = x.in_lens[s];
+    uint32_t hdr = 0;
+    uint64_t dlen = 0;
+    // (an empty stream announces nothing, as for snapmi_decompress_len_batch)
+    if (in_len != 0) {
+        snapmi_error he;
+        if (read_header((gcptr)x.in_ptrs[s], in_len, &hdr, &dlen, &he, 0) !=
+            SNAPMI_OK) {
+            if (lane == 0)
+                write_fail(x, t, s, he.kind, he.a, he.b, he.c);
+            return;
+        }
+    }
+    // the first write that passes the stream's end
+    uint64_t bad = ~0ull;
+    for (uint32_t w = x.ts_w0[t] + lane; w < x.ts_w0[t + 1] && bad == ~0ull;
+         w += 64)
+        if (x.w_off[w] + x.w_len[w] > dlen)
+            bad = w;
+    bad = wave_min64(bad);
+    if (bad != ~0ull) {
+        if (lane == 0)
+            write_fail(x, t, s, SNAPMI_E_ARGUMENT, x.w_off[bad], x.w_len[bad],
+                       dlen);
+        return;
+    }
+    const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
+    if (!bi_range_stream_usable(in_len, hdr, dlen, x.index, f0, f1,
+                                x.entries)) {
+        if (lane == 0)
+            write_fail(x, t, s, SNAPMI_E_ARGUMENT, s, 0, 0);
+        return;
+    }
+    // (bi_write_first_bad_block, the lanes taking a block each)
+    const uint64_t *e = x.index + f0;
+    const uint64_t blocks = f1 - f0 - 1;
+    bad = ~0ull;
+    for (uint64_t k = lane; k < blocks && bad == ~0ull; k += 64)
+        if (!bi_range_block_usable(e, in_len, k))
+            bad = k;
+    bad = wave_min64(bad);
+    if (bad != ~0ull) {
+        if (lane == 0)
+            write_fail(x, t, s, SNAPMI_E_ARGUMENT, s, bad, 0);
+        return;
+    }
+    if (lane == 0) {
+        x.st_dlen[t] = dlen;
+        x.st_hdr[t] = hdr;
+        x.st_state[t] = 1;
+    }
+}
+
+// a thread per touched block of the group
+__global__ __launch_bounds__(256) void k_write_blocks(WriteArgs x)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= x.bg)
+        return;
+    const uint32_t b = x.b0 + (uint32_t)j;
+    const uint32_t t = x.tb_ts[b], r = x.tb_room[b];
+    uint8_t *const slot = x.slot + j * kSlotBytes;
+    // the block of a failed stream: an empty stream of the compress launch,
+    // and a piece that is not the decoder's (mode 3)
+    const void *zin = slot, *pin = nullptr;
+    void *pout = nullptr;
+    uint64_t zlen = 0, pinlen = 0;
+    uint8_t mode = 3;
+    if (x.st_state[t] == 1) {
+        // (state 1: every write lies inside dlen, so k < 65 536; the entries
+        // lie inside the index and inside the stream)
+        const uint32_t s = x.ts_stream[t];
+        const uint64_t k = x.tb_k[b];
+        const uint64_t rest = x.st_dlen[t] - k * kBiBlock;
+        zlen = rest < kBiBlock ? rest : kBiBlock;
+        if (r != 0xFFFFFFFFu) {
+            const uint64_t *e = x.index + x.first[s];
+            pin = (const uint8_t *)x.in_ptrs[s] + e[k];
+            pinlen = e[k + 1] - e[k];
+            pout = x.room + (uint64_t)r * kBiBlock;
+            mode = 2;
+            zin = pout;
+        } else {
+            const uint32_t w = x.tb_w[b];
+            zin = (const uint8_t *)x.w_src[w] + (k * kBiBlock - x.w_off[w]);
+        }
+    }
+    x.z_in[j] = zin;
+    x.z_inlen[j] = zlen;
+    x.z_out[j] = slot;
+    x.z_outlen[j] = 0;
+    if (r != 0xFFFFFFFFu) {
+        x.c_in[r] = pin;
+        x.c_inlen[r] = pinlen;
+        x.c_out[r] = pout;
+        x.c_cap[r] = mode == 2 ? zlen : 0;
+        x.c_outlen[r] = 0;
+        set_error(x.c_err, r, SNAPMI_OK, 0, 0, 0);
+        x.c_mode[r] = mode;
+    }
+}
+
+// a wavefront per touched block of the group: every write that touches an
+// edge block, over its room.  (A room whose piece failed is patched too: its
+// stream fails in k_write_sizes and what the block compresses to is dropped.)
+__global__ __launch_bounds__(256) void k_write_patch(WriteArgs x)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t j = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
+                       (threadIdx.x >> 6);
+    if (j >= x.bg)
+        return;
+    const uint32_t b = x.b0 + (uint32_t)j;
+    const uint32_t t = x.tb_ts[b], r = x.tb_room[b];
+    if (r == 0xFFFFFFFFu || x.st_state[t] != 1)
+        return;
+    const uint64_t k = x.tb_k[b];
+    const gptr room = (gptr)(x.room + (uint64_t)r * kBiBlock);
+    // its first write, and those behind it that start inside the block
+    for (uint32_t w = x.tb_w[b]; w < x.ts_w0[t + 1]; w++) {
+        const uint64_t off = x.w_off[w], len = x.w_len[w];
+        if (off / kBiBlock > k)
+            break;
+        const BiSpan sp = bi_write_span(off, len, k);
+        wave_copy<false>(room + sp.from, (gcptr)x.w_src[w] + sp.to, sp.n,
+                         lane);
+    }
+}
+
+// a workgroup per touched stream of the group
+__global__ __launch_bounds__(256) void k_write_sizes(WriteArgs x)
+{
+    __shared__ uint64_t wave_tot[16][2];
+    __shared__ uint64_t wave_bad[4];
+    const uint32_t t = x.t0 + blockIdx.x;
+    if (x.st_state[t] != 1) // k_write_plan wrote its out_lens and errs
+        return;
+    const uint32_t s = x.ts_stream[t];
+    const uint32_t ba = x.ts_b0[t], nt = x.ts_b0[t + 1] - ba;
+    // the first piece, in block order, that is not OK and full
+    uint64_t bad = ~0ull;
+    for (uint32_t i = threadIdx.x; i < nt && bad == ~0ull; i += blockDim.x) {
+        const uint32_t r = x.tb_room[ba + i];
+        if (r != 0xFFFFFFFFu &&
+            (x.c_mode[r] != 2 || x.c_err[r].kind != SNAPMI_OK ||
+             x.c_outlen[r] != x.c_cap[r]))
+            bad = i;
+    }
+    bad = wave_min64(bad);
+    if ((threadIdx.x & 63) == 0)
+        wave_bad[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    for (uint32_t w = 0; w < 4; w++)
+        bad = wave_bad[w] < bad ? wave_bad[w] : bad;
+    if (bad != ~0ull) {
+        if (threadIdx.x == 0) {
+            const snapmi_error e = x.c_err[x.tb_room[ba + bad]];
+            if (e.kind != SNAPMI_OK)
+                write_fail(x, t, s, e.kind, e.a, e.b, e.c);
+            // not reached, kept as the guard of an invariant (see
+            // k_range_finish): a mode-2 piece that reports OK is full
+            else
+                write_fail(x, t, s, SNAPMI_E_ARGUMENT, s, x.tb_k[ba + bad], 0);
+        }
+        return;
+    }
+    // the running sum of what the touched blocks grew (bi_write_entry's tcum),
+    // blockDim.x blocks a stride
+    const uint64_t *e = x.index + x.first[s];
+    uint64_t *cum = x.tb_cum + ba + t;
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < nt; base += blockDim.x) {
+        const uint32_t i = base + threadIdx.x;
+        uint64_t d = 0, none = 0;
+        if (i < nt) {
+            const uint32_t j = ba + i - x.b0;
+            const uint64_t k = x.tb_k[ba + i];
+            d = x.z_outlen[j] - varint_len(x.z_inlen[j]) - (e[k + 1] - e[k]);
+        }
+        uint64_t all[2];
+        range_scan2(d, none, wave_tot, all);
+        if (i < nt)
+            cum[i] = carry + d;
+        carry += all[0];
+    }
+    if (threadIdx.x != 0)
+        return;
+    cum[nt] = carry;
+    const uint64_t dlen = x.st_dlen[t];
+    const uint32_t hn = varint_len(dlen);
+    // (the last old entry is in_len: bi_range_stream_usable)
+    const uint64_t new_len = x.in_lens[s] + hn - x.st_hdr[t] + carry;
+    const uint64_t cap = x.out_caps[s];
+    if (!bi_write_fits(cap, new_len)) {
+        write_fail(x, t, s, SNAPMI_BUFFER_TOO_SMALL, cap, new_len, 0);
+        return;
+    }
+    gptr out = (gptr)x.out_ptrs[s];
+    uint64_t v = dlen;
+    for (uint32_t q = 0; q < hn; q++) {
+        out[q] = (uint8_t)((v & 0x7F) | (q + 1 < hn ? 0x80 : 0));
+        v >>= 7;
+    }
+    x.out_lens[s] = new_len;
+    set_error(x.errs, s, SNAPMI_OK, 0, 0, 0);
+    x.st_state[t] = 2;
+    atomicAdd(&x.stat[0], 1ull);
+}
+
+// one workgroup: the first splice job of every touched stream of the group -
+// a job per block for a stream that passed, none for the others
+__global__ __launch_bounds__(1024) void k_write_jobs(WriteArgs x)
+{
+    __shared__ uint64_t wave_tot[16][2];
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < x.tg; base += blockDim.x) {
+        const uint32_t i = base + threadIdx.x;
+        uint64_t c = 0, none = 0;
+        if (i < x.tg && x.st_state[x.t0 + i] == 2)
+            c = bi_blocks(x.st_dlen[x.t0 + i]);
+        uint64_t all[2];
+        range_scan2(c, none, wave_tot, all);
+        if (i < x.tg)
+            x.jobs_first[i] = carry + c;
+        carry += all[0];
+    }
+    if (threadIdx.x == 0)
+        x.jobs_first[x.tg] = carry;
+}
+
+// The copies: the wavefronts of a fixed grid take the jobs in turn (the host
+// does not know how many there are: dlen lives here).  Job (stream, block k):
+// the block's bytes - the old ones, or the slot's behind its varint - to the
+// stream's new entry k.
+__global__ __launch_bounds__(256) void k_write_splice(WriteArgs x)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint64_t total = x.jobs_first[x.tg];
+    for (uint64_t id = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
+                       (threadIdx.x >> 6);
+         id < total; id += waves) {
+        // the last stream of the group whose jobs start at or in front of id
+        uint32_t lo = 0, hi = x.tg;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (x.jobs_first[mid] <= id)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint32_t t = x.t0 + lo;
+        const uint64_t k = id - x.jobs_first[lo];
+        const uint32_t s = x.ts_stream[t];
+        const uint32_t ba = x.ts_b0[t], nt = x.ts_b0[t + 1] - ba;
+        const uint64_t *tk = x.tb_k + ba;
+        const uint64_t *e = x.index + x.first[s];
+        const uint64_t below = bi_write_below(tk, nt, k);
+        const gptr dst = (gptr)x.out_ptrs[s] + e[k] +
+                         varint_len(x.st_dlen[t]) - x.st_hdr[t] +
+                         x.tb_cum[ba + t + below];
+        gcptr src;
+        uint64_t len;
+        if (below < nt && tk[below] == k) {
+            const uint32_t j = ba + (uint32_t)below - x.b0;
+            const uint32_t vl = varint_len(x.z_inlen[j]);
+            src = (gcptr)(x.slot + (uint64_t)j * kSlotBytes) + vl;
+            len = x.z_outlen[j] - vl;
+        } else {
+            src = (gcptr)x.in_ptrs[s] + e[k];
+            len = e[k + 1] - e[k];
+        }
+        wave_copy<true>(dst, src, len, lane);
+    }
+}
+
+// a thread per entry: the old entry, moved where a stream that passed owns it
+__global__ __launch_bounds__(256) void k_write_index(WriteArgs x)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= x.entries)
+        return;
+    uint64_t v = x.index[e];
+    const uint32_t s = bi_find_stream(x.first, x.n, e);
+    const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
+    if (f0 <= e && e < f1) {
+        uint32_t lo = 0, hi = x.ts; // the touched stream s is, if any
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (x.ts_stream[mid] < s)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        // (state 2: [f0, f1) lies inside the index, blocks + 1 entries)
+        if (lo < x.ts && x.ts_stream[lo] == s && x.st_state[lo] == 2) {
+            const uint32_t ba = x.ts_b0[lo], nt = x.ts_b0[lo + 1] - ba;
+            v = bi_write_entry(x.index + f0, e - f0, x.tb_k + ba,
+                               x.tb_cum + ba + lo, nt, x.st_hdr[lo],
+                               varint_len(x.st_dlen[lo]));
+        }
+    }
+    x.new_index[e] = v;
+}
+
 } // namespace snapmi

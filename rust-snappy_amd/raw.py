@@ -110,7 +110,9 @@ class Context:
         "index_streams_pieced", "index_streams_fallback", "range_pieces",
         "range_ranges_ok", "range_ranges_failed", "index_build_built",
         "index_build_unaligned", "index_build_corrupt",
-        "index_build_missized", "index_build_walked" (include/snapmi.h)."""
+        "index_build_missized", "index_build_walked", "write_blocks",
+        "write_blocks_decoded", "write_streams_ok", "write_streams_failed"
+        (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:
@@ -416,6 +418,44 @@ def decompress_ranges_indexed(ctx, in_ptrs, in_lens, index_first, index,
         _ptr(range_len), _u64_array(host_range_off),
         _u64_array(host_range_len), _ptr(range_out), _ptr(range_got),
         _ptr(range_errs), m)
+    if rc:
+        _raise(ctx, rc)
+
+
+def write_blocks(streams, offs, lens):
+    """snapmi_write_blocks: blocks the writes [off, off + len) of streams[w]
+    touch - a block that two neighbouring writes share counts once."""
+    assert len(streams) == len(offs) == len(lens)
+    return int(_lib.load().snapmi_write_blocks(
+        (C.c_uint32 * len(streams))(*[int(x) & 0xFFFFFFFF for x in streams]),
+        _u64_array(offs), _u64_array(lens), len(streams)))
+
+
+def write_ranges_indexed(ctx, in_ptrs, in_lens, index_first, index,
+                         write_stream, write_off, write_len, write_src,
+                         out_ptrs, out_caps, out_lens, errs, new_index,
+                         index_entries=None):
+    """snapmi_write_ranges_indexed: write_src[w][0, len) replaces output bytes
+    [off, off + len) of stream write_stream[w]; only the touched blocks are
+    decoded and compressed, the others are copied.  in_ptrs / in_lens /
+    index_first / index: the streams and their block index (int64 CUDA
+    tensors); write_stream / write_off / write_len: sequences of ints sorted
+    by (stream, off); write_src: sequence of device addresses (ints);
+    out_ptrs / out_caps / out_lens / new_index: uint64-as-int64 CUDA tensors
+    ([n], [n], [n], [index_entries]); errs: optional uint8 CUDA tensor of 32*n
+    bytes.  Enqueues on the context's stream."""
+    m = len(write_stream)
+    assert len(write_off) == m and len(write_len) == m and len(write_src) == m
+    if index_entries is None:
+        index_entries = index.numel() if index is not None else 0
+    rc = _lib.of(ctx).snapmi_write_ranges_indexed(
+        ctx._h, _ptr(in_ptrs), _ptr(in_lens),
+        in_ptrs.numel() if in_ptrs is not None else 0, _ptr(index_first),
+        _ptr(index), int(index_entries),
+        (C.c_uint32 * m)(*[int(x) & 0xFFFFFFFF for x in write_stream]),
+        _u64_array(write_off), _u64_array(write_len), _u64_array(write_src),
+        m, _ptr(out_ptrs), _ptr(out_caps), _ptr(out_lens), _ptr(errs),
+        _ptr(new_index))
     if rc:
         _raise(ctx, rc)
 

@@ -1,0 +1,314 @@
+"""The range-write rules on the CPU: bi_write_* of csrc/snapmi_blockindex.hpp,
+compiled into a stand-alone program (tests/writeindex_host.cpp - the source
+the kernels and the host entry point compile) plainly and under the
+sanitizers, against tests/writeindex_ref.py; the splice identity - old bytes
+of untouched blocks around the oracle's bytes of the patched ones ARE the
+oracle's stream of the patched data - that the call's contract rests on; the
+exports and bindings of the two calls."""
+import random
+import subprocess
+
+import pytest
+
+import blockindex_ref as B
+import oracle_lib as O
+import rangeindex_ref as R
+import writeindex_ref as W
+from conftest import ROOT
+
+U64 = 1 << 64
+NONE = U64 - 1
+
+# write lists (stream, off, len): the shapes of the GPU tests on a stream of
+# 200 000 bytes, neighbours that share a block, and what the host refuses
+LISTS = [
+    [],
+    [(4, 0, 1)], [(4, 65535, 1)], [(4, 65536, 1)], [(4, 199999, 1)],
+    [(4, 65530, 16)],
+    [(4, 65536, 65536)],
+    [(4, 1000, 140000)],
+    [(4, 0, 200000)],
+    [(4, 100, 2), (4, 300, 2), (4, 65535, 2)],
+    # neighbours: share block 0; share block 1, the first ending in it; touch
+    # end to end on a boundary (no shared block); three in one block
+    [(4, 0, 10), (4, 10, 10)],
+    [(4, 60000, 10000), (4, 70000, 100)],
+    [(4, 0, 65536), (4, 65536, 65536)],
+    [(4, 10, 1), (4, 20, 1), (4, 30, 70000)],
+    [(4, 0, 65537), (4, 65537, 65535), (4, 131072, 1)],
+    # the same block number in two streams is two blocks
+    [(1, 0, 10), (4, 0, 10)], [(1, 999, 1), (2, 0, 1), (4, 5, 1)],
+    # len == 0 is ignored altogether: anywhere, any stream, any offset
+    [(9, 5, 0)], [(4, 10, 5), (0, U64 - 1, 0), (4, 15, 5)],
+    [(4, 100, 0), (4, 50, 10)], [(4, 50, 10), (4, 55, 0), (4, 60, 1)],
+    # refused: unsorted, overlapping, wrapping, no such stream
+    [(4, 300, 2), (4, 100, 2)], [(4, 0, 1), (3, 0, 1)],
+    [(4, 0, 10), (4, 9, 1)], [(4, 0, 10), (4, 0, 10)],
+    [(4, U64 - 1, 1)], [(4, 1, U64 - 1)], [(4, U64 - 65536, 65536)],
+    [(7, 0, 1)], [(4, 0, 1), (2**32 - 1, 0, 1)],
+    [(4, U64 - 2, 1)],
+]
+N_STREAMS = 7
+
+
+def build(tmp_path_factory, name, extra):
+    exe = tmp_path_factory.mktemp(name) / "writeindex_host"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror",
+                           *extra,
+                           str(ROOT / "tests" / "writeindex_host.cpp"),
+                           "-o", str(exe)])
+
+    def run(lines):
+        out = subprocess.run([str(exe)],
+                             input="".join(s + "\n" for s in lines),
+                             capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        rows = [[int(t) for t in ln.split()]
+                for ln in out.stdout.splitlines()]
+        assert len(rows) == len(lines)
+        return rows
+    return run
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def prog(request, tmp_path_factory):
+    """The stand-alone program, and the same under
+    -fsanitize=address,undefined: every test below runs through both."""
+    extra = [] if request.param == "plain" else [
+        "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    return build(tmp_path_factory, "writeindex_" + request.param, extra)
+
+
+def draws(seed, count):
+    """Sorted, disjoint write lists over a few streams, dense enough that
+    neighbours share blocks; some with empty writes strewn in."""
+    rng = random.Random(seed)
+    out = []
+    for _ in range(count):
+        ws = []
+        for s in sorted(rng.sample(range(N_STREAMS), rng.randrange(1, 4))):
+            pos = rng.choice([0, 0, 65535, 65536, rng.randrange(1 << 18)])
+            for _ in range(rng.randrange(1, 6)):
+                ln = rng.choice([1, 2, 16, 4096, 65536, 65537, 140000,
+                                 rng.randrange(1, 1 << 18)])
+                ws.append((s, pos, ln))
+                pos += ln + rng.choice([0, 0, 1, 100, 65536, 70000])
+                if rng.random() < 0.2:
+                    ws.append((rng.randrange(100), rng.randrange(U64), 0))
+        out.append(ws)
+    return out
+
+
+def fmt(ws):
+    return f"{len(ws)} " + " ".join(f"{s} {o} {n}" for s, o, n in ws)
+
+
+def test_host_checks(prog):
+    lists = LISTS + draws(1, 300)
+    rows = prog([f"C {N_STREAMS} " + fmt(ws) for ws in lists])
+    for ws, row in zip(lists, rows):
+        code, bad = W.check(ws, N_STREAMS)
+        assert row == [code, bad or 0], ws
+    by = {tuple(ws): W.check(ws, N_STREAMS) for ws in LISTS}
+    assert by[((4, 300, 2), (4, 100, 2))] == (W.ORDER, 1)
+    assert by[((4, 0, 1), (3, 0, 1))] == (W.ORDER, 1)
+    assert by[((4, 0, 10), (4, 9, 1))] == (W.ORDER, 1)
+    assert by[((4, 0, 10), (4, 10, 10))] == (0, None)
+    assert by[((4, U64 - 1, 1),)] == (W.WRAPS, 0)
+    assert by[((4, U64 - 2, 1),)] == (0, None)
+    assert by[((7, 0, 1),)] == (W.NO_STREAM, 0)
+    assert by[((9, 5, 0),)] == (0, None)
+    assert by[((4, 100, 0), (4, 50, 10))] == (0, None)
+    assert all(W.check(ws, N_STREAMS) == (0, None) for ws in draws(1, 300))
+
+
+def test_touched_blocks_edges_and_spans(prog):
+    lists = LISTS + draws(2, 300)
+    rows = prog([f"N {fmt(ws)}" for ws in lists])
+    for ws, row in zip(lists, rows):
+        assert row == [W.blocks(ws)], ws
+    good = [ws for ws in lists if W.check(ws, N_STREAMS)[0] == 0]
+    rows = prog([f"T {fmt(ws)}" for ws in good])
+    probes, want = [], []
+    for ws, row in zip(good, rows):
+        t = W.touched(ws)
+        assert row == [len(t)] + [int(x) for q in t for x in q], ws
+        assert len(t) == W.blocks(ws)
+        # a shared block counts once and is an edge block; a covered block
+        # has one write, which fills it
+        seen = set()
+        for s, k, w, edge in t:
+            assert (s, k) not in seen
+            seen.add((s, k))
+            hits = [i for i, (s2, o, n) in enumerate(ws) if s2 == s and n
+                    and R.blocks(o, n)[1] <= k < sum(R.blocks(o, n))]
+            assert hits[0] == w
+            assert edge or len(hits) == 1
+            for i in hits:
+                _, o, n = ws[i]
+                probes.append(f"S {o} {n} {k}")
+                a, to, m = R.span(o, n, k)
+                want.append([int(R.edge(o, n, k)), a, to, m])
+                assert len(hits) == 1 or R.edge(o, n, k)
+            if not edge:
+                assert want[-1] == [0, 0, k * 65536 - ws[w][1], 65536]
+    assert prog(probes) == want
+    by = {tuple(ws): W.touched(ws) for ws in LISTS[:20]}
+    assert by[((4, 65530, 16),)] == [(4, 0, 0, True), (4, 1, 0, True)]
+    assert by[((4, 65536, 65536),)] == [(4, 1, 0, False)]
+    assert [q[3] for q in by[((4, 1000, 140000),)]] == [True, False, True]
+    assert by[((4, 100, 2), (4, 300, 2), (4, 65535, 2))] == [
+        (4, 0, 0, True), (4, 1, 2, True)]
+    assert by[((4, 0, 65536), (4, 65536, 65536))] == [
+        (4, 0, 0, False), (4, 1, 1, False)]
+    # the last block of the 200 000-byte stream is short: an edge block
+    assert [q[3] for q in by[((4, 0, 200000),)]] == [False] * 3 + [True]
+    assert W.blocks([(4, 0, U64 - 1)]) == 1 << 48   # (the sum saturates)
+    rows = prog(["N " + fmt([(s, 0, U64 - 1) for s in range(70000)])])
+    assert rows == [[U64 - 1]]
+
+
+def test_index_rule_over_every_block(prog):
+    lines, want = [], []
+    for blocks in (1, 2, 4, 70):
+        good = [3 + 100 * k for k in range(blocks + 1)]
+        in_len = good[-1]
+        cases = [(good, in_len, None), (good, in_len - 1, blocks - 1),
+                 ([0] * (blocks + 1), in_len, 0)]
+        for k in range(blocks):
+            e = list(good)
+            e[k + 1] = e[k]                      # an empty block
+            cases.append((e, in_len, k))
+            e = list(good)
+            e[k + 1] = in_len + 5                # an entry above in_len
+            cases.append((e, in_len + (5 if k + 1 == blocks else 0), k
+                          if k + 1 < blocks else None))
+        for e, ln, bad in cases:
+            lines.append(f"K {ln} {blocks} " + " ".join(map(str, e)))
+            first = next((k for k in range(blocks)
+                          if not (e[k] < e[k + 1] <= ln)), None)
+            if bad is not None:
+                assert first == bad, (e, ln)
+            want.append([NONE if first is None else first])
+    assert prog(lines) == want
+    assert prog(["F 10 10", "F 9 10", "F 0 0", f"F {NONE} {NONE}",
+                 "F 11 10"]) == [[1], [0], [1], [1], [1]]
+
+
+def test_splice_entries(prog):
+    rng = random.Random(3)
+    lines, want = [], []
+    for _ in range(300):
+        blocks = rng.choice([1, 2, 3, 16, 300])
+        hdr_old = rng.choice([1, 2, 3, 5])
+        hdr_new = rng.choice([hdr_old, 1, 3])
+        e = [hdr_old]
+        for _ in range(blocks):
+            e.append(e[-1] + rng.randrange(1, 70000))
+        nt = rng.randrange(0, blocks + 1)
+        tk = sorted(rng.sample(range(blocks), nt))
+        tsize = [rng.randrange(1, 76490) for _ in tk]
+        lines.append(" ".join(map(str, ["X", hdr_old, hdr_new, blocks, nt]
+                                  + e + tk + tsize)))
+        ne = W.splice(e, tk, tsize, hdr_new)
+        want.append(ne + ne)
+    assert prog(lines) == want
+
+
+@pytest.fixture(scope="module")
+def case():
+    return W.Case()
+
+
+def test_splice_identity_against_the_oracle(case):
+    """varint(dlen), then per block the old bytes [entry k, entry k + 1) or
+    the oracle's stream of the patched block without its varint, is the
+    oracle's stream of the patched data, and the running sums are its index:
+    what makes the call's yardstick exact."""
+    rng = random.Random(11)
+    checked = 0
+    for s in range(6):
+        data = case.inputs[s]
+        for ws in W.shapes(len(data), rng) + (
+                [[(100, data[100:300])]] if len(data) >= 300 else []):
+            writes = [(s, off, b) for off, b in ws]
+            res, new_index = W.expect(
+                case.comps, case.flat, case.first, writes,
+                [1 << 40] * case.n, O.compress, W.decode_piece,
+                W.header_error)
+            new = W.patched(data, ws)
+            out, ne, err = res[s]
+            assert err == W.OK, (s, ws[0][0], err)
+            assert out == O.compress(new), (s, ws[0][0], len(ws[0][1]))
+            assert ne == B.expected_index(new)
+            assert new_index[case.first[s]:case.first[s + 1]] == ne
+            assert new_index[:case.first[s]] == case.flat[:case.first[s]]
+            assert all(r == (None, None, W.OK)
+                       for i, r in enumerate(res) if i != s)
+            checked += 1
+    assert checked >= 40
+    # the same bytes again: the new stream is the old one
+    res, _ = W.expect(case.comps, case.flat, case.first,
+                      [(4, 70000, case.inputs[4][70000:70100])],
+                      [1 << 40] * case.n, O.compress, W.decode_piece,
+                      W.header_error)
+    assert res[4][0] == case.comps[4] and res[4][1] == case.index[4]
+
+
+def test_model_precedence_of_failures(case):
+    """The model's own order of the reasons: header, write beyond dlen, index,
+    piece, cap."""
+    F = case.FOREIGN
+
+    def one(s, off, b, comps=None, flat=None, first=None, cap=1 << 40):
+        res, _ = W.expect(comps or case.comps, flat or case.flat,
+                          first or case.first, [(s, off, b)],
+                          [cap] * case.n, O.compress, W.decode_piece,
+                          W.header_error)
+        return res[s]
+
+    assert one(4, 199999, b"ab")[2] == (101, 199999, 2, 200000)
+    assert one(0, 0, b"a")[2] == (101, 0, 1, 0)
+    bad = list(case.comps)
+    bad[4] = b"\xff" * 11 + bad[4][11:]
+    # (a header that does not parse comes before everything else)
+    assert one(4, 1 << 40, b"a", comps=bad)[2] == W.header_error(bad[4])
+    flat, first = case.with_index(4, case.index[4][:3] + [case.index[4][2]]
+                                  + case.index[4][4:])
+    assert one(4, 0, b"a", flat=flat, first=first)[2] == (101, 4, 2, 0)
+    assert one(4, 1 << 40, b"a", flat=flat, first=first)[2][:2] == (101, 1 << 40)
+    out, ne, err = one(F, 10, b"xyz")
+    assert err == W.OK and out[ne[1]:] == case.comps[F][case.index[F][1]:]
+    assert one(F, 65536, b"a")[2][0] not in (0, 101)
+    need = len(one(4, 0, b"a")[0])
+    assert one(4, 0, b"a", cap=need)[2] == W.OK
+    assert one(4, 0, b"a", cap=need - 1)[2] == (2, need - 1, need, 0)
+    assert W.groups([(1, 0, 5), (4, 1000, 140000), (5, 0, 65536)],
+                    1 << 30) == [[1, 4, 5]]
+    assert W.groups([(1, 0, 5), (4, 1000, 140000), (5, 0, 65536)],
+                    W.FLOOR) == [[1], [4], [5]]
+
+
+def test_binding_exposes_the_two_calls(built):
+    from rust_snappy_amd import _lib, batch, raw
+    L = _lib.load()
+    P = _lib.load_product()
+    names = {s[0] for s in _lib.SYMBOLS}
+    for name in ("snapmi_write_blocks", "snapmi_write_ranges_indexed"):
+        assert name in names
+        assert hasattr(L, name) and hasattr(P, name)
+    header = (ROOT / "include" / "snapmi.h").read_text()
+    assert "SNAPMI_API uint64_t snapmi_write_blocks(" in header
+    assert "SNAPMI_API int snapmi_write_ranges_indexed(" in header
+    for m in ("snapmi.map", "snapmi_test.map"):
+        text = (ROOT / "rust-snappy_amd" / "csrc" / m).read_text()
+        assert "snapmi_write_blocks;" in text
+        assert "snapmi_write_ranges_indexed;" in text
+    # host code: no GPU needed
+    for ws in LISTS + draws(5, 100):
+        assert raw.write_blocks([w[0] for w in ws], [w[1] for w in ws],
+                                [w[2] for w in ws]) == W.blocks(ws), ws
+    assert raw.write_blocks([4], [1000], [140000]) == 3
+    assert raw.write_blocks([4, 4, 4], [100, 300, 65535], [2, 2, 2]) == 2
+    assert callable(batch.write_ranges)
+    assert callable(raw.write_ranges_indexed)

@@ -191,6 +191,15 @@ SNAPMI_API const char *snapmi_version(void);
  *                          the table entry of the probe that follows a miss -
  *                          fewer dependent rounds per block where a block's
  *                          latency is what is waited for; 0: never
+ *   "lane_tail_probes"     2..4: in the tail of a lane-kernel launch - the
+ *                          blocks have all been handed out, lanes only finish
+ *                          and a round costs its latency - a wavefront
+ *                          resolves up to this many probes a round (it
+ *                          fetches the entries of the probes that follow a
+ *                          miss; default 2); 0 or 1: never
+ *   "lane_tail_idle_pct"   ... from the moment this share of the launch's
+ *                          lanes is out of work (default 40; 0: from the
+ *                          first round)
  *   "lane_segment_blocks"  most blocks per lane-kernel launch (default
  *                          262144 = 16 GiB of input).  A larger batch is
  *                          matched and encoded in equal launches of at most

@@ -331,6 +331,12 @@ int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
         ctx->small_batch_kernel = (int)value;
     else if (strcmp(name, "lane_speculate") == 0 && value >= 0 && value <= 1)
         ctx->lane_speculate = (int)value;
+    else if (strcmp(name, "lane_tail_probes") == 0 && value >= 0 &&
+             value <= 4)
+        ctx->lane_tail_probes = (uint32_t)value;
+    else if (strcmp(name, "lane_tail_idle_pct") == 0 && value >= 0 &&
+             value <= 100)
+        ctx->lane_tail_idle_pct = (uint32_t)value;
     else if (strcmp(name, "span_kernel") == 0 && value >= kSpanMin &&
              value <= 1)
         ctx->span_kernel = (int)value;
@@ -653,6 +659,21 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                            ctx->tok_stage.cap + ctx->ntok.cap);
     } else if (strcmp(name, "token_pool_pages") == 0) {
         *value = ctx->tok_pool_pages_last;
+#ifdef SNAPMI_TESTING
+    } else if (strcmp(name, "lane_multi_rounds") == 0) {
+        // of the last token-path segment's lane wavefronts (test build: the
+        // kernel counts them): rounds above the launch's own depth; wait
+        uint32_t w = 0;
+        if (ctx->tok_pages.p) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(&w,
+                                   (const uint32_t *)ctx->tok_pages.p +
+                                       snapmi::kTokCtlMultiRounds,
+                                   sizeof w, hipMemcpyDeviceToHost));
+        }
+        *value = w;
+#endif
     } else if (strcmp(name, "token_pool_pct_now") == 0) {
         *value = ctx->token_pool_now;
     } else if (strcmp(name, "token_pages_asked") == 0 ||
@@ -776,6 +797,32 @@ SNAPMI_API int snapmi_debug_profile(snapmi_ctx *ctx, uint64_t *out16)
     HIP_TRY(ctx, hipMemcpy(out16, ctx->st_prof.p, 16 * sizeof(uint64_t),
                            hipMemcpyDeviceToHost));
     return SNAPMI_OK;
+}
+)
+PROF_TAIL(
+// experiment build SNAPMI_PROFILE=3: the tail records of the last compress
+// call's lane launch (CompressArgs::prof): out[0..2] = start, end and "the
+// ticket was first found empty", out[3 + g] = when lane g went out of work,
+// all on the device's 100 MHz clock; returns the number of lanes, or < 0
+SNAPMI_API int64_t snapmi_debug_lane_tail(snapmi_ctx *ctx, uint64_t *out,
+                                          uint64_t cap)
+{
+    const uint64_t lanes = ctx->prof_tail_lanes;
+    if (!ctx->st_prof.p || cap < 3 + lanes)
+        return -1;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return -1;
+    uint64_t head[3];
+    if (hipMemcpy(head, (const uint64_t *)ctx->st_prof.p + snapmi::kProfTail,
+                  sizeof head, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(out + 3,
+                  (const uint64_t *)ctx->st_prof.p + snapmi::kProfTailLanes,
+                  lanes * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    out[0] = ~head[0];
+    out[1] = head[1];
+    out[2] = ~head[2];
+    return (int64_t)lanes;
 }
 )
 

@@ -2358,7 +2358,10 @@ constexpr uint32_t kLaneRingWords = 64 * 64;
 constexpr uint32_t kLaneTokWords = 64 * 16; // (in 8-byte words: 32 tokens a lane)
 // lane: 0..63 of this wavefront; g: its lane id among all lanes of the launch
 // (its table, its epoch)
-template <bool kSpec>
+// kTail: the form with a run-time depth (options lane_tail_probes,
+// lane_tail_idle_pct); without it the round is the plain one or kSpec's, as
+// compiled, and nothing of the tail's bookkeeping exists.
+template <bool kSpec, bool kTail>
 __device__ __forceinline__ void match_blocks(
     const CompressArgs &a, const uint32_t lane, const uint32_t g,
     __attribute__((address_space(3))) uint32_t *const ring,
@@ -2417,6 +2420,24 @@ __device__ __forceinline__ void match_blocks(
     // the lane's page in hand, and what is left of the wavefront's run
     // (uniform): see tok_page_ask
     uint32_t spare = kNoPage, run_next = 0, run_end = 0;
+    // probes a round resolves (uniform): CompressArgs::lane_depth; raised to
+    // lane_tail_depth, and never lowered again, once this wavefront has seen
+    // the ticket run out (seen_idle) and then reads, every 64 passes of the
+    // loop, that lane_tail_idle lanes of the launch are out of work.  Nothing
+    // waits for anything: a wavefront that reads no fresh count stays as it is.
+    uint32_t depth = a.lane_depth;
+    if (kTail && a.lane_tail_idle == 0 && depth < a.lane_tail_depth)
+        depth = a.lane_tail_depth;
+    auto D = [&]() -> uint32_t { return kTail ? depth : (kSpec ? 2u : 1u); };
+    bool seen_idle = false;
+    uint32_t passes = 0;
+    PROF_TAIL(
+    if (a.prof && lane == 0)
+        atomicMax(&a.prof[kProfTail], ~(unsigned long long)wall_clock64());
+    )
+#ifdef SNAPMI_TESTING
+    uint32_t multi_rounds = 0; // rounds above the launch's own depth
+#endif
     // where token idx goes; the first token of a page takes the page
     auto tok_at = [&](uint32_t idx) -> g_tok * {
         if (idx % kTokPage == 0)
@@ -2435,6 +2456,14 @@ __device__ __forceinline__ void match_blocks(
     };
 
     for (;;) {
+        if (kTail && seen_idle && depth < a.lane_tail_depth &&
+            (++passes & 63) == 0) {
+            const uint32_t idle = __hip_atomic_load(
+                &a.ticket[kTicketIdle], __ATOMIC_RELAXED,
+                __HIP_MEMORY_SCOPE_AGENT);
+            if (uni(idle) >= a.lane_tail_idle)
+                depth = a.lane_tail_depth;
+        }
         // token pages for the lanes that used theirs in the last round (the
         // loop's top is convergent: the run's bounds stay uniform)
         {
@@ -2562,6 +2591,26 @@ __device__ __forceinline__ void match_blocks(
                 }
             }
         }
+        // the lanes that went out of work in this pass count themselves for
+        // the launch's other wavefronts: one atomic
+        if ((kTail || kProfTailBuild) && M_need) {
+            const uint64_t M_out = __ballot(need && out_of_work);
+            if (M_out) {
+                if (kTail && lane == (uint32_t)__builtin_ctzll(M_out))
+                    atomicAdd(&a.ticket[kTicketIdle],
+                              (uint32_t)__builtin_popcountll(M_out));
+                seen_idle = true;
+                PROF_TAIL(
+                if (a.prof) {
+                    const unsigned long long t = wall_clock64();
+                    if (need && out_of_work)
+                        a.prof[kProfTailLanes + g] = t;
+                    if (lane == (uint32_t)__builtin_ctzll(M_out))
+                        atomicMax(&a.prof[kProfTail + 2], ~t);
+                }
+                )
+            }
+        }
         if (__ballot(have) == 0) {
             if (__ballot(!out_of_work) == 0)
                 break;
@@ -2569,6 +2618,10 @@ __device__ __forceinline__ void match_blocks(
         }
         if (!have)
             continue;
+#ifdef SNAPMI_TESTING
+        if (kTail && depth > a.lane_depth)
+            multi_rounds++;
+#endif
 
         // ---- one round ----------------------------------------------------
         // The 17 bytes at pos-1 come from the window (pos = s, or p while a
@@ -2604,20 +2657,33 @@ __device__ __forceinline__ void match_blocks(
         gcptr pa = mode == kExtend ? src + c : (gcptr)(tab + hcur);
         pa = stall ? src_al + hi : pa;
         B16 A = ld128u(pa);
-        // kSpec: the probe behind this one, delta bytes on (r3 ends at
-        // pos + 15: its 12 bytes are in the registers for delta <= 3)
-        uint32_t t0 = 0, t1 = 0, t2 = 0, h2 = 0;
-        bool spec = false;
-        B16 A2 = {{0, 0, 0, 0}};
-        if (kSpec) {
-            const uint32_t delta = mode == kChain ? 1 : s_next - s;
-            spec = mode <= kChain && delta <= 3 && !stall;
-            t0 = __builtin_amdgcn_alignbyte(r1, r0, delta);
-            t1 = __builtin_amdgcn_alignbyte(r2, r1, delta);
-            t2 = __builtin_amdgcn_alignbyte(r3, r2, delta);
-            h2 = hash32(t0, shift);
-            if (spec)
-                A2 = ld128u((gcptr)(tab + h2));
+        // depth > 1: the up to three probes behind this one, should it and
+        // they miss.  Probe k + 1 lies dx[k] bytes on: the skip schedule
+        // (src/compress.rs:207-216; after a copy s + 1, then skip = 32) says
+        // so at the start of the round, and its 12 bytes are in the registers
+        // while dx[k] <= 3 (r3 ends at pos + 15).  Their entries are read
+        // here, in front of everything the round writes.
+        uint32_t hx[3] = {0, 0, 0}, dx[3] = {0, 0, 0};
+        bool okx[3] = {false, false, false};
+        B16 Ax[3] = {{{0, 0, 0, 0}}, {{0, 0, 0, 0}}, {{0, 0, 0, 0}}};
+        if (kSpec || D() > 1) {
+            uint32_t d = mode == kChain ? 1 : s_next - s;
+            uint32_t sk = mode == kChain ? 32 : skip;
+            bool ok = mode <= kChain && !stall;
+#pragma unroll
+            for (uint32_t k = 0; k < 3; k++) {
+                if (k + 1 < D()) { // (uniform)
+                    ok = ok && d <= 3;
+                    dx[k] = d;
+                    okx[k] = ok;
+                    hx[k] = hash32(__builtin_amdgcn_alignbyte(r1, r0, d), shift);
+                    if (ok)
+                        Ax[k] = ld128u((gcptr)(tab + hx[k]));
+                    const uint32_t step = sk >> 5;
+                    d += step;
+                    sk += step;
+                }
+            }
         }
         // (the load is issued HERE, in front of the window's line: a compiler
         // barrier, or it may be sunk behind the fill's wait - two latencies
@@ -2635,8 +2701,12 @@ __device__ __forceinline__ void match_blocks(
         // one wait for the whole round: A is materialised before the branch
         // that uses it (the fill's wait, when there was one, covered it)
         asm volatile("" : "+v"(A.w[0]));
-        if (kSpec)
-            asm volatile("" : "+v"(A2.w[0]));
+        if (kSpec || D() > 1) {
+#pragma unroll
+            for (uint32_t k = 0; k < 3; k++)
+                if (k + 1 < D())
+                    asm volatile("" : "+v"(Ax[k].w[0]));
+        }
         if (stall)
             continue;
 
@@ -2645,6 +2715,8 @@ __device__ __forceinline__ void match_blocks(
         bool tail = false;     // open match within 16 bytes of the block end
         bool finished = false;
         uint32_t mend = 0;
+        const bool was_chain = mode == kChain;
+        const uint32_t s0 = s;
         if (mode <= kChain) {
             if (mode == kChain) {
                 // src/compress.rs:290-297: insert s-1 first; the lookup of s
@@ -2709,62 +2781,87 @@ __device__ __forceinline__ void match_blocks(
                 tail = p + 16 > n;
             }
         }
-        if (kSpec && advance && spec) {
-            // the first probe missed: its advance (src/compress.rs:207-216),
-            // then the probe at the new s with the entry fetched for it
-            const uint32_t s_old = s;
-            const bool was_chain = mode == kChain;
-            s = s_next;
-            const uint32_t step = skip >> 5;
-            s_next = s + step;
-            skip += step;
-            mode = kProbe;
-            advance = false;
-            if (s_next > s_limit) {
-                finished = true;
-            } else {
-                // what this round wrote is newer than what it read
-                if (h2 == hcur) {
-                    A2.w[0] = r0;
-                    A2.w[1] = r1;
-                    A2.w[2] = r2;
-                    A2.w[3] = ((uint32_t)epoch << 16) | s_old;
-                } else if (was_chain && h2 == hprev) {
-                    A2.w[0] = q0;
-                    A2.w[1] = q1;
-                    A2.w[2] = q2;
-                    A2.w[3] = ((uint32_t)epoch << 16) | (s_old - 1);
-                }
-                const unsigned long long p8 =
-                    ((unsigned long long)t1 << 32) | t0;
-                const uint32_t p4 = t2;
-                const bool live = (A2.w[3] >> 16) == (uint32_t)epoch;
-                const uint32_t cand = live ? A2.w[3] & 0xFFFFu : 0;
-                const unsigned long long c8 =
-                    live ? ((unsigned long long)A2.w[1] << 32) | A2.w[0]
-                         : first8;
-                const uint32_t c4 = live ? A2.w[2] : first4b;
-                tab[h2] = (u64x2){
-                    p8, (epoch << 48) | ((unsigned long long)s << 32) | p4};
-                if ((uint32_t)c8 == t0) {
-                    const unsigned long long d8 = c8 ^ p8;
-                    const uint32_t d4 = c4 ^ p4;
-                    const uint32_t m =
-                        d8 ? (uint32_t)__builtin_ctzll(d8) >> 3
-                           : 8 + (d4 ? (uint32_t)__builtin_ctz(d4) >> 3 : 4);
-                    mpos = s;
-                    mcand = cand;
-                    if (m < 12) {
-                        matched = true;
-                        mend = s + m;
+        if (kSpec || D() > 1) {
+#pragma unroll
+            for (uint32_t k = 0; k < 3; k++) {
+                if (k + 1 < D() && advance && okx[k]) {
+                    // the probe in front missed: its advance
+                    // (src/compress.rs:207-216), then the probe at the new s
+                    // with the entry fetched for it
+                    s = s_next;
+                    const uint32_t step = skip >> 5;
+                    s_next = s + step;
+                    skip += step;
+                    mode = kProbe;
+                    advance = false;
+                    if (s_next > s_limit) {
+                        finished = true;
                     } else {
-                        p = s + 12;
-                        c = cand + 12;
-                        mode = kExtend;
-                        tail = p + 16 > n;
+                        const uint32_t t0 =
+                            __builtin_amdgcn_alignbyte(r1, r0, dx[k]);
+                        const uint32_t t1 =
+                            __builtin_amdgcn_alignbyte(r2, r1, dx[k]);
+                        const uint32_t t2 =
+                            __builtin_amdgcn_alignbyte(r3, r2, dx[k]);
+                        // what this round wrote is newer than what it read:
+                        // the chain insert, probe 0, the probes in between -
+                        // the newest of them counts
+                        B16 E = Ax[k];
+                        if (was_chain && hx[k] == hprev) {
+                            E.w[0] = q0;
+                            E.w[1] = q1;
+                            E.w[2] = q2;
+                            E.w[3] = ((uint32_t)epoch << 16) | (s0 - 1);
+                        }
+                        if (hx[k] == hcur) {
+                            E.w[0] = r0;
+                            E.w[1] = r1;
+                            E.w[2] = r2;
+                            E.w[3] = ((uint32_t)epoch << 16) | s0;
+                        }
+#pragma unroll
+                        for (uint32_t j = 0; j < k; j++) {
+                            if (hx[k] == hx[j]) {
+                                E.w[0] = __builtin_amdgcn_alignbyte(r1, r0, dx[j]);
+                                E.w[1] = __builtin_amdgcn_alignbyte(r2, r1, dx[j]);
+                                E.w[2] = __builtin_amdgcn_alignbyte(r3, r2, dx[j]);
+                                E.w[3] = ((uint32_t)epoch << 16) | (s0 + dx[j]);
+                            }
+                        }
+                        const unsigned long long p8 =
+                            ((unsigned long long)t1 << 32) | t0;
+                        const uint32_t p4 = t2;
+                        const bool live = (E.w[3] >> 16) == (uint32_t)epoch;
+                        const uint32_t cand = live ? E.w[3] & 0xFFFFu : 0;
+                        const unsigned long long c8 =
+                            live ? ((unsigned long long)E.w[1] << 32) | E.w[0]
+                                 : first8;
+                        const uint32_t c4 = live ? E.w[2] : first4b;
+                        tab[hx[k]] = (u64x2){
+                            p8,
+                            (epoch << 48) | ((unsigned long long)s << 32) | p4};
+                        if ((uint32_t)c8 == t0) {
+                            const unsigned long long d8 = c8 ^ p8;
+                            const uint32_t d4 = c4 ^ p4;
+                            const uint32_t m =
+                                d8 ? (uint32_t)__builtin_ctzll(d8) >> 3
+                                   : 8 + (d4 ? (uint32_t)__builtin_ctz(d4) >> 3
+                                             : 4);
+                            mpos = s;
+                            mcand = cand;
+                            if (m < 12) {
+                                matched = true;
+                                mend = s + m;
+                            } else {
+                                p = s + 12;
+                                c = cand + 12;
+                                mode = kExtend;
+                                tail = p + 16 > n;
+                            }
+                        } else {
+                            advance = true;
+                        }
                     }
-                } else {
-                    advance = true;
                 }
             }
         }
@@ -2848,29 +2945,35 @@ __device__ __forceinline__ void match_blocks(
         }
     }
     a.lane_epochs[g] = epoch;
+    PROF_TAIL(
+    if (a.prof && lane == 0)
+        atomicMax(&a.prof[kProfTail + 1], (unsigned long long)wall_clock64());
+    )
+#ifdef SNAPMI_TESTING
+    if (kTail && lane == 0 && multi_rounds)
+        atomicAdd(&a.tok_ctl[kTokCtlMultiRounds], multi_rounds);
+#endif
 }
 } // namespace
 
-__global__ __launch_bounds__(64) void k_match_blocks(CompressArgs a)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t ring[kLaneRingWords];
-    __shared__ __attribute__((aligned(16)))
-    unsigned long long tokbuf[kLaneTokWords];
-    match_blocks<false>(
-        a, threadIdx.x, blockIdx.x * 64 + threadIdx.x,
-        (__attribute__((address_space(3))) uint32_t *)ring,
-        (__attribute__((address_space(3))) unsigned long long *)tokbuf);
-}
-__global__ __launch_bounds__(64) void k_match_blocks_spec(CompressArgs a)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t ring[kLaneRingWords];
-    __shared__ __attribute__((aligned(16)))
-    unsigned long long tokbuf[kLaneTokWords];
-    match_blocks<true>(
-        a, threadIdx.x, blockIdx.x * 64 + threadIdx.x,
-        (__attribute__((address_space(3))) uint32_t *)ring,
-        (__attribute__((address_space(3))) unsigned long long *)tokbuf);
-}
+#define SNAPMI_LANE_KERNEL(name, spec, tail)                                  \
+    __global__ __launch_bounds__(64) void name(CompressArgs a)                \
+    {                                                                         \
+        __shared__ __attribute__((aligned(16))) uint32_t ring[kLaneRingWords]; \
+        __shared__ __attribute__((aligned(16)))                               \
+        unsigned long long tokbuf[kLaneTokWords];                             \
+        match_blocks<spec, tail>(                                             \
+            a, threadIdx.x, blockIdx.x * 64 + threadIdx.x,                    \
+            (__attribute__((address_space(3))) uint32_t *)ring,               \
+            (__attribute__((address_space(3))) unsigned long long *)tokbuf);  \
+    }
+// k_match_blocks has the run-time depth (CompressArgs::lane_depth says where
+// it starts); the two with the round as compiled run where the options ask
+// for no more probes than the launch starts with
+SNAPMI_LANE_KERNEL(k_match_blocks, false, true)
+SNAPMI_LANE_KERNEL(k_match_blocks_plain, false, false)
+SNAPMI_LANE_KERNEL(k_match_blocks_spec, true, false)
+#undef SNAPMI_LANE_KERNEL
 
 // Both match finders on every CU (round 5): three wavefronts of the lane
 // kernel - as many as reach the DRAM-transaction ceiling it is bound by
@@ -2881,26 +2984,25 @@ __global__ __launch_bounds__(64) void k_match_blocks_spec(CompressArgs a)
 // tables.  One two-ended ticket: the lanes take blocks from the front of the
 // segment, the windows from its back, until they meet; both write tokens for
 // k_encode_tokens.  (Round 4 split the CUs between the two kernels and gained
-// nothing; here the lanes keep every CU.)
-__global__ __launch_bounds__(kBothWaves * 64) void k_match_both(CompressArgs a)
+// nothing; here the lanes keep every CU.)  k_match_both's lane wavefronts
+// have the run-time depth, k_match_both_plain's the plain round alone.
+namespace {
+template <bool kTail>
+__device__ __forceinline__ void match_both(
+    const CompressArgs &a,
+    __attribute__((address_space(3))) uint32_t *const ring,
+    __attribute__((address_space(3))) unsigned long long *const tokbuf,
+    const lptr16 tables)
 {
-    __shared__ __attribute__((aligned(16)))
-    uint32_t ring[kBothLaneWaves][kLaneRingWords];
-    __shared__ __attribute__((aligned(16)))
-    unsigned long long tokbuf[kBothLaneWaves][kLaneTokWords];
-    __shared__ __attribute__((aligned(16)))
-    uint16_t tables[kBothWaves - kBothLaneWaves][kMaxTable];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = uni(threadIdx.x >> 6);
     if (wave < kBothLaneWaves) {
-        match_blocks<false>(
+        match_blocks<false, kTail>(
             a, lane, (blockIdx.x * kBothLaneWaves + wave) * 64 + lane,
-            (__attribute__((address_space(3))) uint32_t *)&ring[wave][0],
-            (__attribute__((address_space(3))) unsigned long long *)
-                &tokbuf[wave][0]);
+            ring + wave * kLaneRingWords, tokbuf + wave * kLaneTokWords);
         return;
     }
-    const lptr16 table = (lptr16)&tables[wave - kBothLaneWaves][0];
+    const lptr16 table = tables + (wave - kBothLaneWaves) * kMaxTable;
     const uint32_t tbase = (uint32_t)(uintptr_t)table;
     uint32_t nblocks = a.blk_first[a.n_streams];
     if (nblocks > a.host_blocks)
@@ -2914,7 +3016,30 @@ __global__ __launch_bounds__(kBothWaves * 64) void k_match_both(CompressArgs a)
             break;
         compress_one_block_span<false, true>(a, b, lane, table, tbase);
     }
+    PROF_TAIL(
+    if (a.prof && lane == 0)
+        atomicMax(&a.prof[kProfTail + 1], (unsigned long long)wall_clock64());
+    )
 }
+} // namespace
+#define SNAPMI_BOTH_KERNEL(name, tail)                                        \
+    __global__ __launch_bounds__(kBothWaves * 64) void name(CompressArgs a)   \
+    {                                                                         \
+        __shared__ __attribute__((aligned(16)))                               \
+        uint32_t ring[kBothLaneWaves][kLaneRingWords];                        \
+        __shared__ __attribute__((aligned(16)))                               \
+        unsigned long long tokbuf[kBothLaneWaves][kLaneTokWords];             \
+        __shared__ __attribute__((aligned(16)))                               \
+        uint16_t tables[kBothWaves - kBothLaneWaves][kMaxTable];              \
+        match_both<tail>(                                                     \
+            a, (__attribute__((address_space(3))) uint32_t *)&ring[0][0],     \
+            (__attribute__((address_space(3))) unsigned long long *)          \
+                &tokbuf[0][0],                                                \
+            (lptr16)&tables[0][0]);                                           \
+    }
+SNAPMI_BOTH_KERNEL(k_match_both, true)
+SNAPMI_BOTH_KERNEL(k_match_both_plain, false)
+#undef SNAPMI_BOTH_KERNEL
 
 // ---------------------------------------------------------------------
 // K1c: tokens -> Snappy elements, one wavefront per block, 64 tokens per

@@ -170,6 +170,21 @@ struct snapmi_ctx {
     // limit: lane_speculate_max_blocks).
     int lane_speculate = 1;
     uint64_t lane_speculate_max_blocks = 24576;
+    // The tail of a lane-kernel launch (k_match_blocks, k_match_blocks_spec,
+    // the lane wavefronts of k_match_both): once the ticket has run out lanes
+    // only finish, memory falls below its random-access rate and a round
+    // costs its latency.  lane_tail_probes 2..4: a wavefront that has seen
+    // the ticket run out resolves up to that many probes a round from the
+    // moment lane_tail_idle_pct per cent of the launch's lanes are out of
+    // work (0: from the first round); 0 or 1: never (the rounds of the launch
+    // stay what lane_speculate makes them).  Same bytes at every setting.
+    // Measured at cfg2, each time in one process on one table placement
+    // (profiles/lane_tail.json, the timeline in
+    // profiles/lane_tail_timeline.txt): 2 probes from 40 % idle take 2.6 ms
+    // off k_match_both's 107.7 and 1.4 off 110.6 on a second box; 3 and 4
+    // probes cost more than they save.
+    uint32_t lane_tail_probes = 2;
+    uint32_t lane_tail_idle_pct = 40;
     // k_compress_tiny (streams of fewer than 256 bytes, one per LANE, all of
     // their state in LDS): 1 = on (default), 0 = such streams are one-block
     // streams of the block kernels (cross-check, and what round 2 measured)
@@ -311,6 +326,7 @@ struct snapmi_ctx {
     bool dominant_split = false; // ev[4]/ev[5] bracket k_match_blocks
     uint64_t codec_launches = 0;
     uint32_t seam_seq = 0; // the seam's single-launch path: its last ticket
+    uint32_t prof_tail_lanes = 0; // SNAPMI_PROFILE=3: lanes of the last launch
 };
 
 namespace snapmi {

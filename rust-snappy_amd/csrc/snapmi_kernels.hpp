@@ -51,7 +51,8 @@ struct CompressArgs {
     uint32_t *tok_pool;
     uint32_t *tok_pages;
     // [0] pages asked for, [1] blocks spilled, [2] k_redo_spilled's ticket,
-    // from kTokCtlList on: the spilled blocks
+    // [kTokCtlMultiRounds] (test build) rounds of more than one probe; from
+    // kTokCtlList on: the spilled blocks
     uint32_t *tok_ctl;
     uint32_t tok_pool_pages;
     // staging arrays of the window wavefronts of a token-path launch
@@ -76,7 +77,18 @@ struct CompressArgs {
     uint32_t lane_chunks, lane_per_chunk;
     uint32_t *lane_epochs;      // [lanes]
     uint32_t n_lanes;
-    // experiment builds (-DSNAPMI_PROFILE) only: 16 u64 cycle counters
+    // probes a round of the lane match finder resolves (match_blocks): from
+    // the first round lane_depth (1: the plain round, 2: k_match_blocks_spec's;
+    // up to 4), and lane_tail_depth (0 or 1: never more) in a wavefront that
+    // has seen the launch run out of blocks and then read that at least
+    // lane_tail_idle of its lanes are out of work - ticket[kTicketIdle],
+    // which the launch zeroes with the ticket
+    uint32_t lane_depth, lane_tail_depth, lane_tail_idle;
+    // experiment builds (-DSNAPMI_PROFILE) only: 16 u64 cycle counters; with
+    // SNAPMI_PROFILE=3 behind them, from kProfTail on: ~start, end, ~(the
+    // ticket was first found empty) of a lane-kernel launch on the device's
+    // 100 MHz clock (each the maximum over the wavefronts), and from
+    // kProfTailLanes on the clock at which lane g went out of work
     unsigned long long *prof;
     // partial sums of the many-workgroup scans (k_plan_compress_*,
     // k_scan_sizes_*): one per 1024 streams / blocks, + 1
@@ -128,6 +140,13 @@ static_assert(kTokPagesPerBlock + kExcPagesPerBlock <= kPageTabStride, "");
 // ... of a block of at most 8 KiB: 2 049 tokens, 126 exceptions
 constexpr uint32_t kPagesPerSmallBlock = (8192 / 4 + 64 + kTokPage - 1) / kTokPage + 1;
 constexpr uint32_t kTokCtlList = 16;
+constexpr uint32_t kProfTail = 16, kProfTailLanes = 32;
+// word of the ticket's 64-byte line: lanes of the lane match finder that are
+// out of work (words 0 and 1 are the two-ended ticket)
+constexpr uint32_t kTicketIdle = 2;
+// word of tok_ctl (k_redo_spilled's ticket is words 2 and 3), test build
+// only: rounds of the segment's lane wavefronts that ran at more than one probe
+constexpr uint32_t kTokCtlMultiRounds = 4;
 constexpr uint32_t kTokStageWords = kMaxTokens + 2 * (kMaxTokens / 16) + 28; // 128-byte multiple
 constexpr uint32_t kTokSpilled = 0xFFFFFFFEu; // in ntok: see tok_pool
 constexpr uint32_t kTokLiteral = 61, kTokException = 62;
@@ -213,6 +232,12 @@ __global__ void k_compress_small2k(CompressArgs a);  // [1024, 2048)
 __global__ void k_match_blocks(CompressArgs a);
 __global__ void k_match_blocks_spec(CompressArgs a); // launches with blocks <= lanes
 __global__ void k_match_both(CompressArgs a); // 3 lane + 2 window wavefronts per CU
+// k_match_blocks and k_match_both take a run-time number of probes a round
+// (options lane_tail_probes, lane_tail_idle_pct); where the options ask for
+// no more than the launch starts with, the forms with the plain round alone
+// (and k_match_blocks_spec) run: they spare the round a branch and 18 VGPRs
+__global__ void k_match_blocks_plain(CompressArgs a);
+__global__ void k_match_both_plain(CompressArgs a);
 __global__ void k_encode_tokens(CompressArgs a);
 __global__ void k_scan_sizes(CompressArgs a);
 __global__ void k_compact(CompressArgs a);

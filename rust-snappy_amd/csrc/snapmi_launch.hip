@@ -246,12 +246,18 @@ static void launch_match(const RouteOptions &o, const CompressRoute &route,
         break;
     case MatchKernel::both:
         a.tok_stage_wave0 = kBothLaneWaves;
-        hipLaunchKernelGGL(k_match_both, grid, dim3(kBothWaves * 64), 0, s,
-                           a);
+        hipLaunchKernelGGL(a.lane_tail_depth > 1 ? k_match_both
+                                                 : k_match_both_plain,
+                           grid, dim3(kBothWaves * 64), 0, s, a);
         break;
     case MatchKernel::blocks:
-        hipLaunchKernelGGL(g.spec ? k_match_blocks_spec : k_match_blocks, grid,
-                           dim3(64), 0, s, a);
+        a.lane_depth = g.spec ? 2 : 1;
+        // (the tail form only where it would ever run more probes)
+        hipLaunchKernelGGL(a.lane_tail_depth > a.lane_depth
+                               ? k_match_blocks
+                               : (g.spec ? k_match_blocks_spec
+                                         : k_match_blocks_plain),
+                           grid, dim3(64), 0, s, a);
         break;
     case MatchKernel::none:
         break;
@@ -319,6 +325,9 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     a.lane_chunks = 0;
     a.lane_per_chunk = 0;
     a.n_lanes = 0;
+    a.lane_depth = 1;
+    a.lane_tail_depth = 0;
+    a.lane_tail_idle = 0;
     a.tok_base = 0;
     a.small_limit = (uint32_t)small_stream_limit(o);
     a.cls_lo = 0;
@@ -403,6 +412,18 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
             a.lane_chunks = ctx->lane_chunk_count;
             a.lane_per_chunk = ctx->lane_per_chunk;
             a.n_lanes = route.lanes;
+            // options lane_tail_probes, lane_tail_idle_pct: lanes out of
+            // work from which a wavefront resolves more probes a round (one
+            // lane at least: 0 means from the first round)
+            if (ctx->lane_tail_probes > 1) {
+                const uint64_t idle =
+                    ((uint64_t)route.lanes * ctx->lane_tail_idle_pct + 99) /
+                    100;
+                a.lane_tail_depth = ctx->lane_tail_probes;
+                a.lane_tail_idle = ctx->lane_tail_idle_pct == 0 ? 0
+                                   : idle                       ? (uint32_t)idle
+                                                                : 1;
+            }
         }
     }
     a.prof = nullptr;
@@ -412,6 +433,17 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     HIP_TRY(ctx, hipMemsetAsync(ctx->st_prof.p, 0, 16 * sizeof(uint64_t),
                                 ctx->stream));
     a.prof = (unsigned long long *)ctx->st_prof.p;
+    )
+    PROF_TAIL(
+    {
+        const size_t bytes =
+            (size_t)(kProfTailLanes + route.lanes) * sizeof(uint64_t);
+        if ((rc = reserve(ctx, ctx->st_prof, bytes)))
+            return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->st_prof.p, 0, bytes, ctx->stream));
+        a.prof = (unsigned long long *)ctx->st_prof.p;
+        ctx->prof_tail_lanes = route.lanes;
+    }
     )
 
     hipStream_t s = ctx->stream;

@@ -12,9 +12,26 @@
 //                wait is counted where the product build has it - in the
 //                phase that first needs the data)
 //   COUNT(x)     x++
+//
+// SNAPMI_PROFILE=3 (libsnapmi_profile3.so, read by tests/hw/lane_tail.py) is
+// the timeline of a lane-kernel launch's tail and nothing else - PROF, TICK
+// and COUNT are nothing there, so the window wavefronts of k_match_both run
+// the product's code:
+//   PROF_TAIL(code)  the records of match_blocks: the device clock at which
+//                    the launch started, ended, first found the ticket empty,
+//                    and at which every lane went out of work
+//                    (CompressArgs::prof from kProfTail on)
 #pragma once
 
-#ifdef SNAPMI_PROFILE
+#if defined(SNAPMI_PROFILE) && SNAPMI_PROFILE == 3
+#define PROF_TAIL(...) __VA_ARGS__
+constexpr bool kProfTailBuild = true;
+#else
+#define PROF_TAIL(...)
+constexpr bool kProfTailBuild = false;
+#endif
+
+#if defined(SNAPMI_PROFILE) && SNAPMI_PROFILE != 3
 #define PROF(...) __VA_ARGS__
 #if SNAPMI_PROFILE == 2
 #define TICK_WAIT()

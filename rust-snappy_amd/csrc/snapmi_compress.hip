@@ -52,6 +52,7 @@
 
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
+#include "snapmi_scan.hpp"
 #include "snapmi_span.hpp"
 
 namespace snapmi {
@@ -3183,41 +3184,11 @@ __global__ __launch_bounds__(64) void k_encode_tokens(CompressArgs a)
 
 // ---------------------------------------------------------------------
 // Plan: per-stream validation + block table.  One workgroup of 1024 threads
-// walks the streams 1024 at a time with a workgroup-wide exclusive scan.
+// walks the streams 1024 at a time with the workgroup scan of
+// snapmi_scan.hpp (as every scan below: what a kernel names is what it loads
+// and stores).
 // Reference checks: src/compress.rs:104-125.
 // ---------------------------------------------------------------------
-__device__ __forceinline__ uint2 wg_scan2(uint32_t x, uint32_t y,
-                                          uint2 *wave_tot, uint2 *total)
-{
-    // inclusive scan inside the wave
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t sx = x, sy = y;
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint32_t tx = __shfl_up(sx, o), ty = __shfl_up(sy, o);
-        if (lane >= o) {
-            sx += tx;
-            sy += ty;
-        }
-    }
-    if (lane == 63)
-        wave_tot[w] = make_uint2(sx, sy);
-    __syncthreads();
-    uint32_t bx = 0, by = 0, allx = 0, ally = 0;
-    const uint32_t nw = blockDim.x >> 6;
-    for (uint32_t i = 0; i < nw; i++) {
-        const uint2 t = wave_tot[i];
-        if (i < w) {
-            bx += t.x;
-            by += t.y;
-        }
-        allx += t.x;
-        ally += t.y;
-    }
-    __syncthreads();
-    *total = make_uint2(allx, ally);
-    return make_uint2(bx + sx - x, by + sy - y); // exclusive
-}
-
 namespace {
 // blocks of stream i, or 0 for a stream that is rejected, empty or tiny
 // (reference src/compress.rs:104-125)
@@ -3253,142 +3224,45 @@ __device__ __forceinline__ uint32_t plan_blocks(const CompressArgs &a,
         return 0; // k_compress_tiny's / _small's: no blocks, they write out_lens
     return (uint32_t)((len + kMaxBlock - 1) / kMaxBlock);
 }
-} // namespace
-
-__global__ __launch_bounds__(1024) void k_plan_compress(CompressArgs a)
+// item i of the planner's scan: its blocks and its scratch slots
+__device__ __forceinline__ void plan_load(const CompressArgs &a, uint32_t i,
+                                          uint32_t (&x)[2])
 {
-    __shared__ uint2 wave_tot[16];
-    uint32_t carry_b = 0, carry_s = 0;
-    for (uint32_t base = 0; base < a.n_streams; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t nb = i < a.n_streams ? plan_blocks(a, i, true) : 0;
-        uint2 tot;
-        const uint2 ex = wg_scan2(nb, nb ? nb - 1 : 0, wave_tot, &tot);
-        uint32_t fb = carry_b + ex.x, fs = carry_s + ex.y;
-        if (i < a.n_streams) {
-            // The launch was sized from the host's copy of the lengths; a
-            // stream that does not fit in it is rejected, never overrun.
-            if (nb && ((uint64_t)fb + nb > a.host_blocks ||
-                       (uint64_t)fs + (nb - 1) > a.host_slots))
-                set_error(a.errs, i, SNAPMI_E_ARGUMENT, a.in_lens[i], 0, 0);
-            a.blk_first[i] = fb;
-            a.slot_first[i] = fs;
-        }
-        carry_b += tot.x;
-        carry_s += tot.y;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a.blk_first[a.n_streams] = carry_b;
-        a.slot_first[a.n_streams] = carry_s;
-    }
+    x[0] = plan_blocks(a, i, true);
+    x[1] = x[0] ? x[0] - 1 : 0;
 }
-
-// Exclusive scan of blk_size (u32) into blk_off (u64) over the blocks
-// [blk_lo, blk_hi), one workgroup; blk_off[blk_lo] carries over from the
-// segment in front.
-__global__ __launch_bounds__(1024) void k_scan_sizes(CompressArgs a)
+// ... and where they start.  The launch was sized from the host's copy of
+// the lengths; a stream that does not fit in it is rejected, never overrun.
+__device__ __forceinline__ void plan_store(const CompressArgs &a, uint32_t i,
+                                           uint32_t nb, uint32_t fb,
+                                           uint32_t fs)
 {
-    __shared__ uint64_t wave_tot[16];
-    const uint32_t *blk_size = a.blk_size;
-    uint64_t *blk_off = a.blk_off;
-    uint32_t nblocks = a.blk_first[a.n_streams];
-    if (nblocks > a.host_blocks)
-        nblocks = a.host_blocks;
-    if (nblocks > a.blk_hi)
-        nblocks = a.blk_hi;
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t carry = a.blk_lo ? blk_off[a.blk_lo] : 0;
-    __syncthreads(); // (blk_off[blk_lo] is rewritten below)
-    for (uint32_t base = a.blk_lo; base < nblocks; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        const uint64_t x = i < nblocks ? blk_size[i] : 0;
-        uint64_t sx = x;
-        for (uint32_t o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(sx, o);
-            if (lane >= o)
-                sx += t;
-        }
-        if (lane == 63)
-            wave_tot[w] = sx;
-        __syncthreads();
-        uint64_t before = 0, all = 0;
-        for (uint32_t j = 0; j < (blockDim.x >> 6); j++) {
-            const uint64_t t = wave_tot[j];
-            if (j < w)
-                before += t;
-            all += t;
-        }
-        __syncthreads();
-        if (i < nblocks)
-            blk_off[i] = carry + before + sx - x;
-        carry += all;
-    }
-    if (threadIdx.x == 0 && nblocks >= a.blk_lo)
-        blk_off[nblocks] = carry;
-}
-
-// ---------------------------------------------------------------------
-// The same two scans on many workgroups, for batches of many streams /
-// blocks (10.7 M streams of 200 bytes: the one-workgroup kernels above took
-// 27.8 ms and 41 x 0.46 ms of a 104 ms pass).  Three launches each: (a) every
-// workgroup scans its 1024 items and leaves its total, (b) one workgroup
-// scans the totals, (c) every workgroup adds its offset.
-// ---------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_plan_compress_a(CompressArgs a)
-{
-    __shared__ uint2 wave_tot[16];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t nb = i < a.n_streams ? plan_blocks(a, i, true) : 0;
-    uint2 tot;
-    const uint2 ex = wg_scan2(nb, nb ? nb - 1 : 0, wave_tot, &tot);
-    if (i < a.n_streams) {
-        a.blk_first[i] = ex.x;  // within this workgroup, for now
-        a.slot_first[i] = ex.y;
-    }
-    if (threadIdx.x == 0)
-        a.plan_part[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(1024) void k_plan_compress_b(CompressArgs a,
-                                                          uint32_t nparts)
-{
-    __shared__ uint2 wave_tot[16];
-    uint32_t carry_b = 0, carry_s = 0;
-    for (uint32_t base = 0; base < nparts; base += blockDim.x) {
-        const uint32_t j = base + threadIdx.x;
-        const uint2 v = j < nparts ? a.plan_part[j] : make_uint2(0, 0);
-        uint2 tot;
-        const uint2 ex = wg_scan2(v.x, v.y, wave_tot, &tot);
-        if (j < nparts)
-            a.plan_part[j] = make_uint2(carry_b + ex.x, carry_s + ex.y);
-        carry_b += tot.x;
-        carry_s += tot.y;
-    }
-    if (threadIdx.x == 0) {
-        a.blk_first[a.n_streams] = carry_b;
-        a.slot_first[a.n_streams] = carry_s;
-    }
-}
-
-__global__ __launch_bounds__(1024) void k_plan_compress_c(CompressArgs a)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_streams)
-        return;
-    const uint2 off = a.plan_part[blockIdx.x];
-    const uint32_t fb = a.blk_first[i] + off.x, fs = a.slot_first[i] + off.y;
-    const uint32_t nb = plan_blocks(a, i, false);
-    // The launch was sized from the host's copy of the lengths; a stream
-    // that does not fit in it is rejected, never overrun.
     if (nb && ((uint64_t)fb + nb > a.host_blocks ||
                (uint64_t)fs + (nb - 1) > a.host_slots))
         set_error(a.errs, i, SNAPMI_E_ARGUMENT, a.in_lens[i], 0, 0);
     a.blk_first[i] = fb;
     a.slot_first[i] = fs;
 }
+} // namespace
+
+__global__ __launch_bounds__(1024) void k_plan_compress(CompressArgs a)
+{
+    uint32_t carry[2] = {0, 0};
+    wg_scan_strided(
+        a.n_streams, carry,
+        [&](uint32_t i, uint32_t (&x)[2]) { plan_load(a, i, x); },
+        [&](uint32_t i, const uint32_t (&x)[2], const uint32_t (&ex)[2]) {
+            plan_store(a, i, x[0], ex[0], ex[1]);
+        });
+    if (threadIdx.x == 0) {
+        a.blk_first[a.n_streams] = carry[0];
+        a.slot_first[a.n_streams] = carry[1];
+    }
+}
 
 namespace {
+// the blocks k_scan_sizes* scan end here: what the plan counted, inside what
+// the host sized and inside this segment
 __device__ __forceinline__ uint32_t scan_nblocks(const CompressArgs &a)
 {
     uint32_t nblocks = a.blk_first[a.n_streams];
@@ -3398,78 +3272,102 @@ __device__ __forceinline__ uint32_t scan_nblocks(const CompressArgs &a)
         nblocks = a.blk_hi;
     return nblocks;
 }
-// exclusive scan of x over the workgroup (u64), total in *all
-__device__ __forceinline__ uint64_t wg_scan64(uint64_t x, uint64_t *wave_tot,
-                                              uint64_t *all)
-{
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t sx = x;
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(sx, o);
-        if (lane >= o)
-            sx += t;
-    }
-    if (lane == 63)
-        wave_tot[w] = sx;
-    __syncthreads();
-    uint64_t before = 0, tot = 0;
-    for (uint32_t j = 0; j < (blockDim.x >> 6); j++) {
-        const uint64_t t = wave_tot[j];
-        if (j < w)
-            before += t;
-        tot += t;
-    }
-    __syncthreads();
-    *all = tot;
-    return before + sx - x;
-}
 } // namespace
 
-// part64[0, nparts): workgroup totals, then offsets; part64[nparts]: the carry
-// from the segment in front (blk_off[blk_lo] before it is rewritten)
+// Exclusive scan of blk_size (u32) into blk_off (u64) over the blocks
+// [blk_lo, blk_hi), one workgroup; blk_off[blk_lo] carries over from the
+// segment in front.
+__global__ __launch_bounds__(1024) void k_scan_sizes(CompressArgs a)
+{
+    const uint32_t nblocks = scan_nblocks(a);
+    uint64_t carry[1] = {a.blk_lo ? a.blk_off[a.blk_lo] : 0};
+    __syncthreads(); // (blk_off[blk_lo] is rewritten below)
+    wg_scan_strided(
+        nblocks > a.blk_lo ? nblocks - a.blk_lo : 0, carry,
+        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = a.blk_size[a.blk_lo + i]; },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            a.blk_off[a.blk_lo + i] = ex[0];
+        });
+    if (threadIdx.x == 0 && nblocks >= a.blk_lo)
+        a.blk_off[nblocks] = carry[0];
+}
+
+// ---------------------------------------------------------------------
+// The same two scans on many workgroups, for batches of many streams /
+// blocks (10.7 M streams of 200 bytes: the one-workgroup kernels above took
+// 27.8 ms and 41 x 0.46 ms of a 104 ms pass).  Three launches each, the
+// halves of snapmi_scan.hpp: (a) wg_scan_a, (b) wg_scan_b, (c) wg_scan_c.
+// ---------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_plan_compress_a(CompressArgs a)
+{
+    wg_scan_a<uint32_t, 2>(
+        a.n_streams, (uint32_t *)a.plan_part,
+        [&](uint32_t i, uint32_t (&x)[2]) { plan_load(a, i, x); },
+        [&](uint32_t i, const uint32_t (&)[2], const uint32_t (&ex)[2]) {
+            a.blk_first[i] = ex[0]; // within this workgroup, for now
+            a.slot_first[i] = ex[1];
+        });
+}
+
+__global__ __launch_bounds__(1024) void k_plan_compress_b(CompressArgs a,
+                                                          uint32_t nparts)
+{
+    uint32_t carry[2] = {0, 0};
+    wg_scan_b((uint32_t *)a.plan_part, nparts, carry);
+    if (threadIdx.x == 0) {
+        a.blk_first[a.n_streams] = carry[0];
+        a.slot_first[a.n_streams] = carry[1];
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_plan_compress_c(CompressArgs a)
+{
+    wg_scan_c<uint32_t, 2>(
+        a.n_streams, (const uint32_t *)a.plan_part,
+        [&](uint32_t i, const uint32_t (&off)[2]) {
+            // (its own loads first: they are in flight beside plan_blocks')
+            const uint32_t fb = a.blk_first[i] + off[0];
+            const uint32_t fs = a.slot_first[i] + off[1];
+            plan_store(a, i, plan_blocks(a, i, false), fb, fs);
+        });
+}
+
+// scan_part[0, nparts): workgroup totals, then offsets; scan_part[nparts]: the
+// carry from the segment in front (blk_off[blk_lo] before it is rewritten)
 __global__ __launch_bounds__(1024) void k_scan_sizes_a(CompressArgs a,
                                                        uint32_t nparts)
 {
-    __shared__ uint64_t wave_tot[16];
     const uint32_t nblocks = scan_nblocks(a);
-    const uint32_t i = a.blk_lo + blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0)
         a.scan_part[nparts] = a.blk_lo ? a.blk_off[a.blk_lo] : 0;
     __syncthreads();
-    const uint64_t x = i < nblocks ? a.blk_size[i] : 0;
-    uint64_t all;
-    const uint64_t ex = wg_scan64(x, wave_tot, &all);
-    if (i < nblocks)
-        a.blk_off[i] = ex;
-    if (threadIdx.x == 0)
-        a.scan_part[blockIdx.x] = all;
+    wg_scan_a<uint64_t, 1>(
+        nblocks > a.blk_lo ? nblocks - a.blk_lo : 0, (uint64_t *)a.scan_part,
+        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = a.blk_size[a.blk_lo + i]; },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            a.blk_off[a.blk_lo + i] = ex[0];
+        });
 }
 
 __global__ __launch_bounds__(1024) void k_scan_sizes_b(CompressArgs a,
                                                        uint32_t nparts)
 {
-    __shared__ uint64_t wave_tot[16];
     const uint32_t nblocks = scan_nblocks(a);
-    uint64_t carry = a.scan_part[nparts];
-    for (uint32_t base = 0; base < nparts; base += blockDim.x) {
-        const uint32_t j = base + threadIdx.x;
-        const uint64_t v = j < nparts ? a.scan_part[j] : 0;
-        uint64_t all;
-        const uint64_t ex = wg_scan64(v, wave_tot, &all);
-        if (j < nparts)
-            a.scan_part[j] = carry + ex;
-        carry += all;
-    }
+    uint64_t carry[1] = {a.scan_part[nparts]};
+    wg_scan_b((uint64_t *)a.scan_part, nparts, carry);
     if (threadIdx.x == 0 && nblocks >= a.blk_lo)
-        a.blk_off[nblocks] = carry;
+        a.blk_off[nblocks] = carry[0];
 }
 
 __global__ __launch_bounds__(1024) void k_scan_sizes_c(CompressArgs a)
 {
     const uint32_t nblocks = scan_nblocks(a);
-    const uint32_t i = a.blk_lo + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nblocks)
-        a.blk_off[i] += a.scan_part[blockIdx.x];
+    wg_scan_c<uint64_t, 1>(
+        nblocks > a.blk_lo ? nblocks - a.blk_lo : 0,
+        (const uint64_t *)a.scan_part,
+        [&](uint32_t i, const uint64_t (&off)[1]) {
+            a.blk_off[a.blk_lo + i] += off[0];
+        });
 }
 
 // Direct encoding (k_encode_tokens wrote every block at its final position):
@@ -3551,41 +3449,34 @@ __global__ __launch_bounds__(256) void k_compact(CompressArgs a)
 // ---------------------------------------------------------------------
 // The block index of snapmi_compress_batch_indexed (snapmi_blockindex.hpp):
 // first[] is the exclusive scan of the streams' entry counts - on one
-// workgroup, or as (a) (b) (c) like the scans above -, and behind everything
-// else of the batch one thread per entry reads what the compressor already
-// knows: the varint's length, blk_off, the stream's length.
+// workgroup, or as wg_scan_a, _b, _c like the scans above -, and behind
+// everything else of the batch one thread per entry reads what the compressor
+// already knows: the varint's length, blk_off, the stream's length.
 // ---------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_index_first(const uint64_t *in_lens,
                                                       uint32_t n,
                                                       uint64_t *first)
 {
-    __shared__ uint64_t wave_tot[16];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < n; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        const uint64_t x = i < n ? bi_entries(in_lens[i]) : 0;
-        uint64_t all;
-        const uint64_t ex = wg_scan64(x, wave_tot, &all);
-        if (i < n)
-            first[i] = carry + ex;
-        carry += all;
-    }
+    uint64_t carry[1] = {0};
+    wg_scan_strided(
+        n, carry,
+        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = bi_entries(in_lens[i]); },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            first[i] = ex[0];
+        });
     if (threadIdx.x == 0)
-        first[n] = carry;
+        first[n] = carry[0];
 }
 
 __global__ __launch_bounds__(1024) void k_index_first_a(
     const uint64_t *in_lens, uint32_t n, uint64_t *first, uint64_t *part)
 {
-    __shared__ uint64_t wave_tot[16];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t x = i < n ? bi_entries(in_lens[i]) : 0;
-    uint64_t all;
-    const uint64_t ex = wg_scan64(x, wave_tot, &all);
-    if (i < n)
-        first[i] = ex;
-    if (threadIdx.x == 0)
-        part[blockIdx.x] = all;
+    wg_scan_a<uint64_t, 1>(
+        n, part,
+        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = bi_entries(in_lens[i]); },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            first[i] = ex[0];
+        });
 }
 
 __global__ __launch_bounds__(1024) void k_index_first_b(uint32_t n,
@@ -3593,28 +3484,19 @@ __global__ __launch_bounds__(1024) void k_index_first_b(uint32_t n,
                                                         uint64_t *part,
                                                         uint32_t nparts)
 {
-    __shared__ uint64_t wave_tot[16];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nparts; base += blockDim.x) {
-        const uint32_t j = base + threadIdx.x;
-        const uint64_t v = j < nparts ? part[j] : 0;
-        uint64_t all;
-        const uint64_t ex = wg_scan64(v, wave_tot, &all);
-        if (j < nparts)
-            part[j] = carry + ex;
-        carry += all;
-    }
+    uint64_t carry[1] = {0};
+    wg_scan_b(part, nparts, carry);
     if (threadIdx.x == 0)
-        first[n] = carry;
+        first[n] = carry[0];
 }
 
 __global__ __launch_bounds__(1024) void k_index_first_c(uint32_t n,
                                                         uint64_t *first,
                                                         const uint64_t *part)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        first[i] += part[blockIdx.x];
+    wg_scan_c<uint64_t, 1>(
+        n, part,
+        [&](uint32_t i, const uint64_t (&off)[1]) { first[i] += off[0]; });
 }
 
 // Entry j of stream st: the varint's length plus the compressed bytes of the

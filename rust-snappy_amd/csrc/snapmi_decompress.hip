@@ -43,6 +43,7 @@
 // gone; 354 -> 16 ms at cfg2) and what bounds each of them.
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
+#include "snapmi_scan.hpp"
 
 namespace snapmi {
 
@@ -2900,41 +2901,6 @@ __global__ __launch_bounds__(256) void k_index_finish(IndexArgs x)
 // scratch.
 // ---------------------------------------------------------------------
 namespace {
-// exclusive scan of (x, y) over the workgroup, totals in all[2]
-__device__ __forceinline__ void range_scan2(uint64_t &x, uint64_t &y,
-                                            uint64_t (*wave_tot)[2],
-                                            uint64_t *all)
-{
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t sx = x, sy = y;
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint64_t tx = __shfl_up(sx, o), ty = __shfl_up(sy, o);
-        if (lane >= o) {
-            sx += tx;
-            sy += ty;
-        }
-    }
-    if (lane == 63) {
-        wave_tot[w][0] = sx;
-        wave_tot[w][1] = sy;
-    }
-    __syncthreads();
-    uint64_t bx = 0, by = 0, tx = 0, ty = 0;
-    for (uint32_t j = 0; j < (blockDim.x >> 6); j++) {
-        if (j < w) {
-            bx += wave_tot[j][0];
-            by += wave_tot[j][1];
-        }
-        tx += wave_tot[j][0];
-        ty += wave_tot[j][1];
-    }
-    __syncthreads();
-    all[0] = tx;
-    all[1] = ty;
-    x = bx + sx - x;
-    y = by + sy - y;
-}
-
 // what range r of the device arrays asks for (the count clamped: the sums of
 // m < 2^31 of them cannot wrap)
 __device__ __forceinline__ uint64_t range_count(const RangeArgs &x, uint64_t r,
@@ -2974,52 +2940,35 @@ __device__ __forceinline__ void range_fail(const RangeArgs &x, uint64_t r,
 }
 } // namespace
 
+// (the three launches of snapmi_scan.hpp; part: pieces and rooms per
+// workgroup, and nobody wants the totals)
 __global__ __launch_bounds__(1024) void k_range_scan_a(RangeArgs x)
 {
-    __shared__ uint64_t wave_tot[16][2];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t c = 0, e = 0;
-    if (i < x.mg)
-        range_slots(x, (uint64_t)x.r0 + i, &c, &e);
-    uint64_t all[2];
-    range_scan2(c, e, wave_tot, all);
-    if (i < x.mg) {
-        x.slot[x.r0 + i] = c;
-        x.eslot[x.r0 + i] = e;
-    }
-    if (threadIdx.x == 0) {
-        x.part[2 * blockIdx.x] = all[0];
-        x.part[2 * blockIdx.x + 1] = all[1];
-    }
+    wg_scan_a<uint64_t, 2>(
+        x.mg, x.part,
+        [&](uint32_t i, uint64_t (&v)[2]) {
+            range_slots(x, (uint64_t)x.r0 + i, &v[0], &v[1]);
+        },
+        [&](uint32_t i, const uint64_t (&)[2], const uint64_t (&ex)[2]) {
+            x.slot[x.r0 + i] = ex[0];
+            x.eslot[x.r0 + i] = ex[1];
+        });
 }
 
 __global__ __launch_bounds__(1024) void k_range_scan_b(RangeArgs x,
                                                        uint32_t nparts)
 {
-    __shared__ uint64_t wave_tot[16][2];
     uint64_t carry[2] = {0, 0};
-    for (uint32_t base = 0; base < nparts; base += blockDim.x) {
-        const uint32_t j = base + threadIdx.x;
-        uint64_t c = j < nparts ? x.part[2 * j] : 0;
-        uint64_t e = j < nparts ? x.part[2 * j + 1] : 0;
-        uint64_t all[2];
-        range_scan2(c, e, wave_tot, all);
-        if (j < nparts) {
-            x.part[2 * j] = carry[0] + c;
-            x.part[2 * j + 1] = carry[1] + e;
-        }
-        carry[0] += all[0];
-        carry[1] += all[1];
-    }
+    wg_scan_b(x.part, nparts, carry);
 }
 
 __global__ __launch_bounds__(1024) void k_range_scan_c(RangeArgs x)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < x.mg) {
-        x.slot[x.r0 + i] += x.part[2 * blockIdx.x];
-        x.eslot[x.r0 + i] += x.part[2 * blockIdx.x + 1];
-    }
+    wg_scan_c<uint64_t, 2>(x.mg, x.part,
+                           [&](uint32_t i, const uint64_t (&off)[2]) {
+                               x.slot[x.r0 + i] += off[0];
+                               x.eslot[x.r0 + i] += off[1];
+                           });
 }
 
 // a thread per range: everything that can be said without its pieces
@@ -3608,7 +3557,6 @@ __global__ __launch_bounds__(256) void k_write_patch(WriteArgs x)
 // a workgroup per touched stream of the group
 __global__ __launch_bounds__(256) void k_write_sizes(WriteArgs x)
 {
-    __shared__ uint64_t wave_tot[16][2];
     __shared__ uint64_t wave_bad[4];
     const uint32_t t = x.t0 + blockIdx.x;
     if (x.st_state[t] != 1) // k_write_plan wrote its out_lens and errs
@@ -3646,28 +3594,24 @@ __global__ __launch_bounds__(256) void k_write_sizes(WriteArgs x)
     // blockDim.x blocks a stride
     const uint64_t *e = x.index + x.first[s];
     uint64_t *cum = x.tb_cum + ba + t;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nt; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        uint64_t d = 0, none = 0;
-        if (i < nt) {
+    uint64_t carry[1] = {0};
+    wg_scan_strided(
+        nt, carry,
+        [&](uint32_t i, uint64_t (&d)[1]) {
             const uint32_t j = ba + i - x.b0;
             const uint64_t k = x.tb_k[ba + i];
-            d = x.z_outlen[j] - varint_len(x.z_inlen[j]) - (e[k + 1] - e[k]);
-        }
-        uint64_t all[2];
-        range_scan2(d, none, wave_tot, all);
-        if (i < nt)
-            cum[i] = carry + d;
-        carry += all[0];
-    }
+            d[0] = x.z_outlen[j] - varint_len(x.z_inlen[j]) - (e[k + 1] - e[k]);
+        },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            cum[i] = ex[0];
+        });
     if (threadIdx.x != 0)
         return;
-    cum[nt] = carry;
+    cum[nt] = carry[0];
     const uint64_t dlen = x.st_dlen[t];
     const uint32_t hn = varint_len(dlen);
     // (the last old entry is in_len: bi_range_stream_usable)
-    const uint64_t new_len = x.in_lens[s] + hn - x.st_hdr[t] + carry;
+    const uint64_t new_len = x.in_lens[s] + hn - x.st_hdr[t] + carry[0];
     const uint64_t cap = x.out_caps[s];
     if (!bi_write_fits(cap, new_len)) {
         write_fail(x, t, s, SNAPMI_BUFFER_TOO_SMALL, cap, new_len, 0);
@@ -3689,21 +3633,18 @@ __global__ __launch_bounds__(256) void k_write_sizes(WriteArgs x)
 // a job per block for a stream that passed, none for the others
 __global__ __launch_bounds__(1024) void k_write_jobs(WriteArgs x)
 {
-    __shared__ uint64_t wave_tot[16][2];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < x.tg; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        uint64_t c = 0, none = 0;
-        if (i < x.tg && x.st_state[x.t0 + i] == 2)
-            c = bi_blocks(x.st_dlen[x.t0 + i]);
-        uint64_t all[2];
-        range_scan2(c, none, wave_tot, all);
-        if (i < x.tg)
-            x.jobs_first[i] = carry + c;
-        carry += all[0];
-    }
+    uint64_t carry[1] = {0};
+    wg_scan_strided(
+        x.tg, carry,
+        [&](uint32_t i, uint64_t (&c)[1]) {
+            if (x.st_state[x.t0 + i] == 2)
+                c[0] = bi_blocks(x.st_dlen[x.t0 + i]);
+        },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            x.jobs_first[i] = ex[0];
+        });
     if (threadIdx.x == 0)
-        x.jobs_first[x.tg] = carry;
+        x.jobs_first[x.tg] = carry[0];
 }
 
 // The copies: the wavefronts of a fixed grid take the jobs in turn (the host

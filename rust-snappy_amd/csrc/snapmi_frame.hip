@@ -15,7 +15,7 @@
 //                     table lookups, combined by GF(2) multiplication
 //   k_frame_chunks    compress side: chunk descriptors for the raw compressor
 //   k_frame_sizes     compressed-vs-stored decision (src/frame.rs:85) + sizes
-//   k_scan_u64        exclusive scan (one workgroup)
+//   k_scan_u64        exclusive scan (one workgroup; snapmi_scan.hpp)
 //   k_frame_emit      headers + payloads into the framed stream
 //   k_frame_walk      decode side: sequential walk over the chunk headers
 //                     (the format has no index) with the reference's checks
@@ -35,6 +35,7 @@
 #include "snapmi_hostpipe.hpp"
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
+#include "snapmi_scan.hpp"
 #include "snapmi_framewalk.hpp"
 
 using namespace snapmi;
@@ -188,35 +189,14 @@ __global__ void k_frame_sizes(FrameCompressArgs a)
 __global__ __launch_bounds__(1024) void k_scan_u64(const uint64_t *in,
                                                    uint64_t *out, uint32_t n)
 {
-    __shared__ uint64_t wave_tot[16];
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < n; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        const uint64_t x = i < n ? in[i] : 0;
-        uint64_t sx = x;
-        for (uint32_t o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(sx, o);
-            if (lane >= o)
-                sx += t;
-        }
-        if (lane == 63)
-            wave_tot[w] = sx;
-        __syncthreads();
-        uint64_t before = 0, all = 0;
-        for (uint32_t j = 0; j < (blockDim.x >> 6); j++) {
-            const uint64_t t = wave_tot[j];
-            if (j < w)
-                before += t;
-            all += t;
-        }
-        __syncthreads();
-        if (i < n)
-            out[i] = carry + before + sx - x;
-        carry += all;
-    }
+    uint64_t carry[1] = {0};
+    wg_scan_strided(
+        n, carry, [&](uint32_t i, uint64_t (&x)[1]) { x[0] = in[i]; },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            out[i] = ex[0];
+        });
     if (threadIdx.x == 0)
-        out[n] = carry;
+        out[n] = carry[0];
 }
 
 // one chunk at o: header (src/frame.rs:91-93) by thread 0, then the payload

@@ -73,7 +73,8 @@ int slot_reserve(snapmi_ctx *ctx, DevBuf &b, size_t bytes);
 // by k_to_host (16-byte stores over the link) or by hipMemcpyAsync
 int pipe_copy_home(snapmi_ctx *ctx, hipStream_t st, uint8_t *h_dst,
                    const void *d_src, uint64_t n, bool by_kernel);
-// k_scan_u64: out[0..n) = exclusive scan of in[0..n), out[n] = total
+// k_scan_u64 (the strided one-workgroup scan of snapmi_scan.hpp):
+// out[0..n) = exclusive scan of in[0..n), out[n] = total
 int launch_scan_u64(snapmi_ctx *ctx, hipStream_t st, const uint64_t *in,
                     uint64_t *out, uint32_t n);
 // snapmi_frame_decompress_batch of n streams the host has walked: d_first

@@ -90,8 +90,11 @@ struct CompressArgs {
     // 100 MHz clock (each the maximum over the wavefronts), and from
     // kProfTailLanes on the clock at which lane g went out of work
     unsigned long long *prof;
-    // partial sums of the many-workgroup scans (k_plan_compress_*,
-    // k_scan_sizes_*): one per 1024 streams / blocks, + 1
+    // the `part` of the many-workgroup scans (snapmi_scan.hpp: wg_scan_a, _b,
+    // _c in k_plan_compress_*, k_scan_sizes_*): a workgroup's totals, then
+    // its offsets, one per 1024 streams / blocks; scan_part[parts] parks the
+    // carry from the segment in front.  The same memory: the scans of a
+    // batch run one behind the other (k_index_first_* takes it last)
     uint2 *plan_part;
     unsigned long long *scan_part;
     // streams of 1 .. small_limit - 1 bytes get no blocks: k_compress_tiny

@@ -173,21 +173,33 @@ int snapmi_compress_batch_indexed(snapmi_ctx *ctx,
 
 namespace snapmi {
 
+// A scan of n items (snapmi_scan.hpp): one() launches the one-workgroup
+// kernel, three(parts) the (a) (b) (c) kernels over `parts` workgroups of 1024
+// items, for more than kPlanOneWg of them.
+template <class One, class Three>
+static void launch_scan(size_t n, One one, Three three)
+{
+    if (n > kPlanOneWg)
+        three((uint32_t)((n + 1023) / 1024));
+    else
+        one();
+}
+
 // k_scan_sizes over the blocks [a.blk_lo, min(a.blk_hi, host_blocks))
 static void launch_scan_sizes(const CompressArgs &a, hipStream_t s)
 {
     const uint32_t hi = a.blk_hi < a.host_blocks ? a.blk_hi : a.host_blocks;
-    const uint32_t cnt = hi > a.blk_lo ? hi - a.blk_lo : 0;
-    if (cnt > kPlanOneWg) {
-        const uint32_t parts = (cnt + 1023) / 1024;
-        hipLaunchKernelGGL(k_scan_sizes_a, dim3(parts), dim3(1024), 0, s, a,
-                           parts);
-        hipLaunchKernelGGL(k_scan_sizes_b, dim3(1), dim3(1024), 0, s, a,
-                           parts);
-        hipLaunchKernelGGL(k_scan_sizes_c, dim3(parts), dim3(1024), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(1024), 0, s, a);
-    }
+    launch_scan(
+        hi > a.blk_lo ? hi - a.blk_lo : 0,
+        [&] { hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(1024), 0, s, a); },
+        [&](uint32_t parts) {
+            hipLaunchKernelGGL(k_scan_sizes_a, dim3(parts), dim3(1024), 0, s,
+                               a, parts);
+            hipLaunchKernelGGL(k_scan_sizes_b, dim3(1), dim3(1024), 0, s, a,
+                               parts);
+            hipLaunchKernelGGL(k_scan_sizes_c, dim3(parts), dim3(1024), 0, s,
+                               a);
+        });
 }
 
 // match_kernel 2's hint: the latest batch that has finished (a slot reads 0
@@ -449,15 +461,19 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     hipStream_t s = ctx->stream;
     ctx->timing_valid = false;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], s));
-    if (n > kPlanOneWg) {
-        const uint32_t parts = (uint32_t)((n + 1023) / 1024);
-        hipLaunchKernelGGL(k_plan_compress_a, dim3(parts), dim3(1024), 0, s, a);
-        hipLaunchKernelGGL(k_plan_compress_b, dim3(1), dim3(1024), 0, s, a,
-                           parts);
-        hipLaunchKernelGGL(k_plan_compress_c, dim3(parts), dim3(1024), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(k_plan_compress, dim3(1), dim3(1024), 0, s, a);
-    }
+    launch_scan(
+        n,
+        [&] {
+            hipLaunchKernelGGL(k_plan_compress, dim3(1), dim3(1024), 0, s, a);
+        },
+        [&](uint32_t parts) {
+            hipLaunchKernelGGL(k_plan_compress_a, dim3(parts), dim3(1024), 0,
+                               s, a);
+            hipLaunchKernelGGL(k_plan_compress_b, dim3(1), dim3(1024), 0, s, a,
+                               parts);
+            hipLaunchKernelGGL(k_plan_compress_c, dim3(parts), dim3(1024), 0,
+                               s, a);
+        });
     HIP_TRY(ctx, hipEventRecord(ctx->ev[1], s));
     // the lane-per-stream kernels: streams under 256 bytes one per lane,
     // streams under 1 KiB a few per wavefront (a wavefront of streams that
@@ -603,18 +619,21 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     // again: every scan of the batch is done)
     if (d_index_first) {
         uint64_t *part = (uint64_t *)ctx->plan_part.p;
-        if (n > kPlanOneWg) {
-            const uint32_t parts = (uint32_t)((n + 1023) / 1024);
-            hipLaunchKernelGGL(k_index_first_a, dim3(parts), dim3(1024), 0, s,
-                               d_in_lens, (uint32_t)n, d_index_first, part);
-            hipLaunchKernelGGL(k_index_first_b, dim3(1), dim3(1024), 0, s,
-                               (uint32_t)n, d_index_first, part, parts);
-            hipLaunchKernelGGL(k_index_first_c, dim3(parts), dim3(1024), 0, s,
-                               (uint32_t)n, d_index_first, part);
-        } else {
-            hipLaunchKernelGGL(k_index_first, dim3(1), dim3(1024), 0, s,
-                               d_in_lens, (uint32_t)n, d_index_first);
-        }
+        launch_scan(
+            n,
+            [&] {
+                hipLaunchKernelGGL(k_index_first, dim3(1), dim3(1024), 0, s,
+                                   d_in_lens, (uint32_t)n, d_index_first);
+            },
+            [&](uint32_t parts) {
+                hipLaunchKernelGGL(k_index_first_a, dim3(parts), dim3(1024), 0,
+                                   s, d_in_lens, (uint32_t)n, d_index_first,
+                                   part);
+                hipLaunchKernelGGL(k_index_first_b, dim3(1), dim3(1024), 0, s,
+                                   (uint32_t)n, d_index_first, part, parts);
+                hipLaunchKernelGGL(k_index_first_c, dim3(parts), dim3(1024), 0,
+                                   s, (uint32_t)n, d_index_first, part);
+            });
         if (index_entries)
             hipLaunchKernelGGL(k_block_index,
                                dim3((uint32_t)((index_entries + 255) / 256)),

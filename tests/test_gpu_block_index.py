@@ -453,6 +453,54 @@ def test_index_of_more_streams_than_one_workgroup_scans(ctx):
         assert host[o:o + len(d)].tobytes() == d, i
 
 
+@pytest.fixture(scope="module")
+def seam_payloads():
+    """length -> (payload, its index, its compressed stream): the six inputs
+    the oracle sees for the seam batches below."""
+    text = (O.CORPUS / "alice29.txt").read_bytes() * 2
+    out = {}
+    for k, size in enumerate((0, 1, 300, 2100, 65537, 131073)):
+        d = text[1000 * k:1000 * k + size]
+        out[size] = (d, B.expected_index(d), O.compress(d))
+    return out
+
+
+@pytest.mark.parametrize("n", [16384, 16385, 17408, 17409])
+def test_planner_and_index_at_the_workgroup_seams(ctx, seam_payloads, n):
+    """The planner's and the index's scans where one launch becomes three and
+    where the last workgroup ends: 16 384 streams are the most the
+    one-workgroup kernels take (k_plan_compress, k_index_first), one more goes
+    to _a / _b / _c; 17 408 = 17 x 1 024 puts the last stream at the end of
+    the last workgroup, 17 409 alone in an 18th.  Multi-block streams sit at
+    the end of the first workgroup, at the start of the second and last."""
+    from rust_snappy_amd import batch
+    cycle = (0, 1, 300, 2100, 65537)
+    lens = [cycle[i % 5] for i in range(n)]
+    for pos in (1023, 1024, n - 1):
+        lens[pos] = 131073
+    datas = [seam_payloads[size][0] for size in lens]
+    want_first, want = [0], []
+    for size in lens:
+        want_first.append(want_first[-1] + B.entries(size))
+        want += seam_payloads[size][1]
+    src = batch.StreamBatch.from_bytes(datas)
+    enc, first, idx = batch.compress(ctx, src, want_index=True)
+    assert first.cpu().tolist() == want_first
+    assert idx.cpu().tolist() == want
+    assert enc.lens.tolist() == [len(seam_payloads[size][2]) for size in lens]
+    sample = sorted({i for c in (0, 1023, 1024, 2048, 16383, 16384, 17407, n - 1)
+                     for i in range(c - 5, c + 6) if 0 <= i < n})
+    for i in sample:
+        assert enc.stream_bytes(i) == seam_payloads[lens[i]][2], i
+    dec, out_lens, errs = batch.decompress(ctx, enc, caps=lens,
+                                           index=(first, idx))
+    assert out_lens.tolist() == lens and all(e[0] == 0 for e in errs)
+    host = dec.data.cpu().numpy()
+    for i, d in enumerate(datas):
+        o = int(dec.offsets[i])
+        assert host[o:o + len(d)].tobytes() == d, i
+
+
 def test_decode_more_long_streams_than_the_unindexed_path_takes(ctx):
     from rust_snappy_amd import batch
     n, size = 4100, 65537

@@ -871,6 +871,41 @@ def _budget_batch():
     return ins, batch.StreamBatch.from_bytes(ins)
 
 
+def test_block_offsets_carry_into_a_second_large_segment(built):
+    """40 000 one-block streams of 2 100 bytes in launches of 20 000 blocks:
+    each segment has more blocks than one workgroup scans, so
+    k_scan_sizes_a / _b / _c run twice, the second time with blk_lo = 20 000
+    and the carry blk_off[20 000] the first left.  (The route, from
+    snapmi_route.hpp with compress_mode 1, lane_min_blocks 1 and
+    lane_segment_blocks 20 000: every block is at most 8 KiB, so
+    k_match_spans_8k is the match finder, there is no window kernel and the
+    encoder writes directly - route.direct, the scan runs per segment.)  The
+    length of stream 19 999 is blk_off[20 000] - blk_off[19 999]: the word the
+    second segment's scan rewrites."""
+    from rust_snappy_amd import batch
+    blob = b"".join(d for _, d in O.corpus_round())
+    pay = [blob[o:o + 2100] for o in range(0, 8 * 70001, 70001)]
+    want = [O.compress(p) for p in pay]
+    assert len({len(w) for w in want}) > 1
+    n = 40000
+    kind = [(3 * i + i // 1024) % 8 for i in range(n)]
+    src = batch.StreamBatch.from_bytes([pay[k] for k in kind])
+    c = _lane_ctx(lane_segment_blocks=20000)
+    try:
+        dst, lens, errs = batch.compress(c, src)
+    finally:
+        c.close()
+    assert all(e[0] == 0 for e in errs)
+    assert [int(x) for x in lens] == [len(want[k]) for k in kind]
+    sample = sorted({i for s in (0, 1024, 16384, 19999, 20000, 20001, 21024,
+                                 36384, 39999)
+                     for i in range(s - 2, s + 3) if 0 <= i < n}
+                    | set(range(0, n, 997)))
+    assert {19999, 20000, 20001, 39999} <= set(sample)
+    for i in sample:
+        assert dst.stream_bytes(i, lens[i]) == want[kind[i]], i
+
+
 @pytest.mark.parametrize("lib", ["test", "product", "product-plain"])
 @pytest.mark.parametrize("pct", [10, 33])
 def test_lane_table_placement_stays_within_its_budget(built, pct, lib):

@@ -265,6 +265,60 @@ def test_sixty_four_ranges_and_grouping(ctx, case):
     assert grouped == plain
 
 
+def two_thousand(case):
+    """2 051 ranges over streams 1 .. 5 in shuffled order: most of a few
+    hundred bytes inside one block, some across a block boundary, some a whole
+    block; then one of length 0 and, at index 1 024, one that starts behind
+    its stream's end."""
+    rng = random.Random(2051)
+    ranges = []
+    for r in range(2051):
+        if r % 10 == 8:    # across a boundary
+            s = rng.choice([3, 4, 5])
+            d = len(case.whole[s])
+            b = 65536 * rng.randrange(1, (d + 65535) // 65536)
+            off = b - rng.randrange(1, 300)
+            ranges.append((s, off, b - off + rng.randrange(1, min(300, d - b))))
+        elif r % 10 == 9:  # a whole block
+            s = rng.choice([2, 3, 4])
+            k = rng.randrange(len(case.whole[s]) // 65536)
+            ranges.append((s, 65536 * k, 65536))
+        else:
+            s = rng.choice([1, 2, 3, 4, 5])
+            d = len(case.whole[s])
+            k = rng.randrange((d + 65535) // 65536)
+            lo, hi = 65536 * k, min(65536 * (k + 1), d)
+            n = rng.randrange(100, 600)
+            ranges.append((s, rng.randrange(lo, hi - n), n))
+    rng.shuffle(ranges)
+    ranges[77] = (4, 1234, 0)
+    ranges[1024] = (4, 200001, 10)
+    return ranges
+
+
+def test_more_ranges_than_one_workgroup_scans(ctx, case):
+    """2 051 ranges in one group: k_range_scan_a / _c run on three workgroups
+    (the last with three ranges), k_range_scan_b scans three pairs of totals,
+    and the range that fails stands first in the second workgroup.  With the
+    scratch at its floor the same call runs in a thousand groups of one
+    workgroup each and gives the same bytes, lengths and errors."""
+    ranges = two_thousand(case)
+    offs, lens = [r[1] for r in ranges], [r[2] for r in ranges]
+    assert len(R.room_groups(offs, lens, 1 << 30)) == 1
+    assert len(R.room_groups(offs, lens, FLOOR)) > 500
+    _, plain = run(ctx, case, ranges, "2051 ranges")
+    got, errs, _ = plain
+    assert errs[1024] == (101, 200001, 10, 200000) and got[1024] == 0
+    assert (got[77], errs[77]) == (0, OK)
+    assert sum(1 for e in errs if e != OK) == 1
+    ctx.set_option("range_scratch_bytes", FLOOR)
+    try:
+        _, grouped = run(ctx, case, ranges, "2051 ranges, many groups", seed=3)
+    finally:
+        ctx.set_option("range_scratch_bytes", 1 << 30)
+    assert grouped == plain
+
+
 HOSTILE = ["swapped", "mid_element", "beyond", "last_beyond", "count",
            "first_garbage", "zero_index"]
 

@@ -476,6 +476,47 @@ def test_long_stream_strides(ctx):
     assert ctx.info("write_streams_ok") == 1
 
 
+def test_more_touched_streams_than_one_stride_of_the_job_scan(ctx):
+    """1 100 indexed streams of one to three blocks, a small write into each
+    but stream 1 025, the write into stream 1 024 behind its end: 1 099
+    touched streams in one group, so k_write_jobs walks a second stride of its
+    scan, whose first stream (the group's 1 025th) failed and has no jobs."""
+    text = (O.CORPUS / "alice29.txt").read_bytes() * 2
+    pay = [text[:3000], text[500:500 + 70000], text[7:7 + 150000],
+           random.Random(4).randbytes(70000)]
+    comp = [O.compress(d) for d in pay]
+    index = [B.expected_index(d) for d in pay]
+    n = 1100
+
+    class Many:
+        comps = [comp[i % 4] for i in range(n)]
+        flat = [e for i in range(n) for e in index[i % 4]]
+        first = [0]
+    for i in range(n):
+        Many.first.append(Many.first[-1] + len(index[i % 4]))
+    rng = random.Random(1100)
+    writes = []
+    for i in range(n):
+        d = len(pay[i % 4])
+        if i == 1024:
+            writes.append((i, d + 3, b"no"))
+        elif i != 1025:
+            m = rng.randrange(1, 40)
+            writes.append((i, rng.randrange(0, d - m), rng.randbytes(m)))
+    lists = [(s, o, len(b)) for s, o, b in writes]
+    assert W.groups(lists, 1 << 30) == [[i for i in range(n) if i != 1025]]
+    c, (lens, errs, new_index, want) = run(ctx, Many, writes, "1 100 streams")
+    d = len(pay[1024 % 4])
+    assert (lens[1024], errs[1024]) == (0, (101, d + 3, 2, d))
+    assert (lens[1025], errs[1025]) == (0, OK)
+    assert sum(1 for e in errs if e != OK) == 1
+    for i in (0, 1023, 1026, n - 1):
+        new = W.patched(pay[i % 4], [(o, b) for s, o, b in writes if s == i])
+        assert c.out.bytes(i, lens[i]) == O.compress(new), i
+        assert new_index[Many.first[i]:Many.first[i + 1]] == \
+            B.expected_index(new), i
+
+
 def test_groups_at_the_floor(ctx, case):
     """The mixed batch with "write_scratch_bytes" at its floor: one group per
     touched stream (a stream that exceeds the floor alone is a group of its

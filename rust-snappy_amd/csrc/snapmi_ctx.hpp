@@ -280,8 +280,8 @@ struct snapmi_ctx {
     uint32_t stream_seg_log2 = 0;
     uint32_t stream_scan_segs = 0; // test option: 0 = by size
     // frame layer scratch (snapmi_frame.hip)
-    snapmi::DevBuf fr_tables, fr_desc, fr_meta, fr_scan, fr_slots, fr_chunk_off;
-    // snapmi_frame_decompress_batch: per-stream and per-chunk scratch
+    snapmi::DevBuf fr_tables, fr_desc, fr_scan, fr_slots, fr_chunk_off;
+    // frame decode: per-stream and per-chunk scratch
     snapmi::DevBuf fb_streams, fb_chunks;
     bool fr_tables_ready = false;
     // framed streams of at least this many bytes without a side index get

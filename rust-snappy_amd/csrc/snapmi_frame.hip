@@ -7,22 +7,26 @@
 //     type(1) | len24 LE (= 4 + payload) | masked crc32c(uncompressed) LE | payload
 // and every data chunk (<= 64 KiB of input) is an independent raw stream, so
 // the chunk is the parallel unit: the raw codec kernels run unchanged on a
-// batch whose "streams" are the chunks.
+// batch whose "streams" are the chunks.  The chunks of all the streams of a
+// call form one list (stream i owns chunks [first[i], first[i+1])); a call
+// for one stream is a list of one stream.
 //
 // Kernels here:
 //   k_crc32c          masked CRC32C, one wavefront per buffer, 64 interleaved
 //                     partial CRCs advanced 256 bytes per step with 4 LDS
 //                     table lookups, combined by GF(2) multiplication
-//   k_frame_chunks    compress side: chunk descriptors for the raw compressor
-//   k_frame_sizes     compressed-vs-stored decision (src/frame.rs:85) + sizes
 //   k_scan_u64        exclusive scan (one workgroup; snapmi_scan.hpp)
-//   k_frame_emit      headers + payloads into the framed stream
-//   k_frame_walk      decode side: sequential walk over the chunk headers
-//                     (the format has no index) with the reference's checks
-//   k_frame_index     decode side with a side index: one thread per chunk
-//   k_frame_lens      decompressed length of every data chunk
-//   k_frame_desc      descriptors for the raw decompressor
-//   k_frame_verify    CRC comparison, first error in stream order
+//   k_fb_chunks       compress side: chunk descriptors for the raw compressor
+//   k_fb_sizes        compressed-vs-stored decision (src/frame.rs:85) + sizes
+//   k_fb_emit         headers + payloads into the framed streams
+//   k_frame_walk      decode side, one stream: sequential walk over the chunk
+//                     headers (the format has no index) with the reference's
+//                     checks; k_fw_* find the headers of a long stream in
+//                     parallel, k_frame_index checks a side index
+//   k_fbd_walk_*      decode side, many streams: one thread walks a stream
+//   k_fbd_lens        decompressed length of every data chunk
+//   k_fbd_desc        descriptors for the raw decompressor
+//   k_fbd_verify_*    CRC comparison, first error in stream order
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -124,67 +128,6 @@ __global__ __launch_bounds__(64) void k_crc32c(const void *const *ptrs,
     }
 }
 
-// ---------------------------------------------------------------------
-// compress side
-// ---------------------------------------------------------------------
-struct FrameCompressArgs {
-    const uint8_t *in;
-    uint64_t in_len;
-    uint8_t *out;
-    uint64_t out_cap;
-    uint64_t *out_len;       // [1]
-    uint64_t *chunk_offsets; // optional [n+1]
-    uint32_t n;              // chunks of the whole stream
-    // The stream is processed in segments of `cnt` chunks starting at chunk
-    // `lo`, so the per-chunk scratch (one 76 KiB slot each) stays bounded;
-    // the arrays below are per segment, `base` carries the output offset.
-    uint32_t lo, cnt;
-    uint64_t *base; // [1] payload bytes emitted by earlier segments
-    // optional [n+1]: input offset of every chunk (snapmi_frame_compress_chunks:
-    // the caller decides where chunks end); nullptr = 65536-byte multiples
-    const uint64_t *chunk_in_off;
-    uint32_t ident; // 10 when the stream identifier is written, 0 when not
-    // scratch
-    const void **in_ptrs;
-    uint64_t *in_lens;
-    void **slot_ptrs;
-    uint64_t *clens;   // raw-compressed length of every chunk
-    uint32_t *crcs;
-    uint64_t *sizes;   // 8 + payload
-    uint64_t *offs;    // exclusive scan of sizes, [n+1]
-    uint8_t *slots;
-};
-
-__global__ void k_frame_chunks(FrameCompressArgs a)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.cnt)
-        return;
-    uint64_t off, len;
-    if (a.chunk_in_off) {
-        off = a.chunk_in_off[a.lo + i];
-        len = a.chunk_in_off[a.lo + i + 1] - off;
-    } else {
-        off = (uint64_t)(a.lo + i) * kMaxBlock;
-        len = a.in_len - off < kMaxBlock ? a.in_len - off : kMaxBlock;
-    }
-    a.in_ptrs[i] = a.in + off;
-    a.in_lens[i] = len;
-    a.slot_ptrs[i] = a.slots + (uint64_t)i * kFrameSlot;
-}
-
-// reference compress_frame, src/frame.rs:83-89
-__global__ void k_frame_sizes(FrameCompressArgs a)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.cnt)
-        return;
-    const uint64_t len = a.in_lens[i];
-    const uint64_t clen = a.clens[i];
-    const bool stored = clen >= len - len / 8;
-    a.sizes[i] = 8 + (stored ? len : clen);
-}
-
 // exclusive scan of n u64 values, out[n] = total; one workgroup
 __global__ __launch_bounds__(1024) void k_scan_u64(const uint64_t *in,
                                                    uint64_t *out, uint32_t n)
@@ -199,77 +142,18 @@ __global__ __launch_bounds__(1024) void k_scan_u64(const uint64_t *in,
         out[n] = carry[0];
 }
 
-// one chunk at o: header (src/frame.rs:91-93) by thread 0, then the payload
-// from `from` by the whole workgroup
-__device__ inline void frame_put_chunk(gptr o, bool stored, uint64_t payload,
-                                       uint32_t crc, gcptr from)
-{
-    if (threadIdx.x == 0) {
-        const uint32_t cl = 4 + (uint32_t)payload;
-        o[0] = stored ? 0x01 : 0x00;
-        o[1] = (uint8_t)cl;
-        o[2] = (uint8_t)(cl >> 8);
-        o[3] = (uint8_t)(cl >> 16);
-        o[4] = (uint8_t)crc;
-        o[5] = (uint8_t)(crc >> 8);
-        o[6] = (uint8_t)(crc >> 16);
-        o[7] = (uint8_t)(crc >> 24);
-    }
-    gptr to = o + 8;
-    for (uint64_t k = 4 * threadIdx.x; k + 4 <= payload; k += 4 * blockDim.x)
-        st32u(to + k, ld32u(from + k));
-    const uint64_t t = payload & ~3ull;
-    if (threadIdx.x < (payload & 3))
-        to[t + threadIdx.x] = from[t + threadIdx.x];
-}
-
-// one workgroup per chunk: header (src/frame.rs:91-93) + payload
-__global__ __launch_bounds__(256) void k_frame_emit(FrameCompressArgs a)
-{
-    const uint32_t i = blockIdx.x;   // chunk of this segment
-    const uint32_t gi = a.lo + i;    // chunk of the stream
-    const uint64_t len = a.in_lens[i];
-    const uint64_t clen = a.clens[i];
-    const bool stored = clen >= len - len / 8;
-    const uint64_t payload = stored ? len : clen;
-    const uint64_t at = a.ident + a.base[0] + a.offs[i];
-    gptr o = (gptr)a.out + at;
-    if (gi == 0 && a.ident && threadIdx.x < 10) {
-        const uint8_t ident[10] = {0xFF, 0x06, 0x00, 0x00, 's',
-                                   'N',  'a',  'P',  'p',  'Y'};
-        ((gptr)a.out)[threadIdx.x] = ident[threadIdx.x];
-    }
-    frame_put_chunk(o, stored, payload, a.crcs[i],
-                    stored ? (gcptr)a.in_ptrs[i]
-                           : (gcptr)(a.slots + (uint64_t)i * kFrameSlot));
-    if (threadIdx.x == 0) {
-        const uint64_t end = a.ident + a.base[0] + a.offs[a.cnt];
-        if (a.chunk_offsets) {
-            a.chunk_offsets[gi] = at;
-            if (gi + 1 == a.n)
-                a.chunk_offsets[a.n] = end;
-        }
-        if (gi + 1 == a.n)
-            a.out_len[0] = end;
-    }
-}
-
-// after a segment's emit: carry its bytes into the next segment's offsets
-__global__ void k_frame_advance(FrameCompressArgs a)
-{
-    a.base[0] += a.offs[a.cnt];
-}
-
 // ---------------------------------------------------------------------
-// decode side
+// decode side: the fronts of a lone stream
 // ---------------------------------------------------------------------
+// The fronts of a lone stream's decode (snapmi_frame_decompress[_ex]): the
+// side-index check, the parallel header walk and the sequential walk.  Each
+// leaves the stream's chunk table as a batch of one stream, in the layout of
+// FrameBatchDecodeArgs below, for the kernels behind it.
 struct FrameDecodeArgs {
     const uint8_t *in;
     uint64_t in_len;
     uint8_t *out; // may be nullptr (lengths only)
     uint64_t out_cap;
-    uint64_t *out_len; // [1]
-    snapmi_error *err; // [1]
     const uint64_t *index; // optional chunk header offsets
     uint32_t n_index;
     uint32_t cap_chunks; // capacity of chunks[]
@@ -277,23 +161,21 @@ struct FrameDecodeArgs {
     // first 10 bytes of the reference decoder's `src` scratch buffer when
     // this call starts (all zero for a fresh decoder): see frame_short_varint
     uint8_t stale[10];
-    // scratch
+    uint32_t *meta; // for the host: [0] data chunks found, [1] overflow flag,
+                    // [2] 1: the side index met a chunk only a walk can
+                    // judge, 2: so did the parallel walk
+    // the batch of one
     FrameChunk *chunks;
-    uint32_t *meta;      // [0] data chunks found, [1] overflow flag,
-                         // [2] index of the data chunk a structural error
-                         //     precedes (0xFFFFFFFF = none), [3] the side
-                         //     index met a chunk only the walk can judge
-    snapmi_error *serr;  // [1] structural error of the walk
-    uint64_t *dlens;     // [n] decompressed length per data chunk
-    uint64_t *offs;      // [n+1]
-    snapmi_error *cerrs; // [n] per-chunk errors (length stage, decode stage)
-    const void **in_ptrs;
+    uint32_t *c_stream; // [cap_chunks], all 0
+    uint64_t *counts;   // [1] data chunks
+    uint64_t *first;    // {0, data chunks}
+    snapmi_error *serr; // [1] structural error of the walk
+    uint32_t *sidx;     // [1] the data chunk it precedes (0xFFFFFFFF = none)
+    uint32_t *first_bad; // [1] 0xFFFFFFFF: no chunk has failed yet
+    const void **in_ptrs; // [1] each: the call's scalars
     uint64_t *in_lens;
     void **out_ptrs;
     uint64_t *out_caps;
-    uint64_t *out_lens;
-    uint8_t *modes;
-    uint32_t *crcs; // computed
     // parallel header walk (k_fw_*): per 32 MiB segment of the stream, the
     // chains that start at a plausible header inside its first 76 494 bytes
     // and reach the segment's end: {entry, exit, data chunks on the way}
@@ -323,9 +205,28 @@ struct FrameDecodeArgs {
 // Only well-formed stretches are decided here: the first header that the
 // reference's reader would reject (or a chunk the stale-buffer rule applies
 // to) makes the chain "die", the resolve step then finds no continuation and
-// sets meta[3] = 2, and the sequential walk runs and reports the error.
+// sets meta[2] = 2, and the sequential walk runs and reports the error.
 // ---------------------------------------------------------------------
 constexpr uint32_t kFwCands = 32;
+
+// What a front found, by its one deciding thread: nd data chunks, and the
+// structural error e in front of data chunk `sidx` (0xFFFFFFFF = none).
+__device__ inline void frame_front_result(const FrameDecodeArgs &a,
+                                          uint32_t nd, const snapmi_error &e,
+                                          uint32_t sidx)
+{
+    a.meta[0] = nd;
+    a.counts[0] = nd;
+    a.first[0] = 0;
+    a.first[1] = nd;
+    a.serr[0] = e;
+    a.sidx[0] = sidx;
+    a.first_bad[0] = 0xFFFFFFFFu;
+    a.in_ptrs[0] = a.in;
+    a.in_lens[0] = a.in_len;
+    a.out_ptrs[0] = a.out;
+    a.out_caps[0] = a.out_cap;
+}
 constexpr uint32_t kFwScan = 4 + kMaxChunk; // longest chunk, header included
 
 // One hop of a well-formed chain: the chunk at r (header checks of
@@ -393,11 +294,9 @@ __global__ __launch_bounds__(256) void k_fw_candidates(FrameDecodeArgs a)
 __global__ void k_fw_resolve(FrameDecodeArgs a)
 {
     gcptr in = (gcptr)a.in;
-    a.meta[0] = 0;
+    frame_front_result(a, 0, frame_err(SNAPMI_OK, 0, 0), 0xFFFFFFFFu);
     a.meta[1] = 0;
-    a.meta[2] = 0xFFFFFFFFu;
-    a.meta[3] = 2; // until proven well-formed: the sequential walk decides
-    a.serr[0].kind = SNAPMI_OK;
+    a.meta[2] = 2; // until proven well-formed: the sequential walk decides
     // the first chunk must be the stream identifier (src/read.rs:123-128)
     if (!(a.flags & SNAPMI_FRAME_CONTINUATION) &&
         (a.in_len < 4 || in[0] != 0xFF))
@@ -428,15 +327,15 @@ __global__ void k_fw_resolve(FrameDecodeArgs a)
     if (cur != a.in_len)
         return;
     a.fw_base[a.nseg] = total;
-    a.meta[0] = total;
+    frame_front_result(a, total, frame_err(SNAPMI_OK, 0, 0), 0xFFFFFFFFu);
     a.meta[1] = total > a.cap_chunks ? 1 : 0;
-    a.meta[3] = 0;
+    a.meta[2] = 0;
 }
 
 __global__ void k_fw_emit(FrameDecodeArgs a)
 {
     const uint32_t seg = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seg >= a.nseg || a.meta[3] != 0 || a.meta[1] != 0)
+    if (seg >= a.nseg || a.meta[2] != 0 || a.meta[1] != 0)
         return;
     uint64_t r = a.fw_entry[seg];
     if (r == ~0ull)
@@ -457,6 +356,7 @@ __global__ void k_fw_emit(FrameDecodeArgs a)
             c.crc = ld32u(in + r + 4);
             c.type = ty;
             c.pad = 0;
+            a.c_stream[idx] = 0;
             a.chunks[idx++] = c;
         }
         r += 4 + (uint64_t)len;
@@ -469,21 +369,19 @@ __global__ void k_frame_walk(FrameDecodeArgs a)
     if (blockIdx.x || threadIdx.x)
         return;
     a.meta[1] = 0;
-    a.meta[2] = 0xFFFFFFFFu;
-    a.meta[3] = 0;
+    a.meta[2] = 0;
     uint32_t nd;
     const snapmi_error e = frame_walk(
         (gcptr)a.in, a.in_len, a.flags, a.stale, nd,
         [&](uint32_t k, const FrameChunk &c) {
-            if (k < a.cap_chunks)
+            if (k < a.cap_chunks) {
                 a.chunks[k] = c;
-            else
+                a.c_stream[k] = 0;
+            } else {
                 a.meta[1] = 1; // overflow: caller reruns with more room
+            }
         });
-    a.serr[0] = e;
-    a.meta[0] = nd;
-    if (e.kind != SNAPMI_OK)
-        a.meta[2] = nd;
+    frame_front_result(a, nd, e, e.kind != SNAPMI_OK ? nd : 0xFFFFFFFFu);
 }
 
 // With a side index: chunk i's header is at index[i]; all chunks must be
@@ -493,7 +391,7 @@ __global__ void k_frame_index(FrameDecodeArgs a)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     gcptr in = (gcptr)a.in;
-    // (meta[] and serr are cleared by the host before this launch)
+    // (k_frame_meta_init runs before this launch)
     if (i == 0 && !(a.flags & SNAPMI_FRAME_CONTINUATION)) {
         const uint8_t ident[10] = {0xFF, 0x06, 0x00, 0x00, 's',
                                    'N',  'a',  'P',  'p',  'Y'};
@@ -501,13 +399,13 @@ __global__ void k_frame_index(FrameDecodeArgs a)
         for (int k = 0; ok && k < 10; k++)
             ok = in[k] == ident[k];
         if (!ok)
-            a.meta[3] = 1; // the walk reports what is wrong with the start
+            a.meta[2] = 1; // the walk reports what is wrong with the start
     }
     // an index without entries tiles nothing: only a stream that ends right
     // behind its identifier (or an empty continuation) has no chunks
     if (i == 0 && a.n_index == 0 &&
         a.in_len != ((a.flags & SNAPMI_FRAME_CONTINUATION) ? 0u : 10u))
-        a.meta[3] = 1;
+        a.meta[2] = 1;
     if (i >= a.n_index)
         return;
     const uint64_t r = a.index[i];
@@ -542,40 +440,9 @@ __global__ void k_frame_index(FrameDecodeArgs a)
         }
     }
     if (!good)
-        a.meta[3] = 1;
+        a.meta[2] = 1;
     a.chunks[i] = c;
-}
-
-__global__ void k_frame_lens(FrameDecodeArgs a)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = a.meta[0];
-    if (i >= n || i >= a.cap_chunks)
-        return;
-    const FrameChunk c = a.chunks[i];
-    snapmi_error e;
-    a.dlens[i] = frame_chunk_len((gcptr)a.in + c.payload_off, c, e);
-    a.cerrs[i] = e;
-}
-
-// descriptors for the raw decompressor (one "stream" per data chunk)
-__global__ void k_frame_desc(FrameDecodeArgs a)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = a.meta[0];
-    if (i >= n || i >= a.cap_chunks)
-        return;
-    const FrameChunk c = a.chunks[i];
-    const bool bad = a.cerrs[i].kind != SNAPMI_OK;
-    const bool fits = a.offs[n] <= a.out_cap;
-    a.in_ptrs[i] = a.in + c.payload_off;
-    // a chunk that already failed (or an output that does not fit) is
-    // decoded as an empty stored chunk: nothing is written
-    a.in_lens[i] = (bad || !fits) ? 0 : c.payload_len;
-    a.modes[i] = (bad || !fits) ? 1 : (uint8_t)c.type;
-    a.out_ptrs[i] = a.out + a.offs[i];
-    a.out_caps[i] = a.dlens[i];
-    a.out_lens[i] = 0;
+    a.c_stream[i] = 0;
 }
 
 // Final verdict of one framed stream of n data chunks: its first error in
@@ -629,41 +496,12 @@ __device__ inline bool frame_chunk_decode_err(const snapmi_error &derr,
     return false;
 }
 
-__global__ __launch_bounds__(1024) void k_frame_verify(FrameDecodeArgs a,
-                                                       const snapmi_error *derrs)
-{
-    __shared__ uint32_t first_bad;
-    const uint32_t n = a.meta[0] < a.cap_chunks ? a.meta[0] : a.cap_chunks;
-    if (threadIdx.x == 0)
-        first_bad = 0xFFFFFFFFu;
-    __syncthreads();
-    const bool decoded = a.out != nullptr && a.offs[n] <= a.out_cap;
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        bool bad = a.cerrs[i].kind != SNAPMI_OK;
-        if (!bad && decoded)
-            bad = frame_chunk_decode_err(derrs[i], a.chunks[i].crc,
-                                         a.crcs[i], a.cerrs[i]);
-        if (bad)
-            atomicMin(&first_bad, i);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        snapmi_error e;
-        uint64_t len;
-        frame_verdict(first_bad, a.meta[2], n, a.cerrs, a.serr[0],
-                      a.out != nullptr, a.out_cap, a.offs, e, len);
-        a.err[0] = e;
-        a.out_len[0] = len;
-    }
-}
-
 // ---------------------------------------------------------------------
-// Many framed streams per call (snapmi_frame_compress_batch /
-// snapmi_frame_decompress_batch).  The chunks of all streams form one list
-// (stream i owns chunks [first[i], first[i+1])), the codec kernels run over
-// that list as above, and the results map back to each stream: a chunk's
-// output position is its offset in the list's output minus the offset of its
-// stream's first chunk.
+// The chunk list.  The chunks of all streams of a call form one list (stream
+// i owns chunks [first[i], first[i+1])), the codec kernels run over that
+// list, and the results map back to each stream: a chunk's output position
+// is its offset in the list's output minus the offset of its stream's first
+// chunk.
 // ---------------------------------------------------------------------
 struct FrameBatchCompressArgs {
     const void *const *in_ptrs;
@@ -673,6 +511,13 @@ struct FrameBatchCompressArgs {
     uint64_t *out_lens;
     snapmi_error *errs; // nullptr = not reported
     uint32_t n, total, seg; // streams, chunks, chunks per segment
+    // a list of one stream may have these:
+    // [total+1] input offset of every chunk (the caller decides where chunks
+    // end); nullptr = 65536-byte multiples
+    const uint64_t *chunk_in_off;
+    // [total+1] out: where every chunk's header lies, and the frame's length
+    uint64_t *chunk_offsets;
+    uint32_t ident; // 10 when streams begin with the identifier, 0 when not
     uint64_t *counts;       // [n] chunks per stream
     uint64_t *first;        // [n+1] exclusive scan of counts
     uint8_t *refused;       // [n] stream fails the capacity check
@@ -704,6 +549,22 @@ __device__ inline bool fb_refused(const FrameBatchCompressArgs &a, uint32_t i)
     return a.out_caps && len && a.out_caps[i] < frame_max_len_dev(len);
 }
 
+// A lone stream as a list of one stream: the call's scalars in the places of
+// the per-stream arrays (chunks: as the caller cut them, or one per 65536
+// bytes); its first chunk is the list's first.
+__global__ void k_fb_lone(const void **in_ptrs, uint64_t *in_lens,
+                          void **out_ptrs, uint64_t *first, uint64_t *sbase,
+                          const void *in, uint64_t in_len, void *out,
+                          uint64_t chunks)
+{
+    in_ptrs[0] = in;
+    in_lens[0] = in_len;
+    out_ptrs[0] = out;
+    first[0] = 0;
+    first[1] = chunks;
+    sbase[0] = 0;
+}
+
 __global__ void k_fb_counts(FrameBatchCompressArgs a)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -727,10 +588,13 @@ __device__ inline uint32_t fb_stream_of(const uint64_t *first, uint32_t n,
 }
 
 // thread t: stream t's capacity check and result slots, list entry t's
-// chunk descriptor, segment slot t's pointer
+// chunk descriptor, segment slot t's pointer; thread 0 clears the carry (here,
+// not by a memset: a memset a call costs a one-stream call 4 us)
 __global__ void k_fb_chunks(FrameBatchCompressArgs a)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0)
+        a.carry[0] = 0;
     if (t < a.n) {
         const bool r = fb_refused(a, t);
         a.refused[t] = r;
@@ -742,10 +606,17 @@ __global__ void k_fb_chunks(FrameBatchCompressArgs a)
     }
     if (t < a.total) {
         const uint32_t i = fb_stream_of(a.first, a.n, t);
-        const uint64_t off = (t - a.first[i]) * (uint64_t)kMaxBlock;
-        const uint64_t len = a.in_lens[i] - off;
+        uint64_t off, len;
+        if (a.chunk_in_off) {
+            off = a.chunk_in_off[t];
+            len = a.chunk_in_off[t + 1] - off;
+        } else {
+            off = (t - a.first[i]) * (uint64_t)kMaxBlock;
+            len = a.in_lens[i] - off < kMaxBlock ? a.in_lens[i] - off
+                                                 : kMaxBlock;
+        }
         a.c_in[t] = (const uint8_t *)a.in_ptrs[i] + off;
-        a.c_len[t] = len < kMaxBlock ? len : kMaxBlock;
+        a.c_len[t] = len;
         a.c_stream[t] = i;
     }
     if (t < a.seg)
@@ -779,6 +650,30 @@ __global__ void k_fb_base(FrameBatchCompressArgs a)
         a.sbase[s] = a.carry[0] + a.offs[i];
 }
 
+// one chunk at o: header (src/frame.rs:91-93) by thread 0, then the payload
+// from `from` by the whole workgroup
+__device__ inline void frame_put_chunk(gptr o, bool stored, uint64_t payload,
+                                       uint32_t crc, gcptr from)
+{
+    if (threadIdx.x == 0) {
+        const uint32_t cl = 4 + (uint32_t)payload;
+        o[0] = stored ? 0x01 : 0x00;
+        o[1] = (uint8_t)cl;
+        o[2] = (uint8_t)(cl >> 8);
+        o[3] = (uint8_t)(cl >> 16);
+        o[4] = (uint8_t)crc;
+        o[5] = (uint8_t)(crc >> 8);
+        o[6] = (uint8_t)(crc >> 16);
+        o[7] = (uint8_t)(crc >> 24);
+    }
+    gptr to = o + 8;
+    for (uint64_t k = 4 * threadIdx.x; k + 4 <= payload; k += 4 * blockDim.x)
+        st32u(to + k, ld32u(from + k));
+    const uint64_t t = payload & ~3ull;
+    if (threadIdx.x < (payload & 3))
+        to[t + threadIdx.x] = from[t + threadIdx.x];
+}
+
 // one workgroup per chunk of the segment: the stream identifier (first
 // chunk), header (src/frame.rs:91-93) and payload at the chunk's offset in
 // its stream; the stream's last chunk writes its length
@@ -793,10 +688,10 @@ __global__ __launch_bounds__(256) void k_fb_emit(FrameBatchCompressArgs a)
     const uint64_t clen = a.clens[i];
     const bool stored = clen >= len - len / 8;
     const uint64_t payload = stored ? len : clen;
-    const uint64_t at = 10 + a.carry[0] + a.offs[i] - a.sbase[s];
+    const uint64_t at = a.ident + a.carry[0] + a.offs[i] - a.sbase[s];
     gptr base = (gptr)a.out_ptrs[s];
     gptr o = base + at;
-    if (gi == a.first[s] && threadIdx.x < 10) {
+    if (gi == a.first[s] && threadIdx.x < a.ident) {
         const uint8_t ident[10] = {0xFF, 0x06, 0x00, 0x00, 's',
                                    'N',  'a',  'P',  'p',  'Y'};
         base[threadIdx.x] = ident[threadIdx.x];
@@ -804,8 +699,15 @@ __global__ __launch_bounds__(256) void k_fb_emit(FrameBatchCompressArgs a)
     frame_put_chunk(o, stored, payload, a.crcs[i],
                     stored ? (gcptr)a.c_in[gi]
                            : (gcptr)(a.slots + (uint64_t)i * kFrameSlot));
-    if (threadIdx.x == 0 && gi + 1 == a.first[s + 1])
-        a.out_lens[s] = at + 8 + payload;
+    if (threadIdx.x == 0) {
+        if (a.chunk_offsets) {
+            a.chunk_offsets[gi] = at;
+            if (gi + 1 == a.total)
+                a.chunk_offsets[a.total] = at + 8 + payload;
+        }
+        if (gi + 1 == a.first[s + 1])
+            a.out_lens[s] = at + 8 + payload;
+    }
 }
 
 __global__ void k_fb_advance(FrameBatchCompressArgs a)
@@ -826,7 +728,8 @@ struct FrameBatchDecodeArgs {
     uint64_t *first;      // [n+1] exclusive scan of counts
     snapmi_error *serr;   // [n] the walk's structural error
     uint32_t *sidx;       // [n] data chunk it precedes (0xFFFFFFFF = none)
-    uint32_t *first_bad;  // [n] first chunk with an error
+    uint32_t *first_bad;  // [n] first chunk with an error (0xFFFFFFFF = none,
+                          // set with serr and sidx, not by a memset a call)
     // per data chunk of the list
     FrameChunk *chunks;
     uint32_t *c_stream;
@@ -858,6 +761,7 @@ __global__ __launch_bounds__(64) void k_fbd_walk_count(FrameBatchDecodeArgs a)
     a.counts[i] = nd;
     a.serr[i] = e;
     a.sidx[i] = e.kind != SNAPMI_OK ? nd : 0xFFFFFFFFu;
+    a.first_bad[i] = 0xFFFFFFFFu;
 }
 
 // pass 2: the same walk writes the chunk records at the stream's place
@@ -952,17 +856,20 @@ __global__ __launch_bounds__(256) void k_fbd_from_list(FrameBatchDecodeArgs a,
     } else if (t - a.total < a.n) {
         const uint32_t i = t - a.total;
         const uint64_t b = l_first[i], e = l_first[i + 1];
-        uint64_t r = 0;
-        if (e > b)
-            r = list[e - 1].off + 4 + (list[e - 1].hd >> 8);
-        good = fbd_gap((gcptr)a.in_ptrs[i], a.in_lens[i], r, e > b,
-                       a.in_lens[i]);
+        // (stored in front of the walk below: behind it the six pointers
+        // stay live across it and the kernel spills SGPRs)
         a.counts[i] = e - b;
         a.first[i] = b;
         if (i + 1 == a.n)
             a.first[a.n] = e;
         a.serr[i] = frame_err(SNAPMI_OK, 0, 0);
         a.sidx[i] = 0xFFFFFFFFu;
+        a.first_bad[i] = 0xFFFFFFFFu;
+        uint64_t r = 0;
+        if (e > b)
+            r = list[e - 1].off + 4 + (list[e - 1].hd >> 8);
+        good = fbd_gap((gcptr)a.in_ptrs[i], a.in_lens[i], r, e > b,
+                       a.in_lens[i]);
     }
     if (!good)
         *bad = 1;
@@ -987,7 +894,7 @@ __device__ inline bool fbd_fits(const FrameBatchDecodeArgs &a, uint32_t s)
     return a.offs[e] - a.offs[b] <= a.out_caps[s];
 }
 
-// descriptors for the raw decompressor, as k_frame_desc per stream
+// descriptors for the raw decompressor (one "stream" per data chunk)
 __global__ void k_fbd_desc(FrameBatchDecodeArgs a)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -995,6 +902,8 @@ __global__ void k_fbd_desc(FrameBatchDecodeArgs a)
         return;
     const uint32_t s = a.c_stream[c];
     const FrameChunk ch = a.chunks[c];
+    // a chunk that already failed (or an output that does not fit) is
+    // decoded as an empty stored chunk: nothing is written
     const bool skip = a.cerrs[c].kind != SNAPMI_OK || !fbd_fits(a, s);
     a.c_in[c] = (const uint8_t *)a.in_ptrs[s] + ch.payload_off;
     a.c_in_len[c] = skip ? 0 : ch.payload_len;
@@ -1122,57 +1031,125 @@ int snapmi_crc32c_masked_batch(snapmi_ctx *ctx, const void *const *d_ptrs,
 } // extern "C"
 
 namespace snapmi {
-// n chunks of d_in: at 65536-byte multiples (d_chunk_in_off == nullptr) or at
-// the given input offsets ([n+1], device); shared by the two entry points
-static int frame_compress_impl(snapmi_ctx *ctx, const void *d_in,
-                               uint64_t in_len, uint32_t n,
-                               const uint64_t *d_chunk_in_off, bool ident,
-                               void *d_out, uint64_t *d_out_len,
-                               uint64_t *d_chunk_offsets,
-                               const uint32_t *h_chunk_lens = nullptr)
+// What frame_compress_list frames: n streams by arrays in device memory, or
+// (lone) the one stream [in, in + in_len) -> out.
+struct FrameList {
+    bool lone = false;
+    size_t n = 1;
+    uint64_t total = 0;                  // chunks of all streams
+    const uint64_t *h_in_lens = nullptr; // [n] the streams' lengths, host
+    uint64_t *out_lens = nullptr;        // device, [n]
+    // n streams
+    const void *const *in_ptrs = nullptr;
+    const uint64_t *in_lens = nullptr;
+    void *const *out_ptrs = nullptr;
+    const uint64_t *out_caps = nullptr; // nullptr = not checked
+    snapmi_error *errs = nullptr;       // nullptr = not reported
+    // the lone stream
+    const void *in = nullptr;
+    uint64_t in_len = 0;
+    void *out = nullptr;
+    // and what only a lone stream may have:
+    // [total+1] where the caller cut the chunks, device-readable (device or
+    // pinned host memory), and [total] their lengths on the host;
+    // nullptr = 65536-byte multiples
+    const uint64_t *chunk_in_off = nullptr;
+    const uint32_t *h_chunk_lens = nullptr;
+    bool ident = true; // streams begin with the stream identifier
+    uint64_t *chunk_offsets = nullptr; // device, [total+1] out (k_fb_emit)
+};
+
+// The one place that frames chunks: descriptors of the list, then per segment
+// the checksums, the raw compressor, sizes, their scan and the emit.
+static int frame_compress_list(snapmi_ctx *ctx, const FrameList &l)
 {
     hipStream_t s = ctx->stream;
+    const size_t n = l.n;
+    const uint64_t total = l.total;
+    const bool lone = l.lone;
+    // segments of at most lane_segment_blocks chunks (16 GiB of input by
+    // default): 76 KiB of slot + 72 KiB of tokens per chunk of a segment;
+    // per segment the chunks of at most 8 KiB for the compressor's routing
+    // (chunks cut short by the caller - flushes, short reads -, else only a
+    // stream's last chunk can be one)
+    const uint32_t seg = total < ctx->lane_segment_blocks
+                             ? (uint32_t)total
+                             : ctx->lane_segment_blocks;
+    std::vector<uint64_t> c8(seg ? (total + seg - 1) / seg : 0, 0);
+    if (l.h_chunk_lens) {
+        for (uint64_t t = 0; t < total; t++)
+            c8[t / seg] += l.h_chunk_lens[t] <= 8192;
+    } else {
+        for (uint64_t i = 0, at = 0; i < n; i++) {
+            const uint64_t len = l.h_in_lens[i];
+            const uint64_t k = (len + kMaxBlock - 1) / kMaxBlock;
+            if (k && len - (k - 1) * kMaxBlock <= 8192)
+                c8[(at + k - 1) / seg]++;
+            at += k;
+        }
+    }
     int rc = ensure_tables(ctx);
     if (rc)
         return rc;
-    // segments of at most lane_segment_blocks chunks (16 GiB of input by
-    // default): 76 KiB of slot + 72 KiB of tokens per chunk of a segment
-    const uint32_t seg = n < ctx->lane_segment_blocks
-                             ? n
-                             : ctx->lane_segment_blocks;
-    const size_t desc_bytes =
-        (size_t)seg * (8 + 8 + 8 + 8 + 4 + 8 + 8) + 8 + 16 * 8;
-    if ((rc = reserve(ctx, ctx->fr_desc, desc_bytes)) ||
-        (rc = reserve(ctx, ctx->fr_slots, (size_t)seg * kFrameSlot)))
+    const size_t bytes = n * (8 + 8 + 1 + 8) + 8 + 3 * 8 +
+                         total * (8 + 8 + 4) +
+                         (size_t)seg * (8 + 8 + 4 + 8 + 8) + 8 + 8 + 16 * 16;
+    if ((rc = reserve(ctx, ctx->fr_desc, bytes)) ||
+        (seg && (rc = reserve(ctx, ctx->fr_slots, (size_t)seg * kFrameSlot))))
         return rc;
-    FrameCompressArgs a;
+    FrameBatchCompressArgs a;
     uint8_t *p = (uint8_t *)ctx->fr_desc.p;
-    a.in = (const uint8_t *)d_in;
-    a.in_len = in_len;
-    a.out = (uint8_t *)d_out;
-    a.out_cap = 0;
-    a.out_len = d_out_len;
-    a.chunk_offsets = d_chunk_offsets;
-    a.n = n;
-    a.chunk_in_off = d_chunk_in_off;
-    a.ident = ident ? 10 : 0;
-    a.base = carve<uint64_t>(p, 1);
-    a.in_ptrs = carve<const void *>(p, seg);
-    a.in_lens = carve<uint64_t>(p, seg);
+    // (a lone stream's scalars take the places of the arrays: k_fb_lone)
+    const void **lone_in = carve<const void *>(p, lone ? 1 : 0);
+    uint64_t *lone_len = carve<uint64_t>(p, lone ? 1 : 0);
+    void **lone_out = carve<void *>(p, lone ? 1 : 0);
+    a.in_ptrs = lone ? lone_in : l.in_ptrs;
+    a.in_lens = lone ? lone_len : l.in_lens;
+    a.out_ptrs = lone ? lone_out : l.out_ptrs;
+    a.out_caps = l.out_caps;
+    a.out_lens = l.out_lens;
+    a.errs = l.errs;
+    a.n = (uint32_t)n;
+    a.total = (uint32_t)total;
+    a.seg = seg;
+    a.chunk_in_off = l.chunk_in_off;
+    a.chunk_offsets = l.chunk_offsets;
+    a.ident = l.ident ? 10 : 0;
+    a.counts = carve<uint64_t>(p, n);
+    a.first = carve<uint64_t>(p, n + 1);
+    a.refused = carve<uint8_t>(p, n);
+    a.sbase = carve<uint64_t>(p, n);
+    a.c_in = carve<const void *>(p, total);
+    a.c_len = carve<uint64_t>(p, total);
+    a.c_stream = carve<uint32_t>(p, total);
+    a.carry = carve<uint64_t>(p, 1);
     a.slot_ptrs = carve<void *>(p, seg);
     a.clens = carve<uint64_t>(p, seg);
-    a.sizes = carve<uint64_t>(p, seg);
-    a.offs = carve<uint64_t>(p, seg + 1);
     a.crcs = carve<uint32_t>(p, seg);
+    a.sizes = carve<uint64_t>(p, seg);
+    a.offs = carve<uint64_t>(p, (size_t)seg + 1);
     a.slots = (uint8_t *)ctx->fr_slots.p;
+    a.lo = a.cnt = 0;
 
-    HIP_TRY(ctx, hipMemsetAsync(a.base, 0, sizeof(uint64_t), s));
-    for (uint32_t lo = 0; lo < n; lo += seg) {
-        const uint32_t cnt = n - lo < seg ? n - lo : seg;
+    const uint32_t tb = 256;
+    uint64_t most = total > n ? total : n;
+    if (lone) {
+        hipLaunchKernelGGL(k_fb_lone, dim3(1), dim3(1), 0, s, lone_in,
+                           lone_len, lone_out, a.first, a.sbase, l.in,
+                           l.in_len, l.out, total);
+    } else {
+        hipLaunchKernelGGL(k_fb_counts, dim3((uint32_t)((n + tb - 1) / tb)),
+                           dim3(tb), 0, s, a);
+        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.counts,
+                           a.first, (uint32_t)n);
+    }
+    hipLaunchKernelGGL(k_fb_chunks, dim3((uint32_t)((most + tb - 1) / tb)),
+                       dim3(tb), 0, s, a);
+    for (uint32_t lo = 0; lo < total; lo += seg) {
+        const uint32_t cnt = total - lo < seg ? (uint32_t)total - lo : seg;
         a.lo = lo;
         a.cnt = cnt;
-        const uint32_t tb = 256, gb = (cnt + tb - 1) / tb;
-        hipLaunchKernelGGL(k_frame_chunks, dim3(gb), dim3(tb), 0, s, a);
+        const uint32_t gb = (cnt + tb - 1) / tb;
         // The checksums only need the input: they run on the side stream,
         // under the match finder (which waits on HBM round trips and leaves
         // 16 KiB of LDS per CU free - room for three CRC workgroups).  Fusing
@@ -1185,28 +1162,25 @@ static int frame_compress_impl(snapmi_ctx *ctx, const void *d_in,
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_crc[0], 0));
         }
         hipLaunchKernelGGL(k_crc32c, dim3(cnt), dim3(64), 0,
-                           side ? ctx->stream2 : s, a.in_ptrs, a.in_lens,
+                           side ? ctx->stream2 : s, a.c_in + lo, a.c_len + lo,
                            a.crcs, cnt, (const CrcTables *)ctx->fr_tables.p);
         if (side)
             HIP_TRY(ctx, hipEventRecord(ctx->ev_crc[1], ctx->stream2));
         // every chunk is a one-block raw stream: cnt blocks, no scratch slots
-        // (chunks cut short by the caller - flushes, short reads - are
-        // counted for the small-block kernels)
-        uint64_t c8 = 0;
-        if (h_chunk_lens)
-            for (uint32_t i = lo; i < lo + cnt; i++)
-                c8 += h_chunk_lens[i] <= 8192;
-        rc = launch_compress(ctx, a.in_ptrs, a.in_lens, a.slot_ptrs, nullptr,
-                             a.clens, nullptr, cnt, cnt, 0, 0xF, c8);
+        rc = launch_compress(ctx, a.c_in + lo, a.c_len + lo, a.slot_ptrs,
+                             nullptr, a.clens, nullptr, cnt, cnt, 0, 0xF,
+                             c8[lo / seg]);
         if (rc)
             return rc;
         if (side)
             HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_crc[1], 0));
-        hipLaunchKernelGGL(k_frame_sizes, dim3(gb), dim3(tb), 0, s, a);
+        hipLaunchKernelGGL(k_fb_sizes, dim3(gb), dim3(tb), 0, s, a);
         hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.sizes,
                            a.offs, cnt);
-        hipLaunchKernelGGL(k_frame_emit, dim3(cnt), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_frame_advance, dim3(1), dim3(1), 0, s, a);
+        if (!lone) // (a lone stream's first chunk is the list's: k_fb_lone)
+            hipLaunchKernelGGL(k_fb_base, dim3(gb), dim3(tb), 0, s, a);
+        hipLaunchKernelGGL(k_fb_emit, dim3(cnt), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_fb_advance, dim3(1), dim3(1), 0, s, a);
     }
     HIP_TRY(ctx, hipGetLastError());
     return SNAPMI_OK;
@@ -1235,8 +1209,16 @@ int snapmi_frame_compress(snapmi_ctx *ctx, const void *d_in, uint64_t in_len,
     const uint64_t n64 = (in_len + kMaxBlock - 1) / kMaxBlock;
     if (n64 > 0x7FFFFFFFu)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "frame_compress: too long");
-    return frame_compress_impl(ctx, d_in, in_len, (uint32_t)n64, nullptr, true,
-                               d_out, d_out_len, d_chunk_offsets);
+    FrameList l;
+    l.lone = true;
+    l.in = d_in;
+    l.in_len = in_len;
+    l.out = d_out;
+    l.out_lens = d_out_len;
+    l.h_in_lens = &in_len;
+    l.total = n64;
+    l.chunk_offsets = d_chunk_offsets;
+    return frame_compress_list(ctx, l);
 }
 
 int snapmi_frame_compress_chunks(snapmi_ctx *ctx, const void *d_in,
@@ -1277,10 +1259,18 @@ int snapmi_frame_compress_chunks(snapmi_ctx *ctx, const void *d_in,
                                 (n + 1) * sizeof(uint64_t),
                                 hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipStreamSynchronize(s)); // `off` is pageable host memory
-    return frame_compress_impl(ctx, d_in, off[n], (uint32_t)n,
-                               (const uint64_t *)ctx->fr_chunk_off.p, ident,
-                               d_out, d_out_len, d_chunk_offsets,
-                               h_chunk_lens);
+    FrameList l;
+    l.lone = true;
+    l.in = d_in;
+    l.in_len = off[n];
+    l.out = d_out;
+    l.out_lens = d_out_len;
+    l.total = n;
+    l.chunk_in_off = (const uint64_t *)ctx->fr_chunk_off.p;
+    l.h_chunk_lens = h_chunk_lens;
+    l.ident = ident;
+    l.chunk_offsets = d_chunk_offsets;
+    return frame_compress_list(ctx, l);
 }
 
 int snapmi_frame_index_host(const void *h_in, uint64_t in_len,
@@ -1295,15 +1285,13 @@ int snapmi_frame_index_host(const void *h_in, uint64_t in_len,
                             n_chunks);
 }
 
-// meta[] and the structural error slot before the index kernel (whose
-// threads only ever raise meta[3])
+// the index kernel's result if its threads find nothing wrong (they only
+// ever raise meta[2])
 __global__ void k_frame_meta_init(FrameDecodeArgs a)
 {
-    a.meta[0] = a.n_index;
+    frame_front_result(a, a.n_index, frame_err(SNAPMI_OK, 0, 0), 0xFFFFFFFFu);
     a.meta[1] = 0;
-    a.meta[2] = 0xFFFFFFFFu;
-    a.meta[3] = 0;
-    a.serr[0].kind = SNAPMI_OK;
+    a.meta[2] = 0;
 }
 
 // Device memory -> pinned (device-mapped) host memory by a kernel: 16-byte
@@ -1469,6 +1457,121 @@ int snapmi_frame_scan_host(const void *h_in, uint64_t in_len, uint32_t flags,
                       ~0ull, n_chunks, consumed);
 }
 
+// The per-stream scratch of a decode of n streams, and `extra` bytes behind
+// it that are the caller's (*rest).
+static int fbd_streams(snapmi_ctx *ctx, FrameBatchDecodeArgs &a, size_t n,
+                       size_t extra, uint8_t **rest)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_tables(ctx);
+    if (rc)
+        return rc;
+    // per-stream scratch and per-chunk scratch in two buffers: the second is
+    // sized after the walk, and growing it must not drop the first
+    if ((rc = reserve(ctx, ctx->fb_streams,
+                      n * (8 + 8 + sizeof(snapmi_error) + 4 + 4) + 8 +
+                          16 * 8 + extra)))
+        return rc;
+    uint8_t *p = (uint8_t *)ctx->fb_streams.p;
+    a.n = (uint32_t)n;
+    a.total = 0;
+    a.counts = carve<uint64_t>(p, n);
+    a.first = carve<uint64_t>(p, n + 1);
+    a.serr = carve<snapmi_error>(p, n);
+    a.sidx = carve<uint32_t>(p, n);
+    a.first_bad = carve<uint32_t>(p, n);
+    if (rest)
+        *rest = p;
+    return SNAPMI_OK;
+}
+
+// A batch call's arguments (false ones are reported) and per-stream scratch.
+static int fbd_begin(snapmi_ctx *ctx, const char *what,
+                     const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+                     void *const *d_out_ptrs, const uint64_t *d_out_caps,
+                     uint64_t *d_out_lens, snapmi_error *d_errs, size_t n,
+                     FrameBatchDecodeArgs &a)
+{
+    if (!d_in_ptrs || !d_in_lens || !d_out_lens || (d_out_ptrs && !d_out_caps))
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "%s: bad args", what);
+    if (n > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "%s: %zu streams (at most 2^31 - 1)", what, n);
+    a.in_ptrs = d_in_ptrs;
+    a.in_lens = d_in_lens;
+    a.out_ptrs = d_out_ptrs;
+    a.out_caps = d_out_caps;
+    a.out_lens = d_out_lens;
+    a.errs = d_errs;
+    return fbd_streams(ctx, a, n, 0, nullptr);
+}
+
+// The per-chunk scratch of a decode, for a list of `total` data chunks.
+static int fbd_table(snapmi_ctx *ctx, const char *what,
+                     FrameBatchDecodeArgs &a, uint64_t total)
+{
+    if (total > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "%s: %llu chunks (at most 2^31 - 1)", what,
+                        (unsigned long long)total);
+    const size_t t = (size_t)total;
+    int rc;
+    if ((rc = reserve(ctx, ctx->fb_chunks,
+                      t * (sizeof(FrameChunk) + 4 + 8 + 8 +
+                           2 * sizeof(snapmi_error) + 8 + 8 + 8 + 8 + 8 + 1 +
+                           4) + 8 + 16 * 16)))
+        return rc;
+    uint8_t *p = (uint8_t *)ctx->fb_chunks.p;
+    a.total = (uint32_t)total;
+    a.chunks = carve<FrameChunk>(p, t);
+    a.c_stream = carve<uint32_t>(p, t);
+    a.dlens = carve<uint64_t>(p, t);
+    a.offs = carve<uint64_t>(p, t + 1);
+    a.cerrs = carve<snapmi_error>(p, t);
+    a.derrs = carve<snapmi_error>(p, t);
+    a.c_in = carve<const void *>(p, t);
+    a.c_in_len = carve<uint64_t>(p, t);
+    a.c_out = carve<void *>(p, t);
+    a.c_caps = carve<uint64_t>(p, t);
+    a.c_out_lens = carve<uint64_t>(p, t);
+    a.modes = carve<uint8_t>(p, t);
+    a.crcs = carve<uint32_t>(p, t);
+    return SNAPMI_OK;
+}
+
+// Everything behind the chunk table (chunks[], c_stream[] of a.total data
+// chunks; first[], serr[], sidx[], first_bad[] per stream): lengths,
+// descriptors, the codec, the checksums and the verdicts.
+static int fbd_finish(snapmi_ctx *ctx, FrameBatchDecodeArgs &a)
+{
+    hipStream_t s = ctx->stream;
+    const size_t n = a.n;
+    const uint32_t tb = 256;
+    const uint32_t gc = a.total ? (a.total + tb - 1) / tb : 1;
+    if (a.total)
+        hipLaunchKernelGGL(k_fbd_lens, dim3(gc), dim3(tb), 0, s, a);
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.dlens, a.offs,
+                       a.total);
+    if (a.out_ptrs && a.total) {
+        hipLaunchKernelGGL(k_fbd_desc, dim3(gc), dim3(tb), 0, s, a);
+        int rc = launch_decompress(ctx, a.c_in, a.c_in_len, a.c_out, a.c_caps,
+                                   a.c_out_lens, a.derrs, a.modes, a.total);
+        if (rc)
+            return rc;
+        // CRC of what was produced (chunks that were skipped have c_out_lens
+        // 0: their CRC is never compared)
+        hipLaunchKernelGGL(k_crc32c, dim3(a.total), dim3(64), 0, s,
+                           (const void *const *)a.c_out, a.c_out_lens, a.crcs,
+                           a.total, (const CrcTables *)ctx->fr_tables.p);
+    }
+    if (a.total)
+        hipLaunchKernelGGL(k_fbd_verify_chunks, dim3(gc), dim3(tb), 0, s, a);
+    hipLaunchKernelGGL(k_fbd_verify_streams,
+                       dim3((uint32_t)((n + tb - 1) / tb)), dim3(tb), 0, s, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SNAPMI_OK;
+}
+
 int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
                                uint64_t in_len, void *d_out, uint64_t out_cap,
                                uint64_t *d_out_len, snapmi_error *d_err,
@@ -1476,14 +1579,10 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
                                uint64_t n_chunks, uint32_t flags,
                                const uint8_t *stale10)
 {
+    const char *what = "frame";
     if (!ctx || !d_out_len || !d_err || (in_len && !d_in) ||
         (flags & ~(uint32_t)SNAPMI_FRAME_CONTINUATION))
         return SNAPMI_E_ARGUMENT;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    int rc = ensure_tables(ctx);
-    if (rc)
-        return rc;
     // capacity for the chunk table: exact with an index, else an estimate
     // that is retried once with the exact count
     bool use_index = d_chunk_offsets != nullptr;
@@ -1495,52 +1594,58 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
     if (nseg64 == 0 || nseg64 > 65535)
         parallel_walk = false; // (empty; grid limit: 2 TiB at the default)
     const uint32_t nseg = parallel_walk ? (uint32_t)nseg64 : 0;
+    // The stream is a batch of one: the call's scalars go where the batch's
+    // arrays lie (frame_front_result), beside the fronts' own state.  All of
+    // it is sized here, once: a retry below grows the chunk table only.
+    FrameDecodeArgs a;
+    FrameBatchDecodeArgs b;
+    uint8_t *p;
+    const size_t front_bytes = 4 * 8 + 16 + 16 * 16 +
+                               (size_t)(nseg + 2) * (kFwCands * 24 + 4 + 8 + 4);
+    a.in = (const uint8_t *)d_in;
+    a.in_len = in_len;
+    a.out = (uint8_t *)d_out;
+    a.out_cap = out_cap;
+    a.flags = flags;
+    for (int k = 0; k < 10; k++)
+        a.stale[k] = stale10 ? stale10[k] : 0;
+    int rc = fbd_streams(ctx, b, 1, front_bytes, &p);
+    if (rc || (rc = mailbox(ctx)))
+        return rc;
+    hipStream_t s = ctx->stream;
+    a.in_ptrs = carve<const void *>(p, 1);
+    a.in_lens = carve<uint64_t>(p, 1);
+    a.out_ptrs = carve<void *>(p, 1);
+    a.out_caps = carve<uint64_t>(p, 1);
+    a.meta = carve<uint32_t>(p, 4);
+    a.nseg = nseg;
+    a.fw_seg = fw_seg;
+    a.fw_cand = carve<unsigned long long>(p, (size_t)nseg * kFwCands * 3);
+    a.fw_entry = carve<unsigned long long>(p, (size_t)nseg + 1);
+    a.fw_ncand = carve<uint32_t>(p, nseg);
+    a.fw_base = carve<uint32_t>(p, (size_t)nseg + 1);
+    a.counts = b.counts;
+    a.first = b.first;
+    a.serr = b.serr;
+    a.sidx = b.sidx;
+    a.first_bad = b.first_bad;
+    b.in_ptrs = a.in_ptrs;
+    b.in_lens = a.in_lens;
+    b.out_ptrs = d_out ? a.out_ptrs : nullptr; // nullptr = lengths only
+    b.out_caps = a.out_caps;
+    b.out_lens = d_out_len;
+    b.errs = d_err;
     for (int attempt = 0; attempt < 4; attempt++) {
         if (cap > 0x7FFFFFFFu)
             return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "frame: too many chunks");
         const size_t n = (size_t)cap;
-        const size_t meta_bytes = 64 + sizeof(snapmi_error) +
-                                  n * (sizeof(FrameChunk) + 8 + 8 +
-                                       sizeof(snapmi_error) * 2 + 8 * 5 + 1 +
-                                       4) + 32 * 16 +
-                                  (size_t)(nseg + 2) *
-                                      (kFwCands * 24 + 4 + 8 + 4);
-        if ((rc = reserve(ctx, ctx->fr_meta, meta_bytes)))
+        if ((rc = fbd_table(ctx, what, b, cap)))
             return rc;
-        FrameDecodeArgs a;
-        uint8_t *p = (uint8_t *)ctx->fr_meta.p;
-        a.in = (const uint8_t *)d_in;
-        a.in_len = in_len;
-        a.out = (uint8_t *)d_out;
-        a.out_cap = out_cap;
-        a.out_len = d_out_len;
-        a.err = d_err;
+        a.chunks = b.chunks;
+        a.c_stream = b.c_stream;
         a.index = use_index ? d_chunk_offsets : nullptr;
         a.n_index = use_index ? (uint32_t)n_chunks : 0;
         a.cap_chunks = (uint32_t)n;
-        a.flags = flags;
-        for (int k = 0; k < 10; k++)
-            a.stale[k] = stale10 ? stale10[k] : 0;
-        a.meta = carve<uint32_t>(p, 4);
-        a.serr = carve<snapmi_error>(p, 1);
-        a.chunks = carve<FrameChunk>(p, n);
-        a.dlens = carve<uint64_t>(p, n);
-        a.offs = carve<uint64_t>(p, n + 1);
-        a.cerrs = carve<snapmi_error>(p, n);
-        snapmi_error *derrs = carve<snapmi_error>(p, n);
-        a.in_ptrs = carve<const void *>(p, n);
-        a.in_lens = carve<uint64_t>(p, n);
-        a.out_ptrs = carve<void *>(p, n);
-        a.out_caps = carve<uint64_t>(p, n);
-        a.out_lens = carve<uint64_t>(p, n);
-        a.crcs = carve<uint32_t>(p, n);
-        a.modes = carve<uint8_t>(p, n);
-        a.nseg = nseg;
-        a.fw_seg = fw_seg;
-        a.fw_cand = carve<unsigned long long>(p, (size_t)nseg * kFwCands * 3);
-        a.fw_entry = carve<unsigned long long>(p, (size_t)nseg + 1);
-        a.fw_ncand = carve<uint32_t>(p, nseg);
-        a.fw_base = carve<uint32_t>(p, (size_t)nseg + 1);
 
         const uint32_t tb = 256;
         const uint32_t gb = n ? (uint32_t)((n + tb - 1) / tb) : 1;
@@ -1559,19 +1664,17 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
             hipLaunchKernelGGL(k_frame_walk, dim3(1), dim3(64), 0, s, a);
         }
         // the number of data chunks decides the launch sizes below
-        uint32_t meta[4];
-        if ((rc = mailbox(ctx)))
-            return rc;
+        uint32_t meta[3];
         hipLaunchKernelGGL(k_post_words, dim3(1), dim3(64), 0, s,
-                           (uint32_t *)ctx->h_mail, a.meta, 4u);
+                           (uint32_t *)ctx->h_mail, a.meta, 3u);
         HIP_TRY(ctx, hipStreamSynchronize(s));
         memcpy(meta, (const void *)ctx->h_mail, sizeof meta);
-        if (use_index && meta[3]) { // the index does not tile the stream with
+        if (use_index && meta[2]) { // the index does not tile the stream with
             use_index = false;      // plain data chunks: the walk decides
             cap = n_chunks + in_len / 65536 + 64;
             continue;
         }
-        if (parallel_walk && meta[3] == 2) { // something in the stream that
+        if (parallel_walk && meta[2] == 2) { // something in the stream that
             parallel_walk = false;           // only the sequential walk judges
             continue;
         }
@@ -1579,29 +1682,8 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
             cap = meta[0];
             continue;
         }
-        const uint32_t nd = meta[0] < n ? meta[0] : (uint32_t)n;
-        const uint32_t gd = nd ? (nd + tb - 1) / tb : 1;
-        hipLaunchKernelGGL(k_frame_lens, dim3(gd), dim3(tb), 0, s, a);
-        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.dlens,
-                           a.offs, nd);
-        if (d_out && nd) {
-            hipLaunchKernelGGL(k_frame_desc, dim3(gd), dim3(tb), 0, s, a);
-            rc = launch_decompress(ctx, a.in_ptrs, a.in_lens, a.out_ptrs,
-                                   a.out_caps, a.out_lens, derrs, a.modes,
-                                   nd);
-            if (rc)
-                return rc;
-            // CRC of what was produced (chunks that were skipped have
-            // out_lens 0: their CRC is never compared)
-            hipLaunchKernelGGL(k_crc32c, dim3(nd), dim3(64), 0, s,
-                               (const void *const *)a.out_ptrs, a.out_lens,
-                               a.crcs, nd,
-                               (const CrcTables *)ctx->fr_tables.p);
-        }
-        hipLaunchKernelGGL(k_frame_verify, dim3(1), dim3(1024), 0, s, a,
-                           (const snapmi_error *)derrs);
-        HIP_TRY(ctx, hipGetLastError());
-        return SNAPMI_OK;
+        b.total = meta[0] < n ? meta[0] : (uint32_t)n;
+        return fbd_finish(ctx, b);
     }
     return fail_ctx(ctx, SNAPMI_E_DEVICE, "frame: chunk table retry failed");
 }
@@ -1654,205 +1736,17 @@ int snapmi_frame_compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
                         "frame_compress_batch: %llu chunks (at most 2^31 - 1)",
                         (unsigned long long)total);
-    // segments of the list as in frame_compress_impl; per segment the chunks
-    // of at most 8 KiB for the compressor's routing (only a stream's last
-    // chunk can be one)
-    const uint32_t seg = total < ctx->lane_segment_blocks
-                             ? (uint32_t)total
-                             : ctx->lane_segment_blocks;
-    std::vector<uint64_t> c8(seg ? (total + seg - 1) / seg : 0, 0);
-    for (uint64_t i = 0, at = 0; i < n; i++) {
-        const uint64_t len = h_in_lens[i];
-        const uint64_t k = (len + kMaxBlock - 1) / kMaxBlock;
-        if (k && len - (k - 1) * kMaxBlock <= 8192)
-            c8[(at + k - 1) / seg]++;
-        at += k;
-    }
-    int rc = ensure_tables(ctx);
-    if (rc)
-        return rc;
-    const size_t bytes = n * (8 + 8 + 1 + 8) + 8 + total * (8 + 8 + 4) +
-                         (size_t)seg * (8 + 8 + 4 + 8 + 8) + 8 + 8 + 16 * 16;
-    if ((rc = reserve(ctx, ctx->fr_desc, bytes)) ||
-        (seg && (rc = reserve(ctx, ctx->fr_slots, (size_t)seg * kFrameSlot))))
-        return rc;
-    FrameBatchCompressArgs a;
-    uint8_t *p = (uint8_t *)ctx->fr_desc.p;
-    a.in_ptrs = d_in_ptrs;
-    a.in_lens = d_in_lens;
-    a.out_ptrs = d_out_ptrs;
-    a.out_caps = d_out_caps;
-    a.out_lens = d_out_lens;
-    a.errs = d_errs;
-    a.n = (uint32_t)n;
-    a.total = (uint32_t)total;
-    a.seg = seg;
-    a.counts = carve<uint64_t>(p, n);
-    a.first = carve<uint64_t>(p, n + 1);
-    a.refused = carve<uint8_t>(p, n);
-    a.sbase = carve<uint64_t>(p, n);
-    a.c_in = carve<const void *>(p, total);
-    a.c_len = carve<uint64_t>(p, total);
-    a.c_stream = carve<uint32_t>(p, total);
-    a.carry = carve<uint64_t>(p, 1);
-    a.slot_ptrs = carve<void *>(p, seg);
-    a.clens = carve<uint64_t>(p, seg);
-    a.crcs = carve<uint32_t>(p, seg);
-    a.sizes = carve<uint64_t>(p, seg);
-    a.offs = carve<uint64_t>(p, (size_t)seg + 1);
-    a.slots = (uint8_t *)ctx->fr_slots.p;
-    a.lo = a.cnt = 0;
-
-    const uint32_t tb = 256;
-    uint64_t most = total > n ? total : n;
-    HIP_TRY(ctx, hipMemsetAsync(a.carry, 0, sizeof(uint64_t), s));
-    hipLaunchKernelGGL(k_fb_counts, dim3((uint32_t)((n + tb - 1) / tb)),
-                       dim3(tb), 0, s, a);
-    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.counts,
-                       a.first, (uint32_t)n);
-    hipLaunchKernelGGL(k_fb_chunks, dim3((uint32_t)((most + tb - 1) / tb)),
-                       dim3(tb), 0, s, a);
-    for (uint32_t lo = 0; lo < total; lo += seg) {
-        const uint32_t cnt = total - lo < seg ? (uint32_t)total - lo : seg;
-        a.lo = lo;
-        a.cnt = cnt;
-        const uint32_t gb = (cnt + tb - 1) / tb;
-        // (the CRC beside the compressor, as in frame_compress_impl)
-        const bool side = ctx->frame_crc_side_stream;
-        if (side) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_crc[0], s));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_crc[0], 0));
-        }
-        hipLaunchKernelGGL(k_crc32c, dim3(cnt), dim3(64), 0,
-                           side ? ctx->stream2 : s, a.c_in + lo, a.c_len + lo,
-                           a.crcs, cnt, (const CrcTables *)ctx->fr_tables.p);
-        if (side)
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_crc[1], ctx->stream2));
-        rc = launch_compress(ctx, a.c_in + lo, a.c_len + lo, a.slot_ptrs,
-                             nullptr, a.clens, nullptr, cnt, cnt, 0, 0xF,
-                             c8[lo / seg]);
-        if (rc)
-            return rc;
-        if (side)
-            HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_crc[1], 0));
-        hipLaunchKernelGGL(k_fb_sizes, dim3(gb), dim3(tb), 0, s, a);
-        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.sizes,
-                           a.offs, cnt);
-        hipLaunchKernelGGL(k_fb_base, dim3(gb), dim3(tb), 0, s, a);
-        hipLaunchKernelGGL(k_fb_emit, dim3(cnt), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_fb_advance, dim3(1), dim3(1), 0, s, a);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return SNAPMI_OK;
-}
-
-// The per-stream scratch of a batch decode; false arguments are reported.
-static int fbd_begin(snapmi_ctx *ctx, const char *what,
-                     const void *const *d_in_ptrs, const uint64_t *d_in_lens,
-                     void *const *d_out_ptrs, const uint64_t *d_out_caps,
-                     uint64_t *d_out_lens, snapmi_error *d_errs, size_t n,
-                     FrameBatchDecodeArgs &a)
-{
-    if (!d_in_ptrs || !d_in_lens || !d_out_lens || (d_out_ptrs && !d_out_caps))
-        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "%s: bad args", what);
-    if (n > 0x7FFFFFFFu)
-        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
-                        "%s: %zu streams (at most 2^31 - 1)", what, n);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_tables(ctx);
-    if (rc)
-        return rc;
-    // per-stream scratch and per-chunk scratch in two buffers: the second is
-    // sized after the walk, and growing it must not drop the first
-    if ((rc = reserve(ctx, ctx->fb_streams,
-                      n * (8 + 8 + sizeof(snapmi_error) + 4 + 4) + 8 +
-                          16 * 8)))
-        return rc;
-    uint8_t *p = (uint8_t *)ctx->fb_streams.p;
-    a.in_ptrs = d_in_ptrs;
-    a.in_lens = d_in_lens;
-    a.out_ptrs = d_out_ptrs;
-    a.out_caps = d_out_caps;
-    a.out_lens = d_out_lens;
-    a.errs = d_errs;
-    a.n = (uint32_t)n;
-    a.total = 0;
-    a.counts = carve<uint64_t>(p, n);
-    a.first = carve<uint64_t>(p, n + 1);
-    a.serr = carve<snapmi_error>(p, n);
-    a.sidx = carve<uint32_t>(p, n);
-    a.first_bad = carve<uint32_t>(p, n);
-    return SNAPMI_OK;
-}
-
-// Everything behind the count of the batch's data chunks: the chunk records -
-// by the walk again, or from the host's list (l_first, list, bad:
-// k_fbd_from_list) -, lengths, descriptors, the codec, the checksums and the
-// verdicts.
-static int fbd_finish(snapmi_ctx *ctx, const char *what,
-                      FrameBatchDecodeArgs &a, uint64_t total,
-                      const uint64_t *l_first, const FwEntry *list,
-                      uint32_t *bad)
-{
-    hipStream_t s = ctx->stream;
-    const size_t n = a.n;
-    if (total > 0x7FFFFFFFu)
-        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
-                        "%s: %llu chunks (at most 2^31 - 1)", what,
-                        (unsigned long long)total);
-    const size_t t = (size_t)total;
-    int rc;
-    if ((rc = reserve(ctx, ctx->fb_chunks,
-                      t * (sizeof(FrameChunk) + 4 + 8 + 8 +
-                           2 * sizeof(snapmi_error) + 8 + 8 + 8 + 8 + 8 + 1 +
-                           4) + 8 + 16 * 16)))
-        return rc;
-    uint8_t *p = (uint8_t *)ctx->fb_chunks.p;
-    a.total = (uint32_t)total;
-    a.chunks = carve<FrameChunk>(p, t);
-    a.c_stream = carve<uint32_t>(p, t);
-    a.dlens = carve<uint64_t>(p, t);
-    a.offs = carve<uint64_t>(p, t + 1);
-    a.cerrs = carve<snapmi_error>(p, t);
-    a.derrs = carve<snapmi_error>(p, t);
-    a.c_in = carve<const void *>(p, t);
-    a.c_in_len = carve<uint64_t>(p, t);
-    a.c_out = carve<void *>(p, t);
-    a.c_caps = carve<uint64_t>(p, t);
-    a.c_out_lens = carve<uint64_t>(p, t);
-    a.modes = carve<uint8_t>(p, t);
-    a.crcs = carve<uint32_t>(p, t);
-    HIP_TRY(ctx, hipMemsetAsync(a.first_bad, 0xFF, n * sizeof(uint32_t), s));
-    const uint32_t tb = 256;
-    const uint32_t gc = total ? (uint32_t)((total + tb - 1) / tb) : 1;
-    const uint32_t gs = (uint32_t)((n + 63) / 64);
-    if (list)
-        hipLaunchKernelGGL(k_fbd_from_list,
-                           dim3((uint32_t)((total + n + tb - 1) / tb)),
-                           dim3(tb), 0, s, a, l_first, list, bad);
-    if (total) {
-        if (!list)
-            hipLaunchKernelGGL(k_fbd_walk_fill, dim3(gs), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(k_fbd_lens, dim3(gc), dim3(tb), 0, s, a);
-    }
-    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, s, a.dlens, a.offs,
-                       a.total);
-    if (a.out_ptrs && total) {
-        hipLaunchKernelGGL(k_fbd_desc, dim3(gc), dim3(tb), 0, s, a);
-        rc = launch_decompress(ctx, a.c_in, a.c_in_len, a.c_out, a.c_caps,
-                               a.c_out_lens, a.derrs, a.modes, t);
-        if (rc)
-            return rc;
-        hipLaunchKernelGGL(k_crc32c, dim3(a.total), dim3(64), 0, s,
-                           (const void *const *)a.c_out, a.c_out_lens, a.crcs,
-                           a.total, (const CrcTables *)ctx->fr_tables.p);
-    }
-    if (total)
-        hipLaunchKernelGGL(k_fbd_verify_chunks, dim3(gc), dim3(tb), 0, s, a);
-    hipLaunchKernelGGL(k_fbd_verify_streams,
-                       dim3((uint32_t)((n + tb - 1) / tb)), dim3(tb), 0, s, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SNAPMI_OK;
+    FrameList l;
+    l.in_ptrs = d_in_ptrs;
+    l.in_lens = d_in_lens;
+    l.out_ptrs = d_out_ptrs;
+    l.out_caps = d_out_caps;
+    l.out_lens = d_out_lens;
+    l.errs = d_errs;
+    l.n = n;
+    l.h_in_lens = h_in_lens;
+    l.total = total;
+    return frame_compress_list(ctx, l);
 }
 
 int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
@@ -1885,7 +1779,12 @@ int snapmi_frame_decompress_batch(snapmi_ctx *ctx,
     HIP_TRY(ctx, hipStreamSynchronize(s));
     const uint64_t total =
         (uint64_t)ctx->h_mail[0] | ((uint64_t)ctx->h_mail[1] << 32);
-    return fbd_finish(ctx, what, a, total, nullptr, nullptr, nullptr);
+    if ((rc = fbd_table(ctx, what, a, total)))
+        return rc;
+    // the same walk again, now with a place for every chunk record
+    if (total)
+        hipLaunchKernelGGL(k_fbd_walk_fill, dim3(gs), dim3(64), 0, s, a);
+    return fbd_finish(ctx, a);
 }
 
 } // extern "C"
@@ -1913,10 +1812,14 @@ int snapmi::frame_decompress_batch_listed(
     FrameBatchDecodeArgs a;
     int rc = fbd_begin(ctx, what, d_in_ptrs, d_in_lens, d_out_ptrs, d_out_caps,
                        d_out_lens, d_errs, n, a);
-    if (rc)
+    if (rc || (rc = fbd_table(ctx, what, a, total)))
         return rc;
-    return fbd_finish(ctx, what, a, total, d_first, (const FwEntry *)d_list,
-                      d_bad);
+    const uint32_t tb = 256;
+    hipLaunchKernelGGL(k_fbd_from_list,
+                       dim3((uint32_t)((total + n + tb - 1) / tb)), dim3(tb), 0,
+                       ctx->stream, a, d_first, (const FwEntry *)d_list,
+                       d_bad);
+    return fbd_finish(ctx, a);
 }
 
 extern "C" {
@@ -2131,9 +2034,17 @@ int snapmi_frame_encode_host(snapmi_ctx *ctx, const uint8_t *h_in,
             // (the chunk offsets are read where they lie, in pinned host
             // memory: a copy would wait behind the bulk copy of the next
             // slice; so would one of the result)
-            rc = snapmi::frame_compress_impl(
-                ctx, s.in.p, x.bytes, (uint32_t)cn, s.h_off, ident, s.out.p,
-                d_len, nullptr, h_chunk_lens + x.c0);
+            FrameList l;
+            l.lone = true;
+            l.in = s.in.p;
+            l.in_len = x.bytes;
+            l.out = s.out.p;
+            l.out_lens = d_len;
+            l.total = cn;
+            l.chunk_in_off = s.h_off;
+            l.h_chunk_lens = h_chunk_lens + x.c0;
+            l.ident = ident;
+            rc = frame_compress_list(ctx, l);
             if (rc)
                 return rc;
             hipLaunchKernelGGL(k_post_words, dim3(1), dim3(64), 0, sK,

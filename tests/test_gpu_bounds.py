@@ -457,6 +457,33 @@ def test_frame_calls_keep_to_their_buffers(ctx):
             out.assert_guards(f"frame_decompress of a corrupted case {i}")
 
 
+def test_frame_chunks_call_keeps_to_its_buffer(built):
+    """snapmi_frame_compress_chunks without the identifier, the chunks cut by
+    the caller, in segments of 64 chunks: an output buffer of exactly
+    total + 8 n bytes between bands."""
+    import ctypes as C
+    from rust_snappy_amd import _lib
+    from test_gpu_frame import cut_chunks, frame_of_chunks, segment_context
+    c = segment_context()
+    data, lens, chunks = cut_chunks()
+    n = len(lens)
+    h_lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    src = Guarded([len(data)], 7, aligned=False, fill=[data])
+    cap = len(data) + 8 * n
+    dst = Guarded([cap], 8, aligned=False)
+    out_len = torch.zeros(1, dtype=torch.int64, device="cuda")
+    rc = _lib.of(c).snapmi_frame_compress_chunks(
+        c._h, C.c_void_p(int(src.d_ptrs[0].item())),
+        h_lens.ctypes.data_as(C.c_void_p), n, 1,
+        C.c_void_p(int(dst.d_ptrs[0].item())), cap,
+        C.c_void_p(out_len.data_ptr()), None)
+    assert rc == 0
+    c.synchronize()
+    dst.assert_guards("frame_compress_chunks")
+    assert dst.bytes(0, int(out_len.item())) == frame_of_chunks(chunks)[10:]
+    c.close()
+
+
 def test_host_frame_calls_keep_to_their_buffers(ctx):
     """snapmi_frame_encode_host / _decode_host (the copy kernel k_to_host
     writes mapped pinned memory): pinned buffers with bands around the

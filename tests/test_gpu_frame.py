@@ -857,6 +857,171 @@ def test_frame_compress_chunks_on_device_buffers(ctx):
     assert out[:n].cpu().numpy().tobytes() == want
     out, n = frame.compress_chunks_device(ctx, d_in, lens, ident=False)
     assert out[:n].cpu().numpy().tobytes() == want[10:]
+    # 150 chunks in segments of 64: two segment boundaries inside the stream,
+    # from device memory and (encode_host_into: the offsets are read where the
+    # host wrote them) from a pinned buffer
+    c = segment_context()
+    data, lens, chunks = cut_chunks()
+    want = frame_of_chunks(chunks)
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    h_in = frame.HostBuffer(len(data))
+    h_in.array[:] = np.frombuffer(data, dtype=np.uint8)
+    h_out = frame.HostBuffer(10 + len(data) + 8 * len(lens))
+    try:
+        for ident in (True, False):
+            out, n = frame.compress_chunks_device(c, d_in, lens, ident=ident)
+            assert out[:n].cpu().numpy().tobytes() == want[0 if ident else 10:]
+            k = frame.encode_host_into(c, h_in.view, lens, h_out, ident=ident)
+            assert bytes(h_out.view[:k]) == want[0 if ident else 10:], ident
+    finally:
+        h_in.close()
+        h_out.close()
+        c.close()
+
+
+CUT_SIZES = [1, 17, 4096, 8192, 8193, 65535, 65536]
+
+
+def cut_chunks(count=150, seed=3):
+    """(data, lens, chunks): `count` chunks of CUT_SIZES bytes, as a caller of
+    snapmi_frame_compress_chunks / _encode_host might cut its input."""
+    rng = random.Random(seed)
+    lens = [rng.choice(CUT_SIZES) for _ in range(count)]
+    assert set(lens) == set(CUT_SIZES)
+    src = b"".join(d for _, d in O.corpus_round())
+    data = (src * (sum(lens) // len(src) + 1))[:sum(lens)]
+    chunks, pos = [], 0
+    for n in lens:
+        chunks.append(data[pos:pos + n])
+        pos += n
+    return data, lens, chunks
+
+
+def segment_context():
+    """The lane kernel in segments of 64 chunks (262 144 by default)."""
+    import rust_snappy_amd as R
+    c = R.raw.Context(0)
+    c.set_option("compress_mode", 1)
+    c.set_option("lane_min_blocks", 1)
+    c.set_option("lane_segment_blocks", 64)
+    return c
+
+
+@pytest.mark.parametrize("ident", [True, False])
+def test_frame_compress_chunks_writes_the_side_index(built, ident):
+    """d_chunk_offsets of snapmi_frame_compress_chunks: entry i is where chunk
+    i's header lies, entry n the frame's length, whatever the segmentation;
+    decoding with that index returns the data."""
+    import ctypes as C
+    from rust_snappy_amd import _lib, frame
+    c = segment_context()
+    data, lens, chunks = cut_chunks()
+    want = frame_of_chunks(chunks)[0 if ident else 10:]
+    n = len(lens)
+    h_lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    cap = (10 if ident else 0) + len(data) + 8 * n
+    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    out = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    out_len = torch.zeros(1, dtype=torch.int64, device="cuda")
+    index = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    rc = _lib.of(c).snapmi_frame_compress_chunks(
+        c._h, C.c_void_p(d_in.data_ptr()), h_lens.ctypes.data_as(C.c_void_p),
+        n, 0 if ident else 1, C.c_void_p(out.data_ptr()), cap,
+        C.c_void_p(out_len.data_ptr()), C.c_void_p(index.data_ptr()))
+    assert rc == 0
+    c.synchronize()
+    flen = int(out_len.item())
+    assert out[:flen].cpu().numpy().tobytes() == want
+    where, pos = [], 10 if ident else 0
+    for ch in chunks:
+        where.append(pos)
+        pos += len(O.frame_compress(ch)) - 10
+    assert index.cpu().tolist() == where + [len(want)]
+    assert where[0] == (10 if ident else 0)
+    got = frame.decompress_batch_device(c, out, flen, n, index=index,
+                                        continuation=not ident)
+    assert got == (data, None)
+    c.close()
+
+
+def lone_decode(ctx, stream, out, cap, index=None):
+    """snapmi_frame_decompress of `stream` into the device address `out`
+    (None: lengths only): (length, (kind, a, b, c))."""
+    import ctypes as C
+    from rust_snappy_amd import _lib, batch
+    d_in = torch.frombuffer(bytearray(stream), dtype=torch.uint8).cuda()
+    out_len = torch.zeros(1, dtype=torch.int64, device="cuda")
+    err = torch.zeros(32, dtype=torch.uint8, device="cuda")
+    rc = _lib.of(ctx).snapmi_frame_decompress(
+        ctx._h, C.c_void_p(d_in.data_ptr()), len(stream),
+        C.c_void_p(out) if out is not None else None, cap,
+        C.c_void_p(out_len.data_ptr()), C.c_void_p(err.data_ptr()),
+        C.c_void_p(index.data_ptr()) if index is not None else None,
+        index.numel() - 1 if index is not None else 0)
+    assert rc == 0
+    ctx.synchronize()
+    return int(out_len.item()), batch.read_errors(err)[0]
+
+
+def test_frame_chunk_table_retry_in_a_lone_decode(ctx):
+    """300 one-byte chunks in 2710 bytes: more data chunks than the first
+    pass's chunk table holds (in_len / 2048 + 64), so the call walks the
+    stream again with the exact count."""
+    from test_gpu_bounds import Guarded
+    chunks = [bytes([i & 255]) for i in range(300)]
+    data = b"".join(chunks)
+    s = frame_of_chunks(chunks)
+    assert len(s) // 2048 + 64 < 300
+    assert O.frame_decompress(s) == data
+    out = Guarded([300], seed=1)
+    assert lone_decode(ctx, s, int(out.d_ptrs[0].item()), 300) == \
+        (300, (0, 0, 0, 0))
+    out.assert_guards("frame_decompress behind a chunk table retry")
+    assert out.bytes(0, 300) == data
+    # one byte short: BufferTooSmall{given, needed}, nothing written
+    out = Guarded([299], seed=2)
+    before = out.fetch().copy()
+    assert lone_decode(ctx, s, int(out.d_ptrs[0].item()), 299) == \
+        (0, (2, 299, 300, 0))
+    assert (out.fetch() == before).all()
+    assert lone_decode(ctx, s, None, 0) == (300, (0, 0, 0, 0))
+
+
+def test_lone_stream_fronts_give_the_oracles_verdict(built):
+    """The three fronts of snapmi_frame_decompress - the parallel header
+    walk, the sequential walk, a side index - hand one chunk table to the
+    same kernels: a wrong checksum in chunk 25 of 40 is the oracle's Checksum
+    error behind the bytes of the 25 chunks in front, by each of them."""
+    import rust_snappy_amd as R
+    from rust_snappy_amd import frame
+    par = R.raw.Context(0)
+    par.set_option("frame_parallel_walk_min", 0)
+    par.set_test_option("frame_walk_segment", 128 << 10)
+    seq = R.raw.Context(0)
+    seq.set_option("frame_parallel_walk_min", 1 << 60)
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("lcet10.txt", "plrabn12.txt"))
+    chunks = [text[20000 * i:20000 * (i + 1)] for i in range(40)]
+    assert len(chunks[-1]) == 20000
+    f = bytearray(frame_of_chunks(chunks))
+    assert len(f) > 3 * (128 << 10)          # several segments of the walk
+    offs = frame.index_host(bytes(f))
+    assert len(offs) == 41
+    f[int(offs[25]) + 4] ^= 1
+    f = bytes(f)
+    with pytest.raises(O.SnapError) as oe:
+        O.frame_decompress(f)
+    oe = oe.value
+    assert oe.name == "Checksum"
+    d_in = torch.frombuffer(bytearray(f), dtype=torch.uint8).cuda()
+    index = torch.from_numpy(offs).cuda()
+    for cx, idx in ((par, None), (seq, None), (seq, index)):
+        good, err = frame.decompress_batch_device(cx, d_in, len(f), 40, idx)
+        assert err is not None
+        assert (err.kind,) + err.abc == (oe.kind, oe.a, oe.b, oe.c)
+        assert good == b"".join(chunks[:25])
+    par.close()
+    seq.close()
 
 
 def test_host_calls_on_pinned_buffers(ctx):

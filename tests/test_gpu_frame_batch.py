@@ -21,6 +21,9 @@ IDENT = b"\xff\x06\x00\x00sNaPpY"
 OK = (0, 0, 0, 0)
 BUFFER_TOO_SMALL = 2
 UNEXPECTED_EOF = 64          # SNAPMI_E_UNEXPECTED_EOF (the oracle says -1)
+# errors that only decoding a chunk's payload brings out
+DECODE_STAGE = {"HeaderMismatch", "Literal", "CopyRead", "CopyWrite", "Offset",
+                "Checksum"}
 CORPUS = ["html", "urls.10K", "fireworks.jpeg", "paper-100k.pdf", "html_x_4",
           "alice29.txt", "asyoulik.txt", "lcet10.txt", "plrabn12.txt",
           "geo.protodata", "kppkn.gtb", "Mark.Twain-Tom.Sawyer.txt"]
@@ -81,6 +84,27 @@ def oracle_verdict(s):
         return None, oe
 
 
+def declared_len(s):
+    """What the data chunks of a structurally sound stream say they hold: a
+    stored chunk's payload, the varint in front of a compressed one."""
+    pos, total = 0, 0
+    while pos < len(s):
+        ty, n = s[pos], int.from_bytes(s[pos + 1:pos + 4], "little")
+        body = s[pos + 8:pos + 4 + n]
+        if ty == 1:
+            total += len(body)
+        elif ty == 0:
+            v = shift = 0
+            for b in body:
+                v |= (b & 0x7F) << shift
+                shift += 7
+                if b < 0x80:
+                    break
+            total += v
+        pos += 4 + n
+    return total
+
+
 def assert_oracle_error(got, oe, s):
     if oe.kind == -1:
         assert got[0] == UNEXPECTED_EOF, (got, oe)
@@ -138,7 +162,7 @@ def test_decompress_many_round_trip_equals_single_calls(ctx):
     for i, d in enumerate(datas):
         got = dst.stream_bytes(i, lens[i])
         assert errs[i] == OK, (i, errs[i])
-        assert got == d, i
+        assert got == d == O.frame_decompress(framed[i]), i
         assert single_decode(ctx, framed[i], len(d)) == \
             (int(lens[i]), errs[i], got), i
 
@@ -242,6 +266,17 @@ def test_lengths_only_equals_single_calls(ctx):
         assert (int(lens[i]), errs[i]) == (n, e), i
         if origs[i] is not None:
             assert (int(lens[i]), errs[i]) == (len(origs[i]), OK)
+        # the oracle's verdict, as far as a call that decodes nothing can
+        # reach it: what the raw decoder or a checksum would find stays unseen
+        # (every stream here has one defect at the most)
+        want, oe = oracle_verdict(s)
+        if oe is None:
+            assert (int(lens[i]), errs[i]) == (len(want), OK), i
+        elif errs[i] != OK:
+            assert_oracle_error(errs[i], oe, s)
+        else:
+            assert O.KIND_NAMES[oe.kind] in DECODE_STAGE, (i, oe)
+            assert int(lens[i]) == declared_len(s), i
 
 
 @pytest.mark.parametrize("aligned", [True, False])
@@ -310,6 +345,12 @@ def test_decompress_cap_one_short_and_guards(ctx, aligned):
             assert (gout.host[o:o + caps[i]] == before[o:o + caps[i]]).all()
         elif i < len(datas):
             assert (errs[i], got) == (OK, datas[i]), i
+        else:
+            want, oe = oracle_verdict(s)
+            if oe is None:
+                assert (errs[i], got) == (OK, want), i
+            else:
+                assert_oracle_error(errs[i], oe, s)
         assert single_decode(ctx, s, caps[i]) == (int(lens[i]), errs[i], got)
     assert short >= 5
 

@@ -1617,6 +1617,151 @@ def raw_writes(args, ctx, dev):
     return res
 
 
+def raw_appends(args, ctx, dev):
+    """Appends through the block index (snapmi_append_indexed) on the 256
+    streams of 1 MiB of text of raw_writes, with the index compress wrote:
+    4 KiB per stream (the streams are block-aligned: no tail is decoded), the
+    same with the streams cut to 1 MiB - 1000 bytes (every tail is decoded),
+    64 KiB per stream, 1 MiB per stream - each beside the whole-stream way to
+    the same result: snapmi_decompress_batch_indexed of the streams, a device
+    copy of the new bytes behind them, and snapmi_compress_batch_indexed of
+    the concatenation; in this process on one context, five alternating
+    repeats of --steps calls each (medians, and the spread max - min over the
+    repeats).  Writes profiles/raw_appends.json (--sets 4k,1m:append,...: only
+    these shapes, only that way - for a kernel trace; nothing is written)."""
+    import random
+    import statistics
+    import oracle_lib as O
+    from rust_snappy_amd import batch, raw
+    text = b"".join((O.CORPUS / n).read_bytes()
+                    for n in ("alice29.txt", "asyoulik.txt", "lcet10.txt",
+                              "plrabn12.txt")) * 2
+    rng = random.Random(0x5EED)
+    n, size = 256, 1 << 20
+    datas = []
+    for _ in range(n):
+        o = rng.randrange(len(text) - size)
+        datas.append(text[o:o + size])
+    # shape: (old length of every stream, bytes appended to each)
+    shapes = {"4k": (size, 4096), "4k_tail": (size - 1000, 4096),
+              "64k": (size, 65536), "1m": (size, size)}
+    ways = ("append", "whole")
+    if args.sets:
+        picked = [x.partition(":") for x in args.sets.split(",")]
+        shapes = {k: v for k, v in shapes.items()
+                  if k in [x[0] for x in picked]}
+        ways = tuple(w for w in ways
+                     if any(x[2] in ("", w) for x in picked))
+    repeats = 5
+    res = {"config": "raw_appends: appends through the block index vs decode "
+                     "whole + copy + compress whole of the same 256 streams "
+                     "of 1 MiB of text",
+           "steps": args.steps, "repeats": repeats, "streams": n}
+    side = torch.cuda.ExternalStream(ctx.stream) if ctx.stream \
+        else torch.cuda.default_stream(dev)
+    timers, olds = {}, {}
+    for key, (old, add) in shapes.items():
+        if old not in olds:
+            src = batch.StreamBatch.from_bytes([d[:old] for d in datas], dev)
+            olds[old] = batch.compress(ctx, src, want_index=True)
+        comp, first, index = olds[old]
+        entries = index.numel()
+        new_len = old + add
+        h_old = [old] * n
+        news = []
+        for _ in range(n):
+            o = rng.randrange(len(text) - add)
+            news.append(text[o:o + add])
+        asrc = batch.StreamBatch.from_bytes(news, dev)
+        a_ptrs = [int(p) for p in asrc.d_ptrs.cpu().tolist()]
+        a_lens = [add] * n
+        new_entries = raw.block_index_entries([new_len] * n)
+        cap = raw.max_compress_len(new_len)
+        # the append way's buffers
+        out = batch.StreamBatch.empty([cap] * n, dev)
+        olens = torch.zeros(n, dtype=torch.int64, device=dev)
+        oerrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+        ofirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        oindex = torch.zeros(new_entries, dtype=torch.int64, device=dev)
+        # the whole-stream way's buffers: the decoded streams with room for
+        # the new bytes, the concatenations compressed, their index
+        back = batch.StreamBatch.empty([new_len] * n, dev)
+        blens = torch.zeros(n, dtype=torch.int64, device=dev)
+        berrs = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+        again = batch.StreamBatch.empty([cap] * n, dev)
+        alens = torch.zeros(n, dtype=torch.int64, device=dev)
+        afirst = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        aindex = torch.zeros(new_entries, dtype=torch.int64, device=dev)
+        h_new = torch.full((n,), new_len, dtype=torch.int64)
+        # (the whole-stream way's copy: one strided copy of all new bytes -
+        # the streams of `back` lie a fixed stride apart)
+        new_rows = torch.from_numpy(
+            np.frombuffer(b"".join(news), dtype=np.uint8).copy()).to(
+                dev).view(n, add)
+        stride = int(back.offsets[1])
+        assert list(back.offsets) == [i * stride for i in range(n)]
+        behind = back.data[:n * stride].view(n, stride)[:, old:new_len]
+
+        def append(comp=comp, first=first, index=index, entries=entries,
+                   h_old=h_old, a_ptrs=a_ptrs, a_lens=a_lens, out=out,
+                   olens=olens, oerrs=oerrs, ofirst=ofirst, oindex=oindex,
+                   new_entries=new_entries):
+            raw.append_indexed(
+                ctx, comp.d_ptrs, comp.d_lens, h_old, first, index, a_ptrs,
+                a_lens, out.d_ptrs, out.d_lens, olens, oerrs, ofirst, oindex,
+                index_entries=entries, new_index_cap=new_entries)
+
+        def whole(comp=comp, first=first, index=index, entries=entries,
+                  back=back, blens=blens, berrs=berrs, again=again,
+                  alens=alens, afirst=afirst, aindex=aindex, h_new=h_new,
+                  new_rows=new_rows, behind=behind, new_entries=new_entries):
+            raw.decompress_batch(ctx, comp.d_ptrs, comp.d_lens, back.d_ptrs,
+                                 back.d_lens, blens, berrs, index_first=first,
+                                 index=index, index_entries=entries)
+            with torch.cuda.stream(side):  # (the context's stream)
+                behind.copy_(new_rows)
+            raw.compress_batch(ctx, back.d_ptrs, back.d_lens, again.d_ptrs,
+                               again.d_lens, alens, None, host_in_lens=h_new,
+                               index_first=afirst, index=aindex,
+                               index_cap=new_entries)
+        append()
+        whole()
+        ctx.synchronize()
+        torch.cuda.synchronize()
+        assert all(e[0] == 0 for e in batch.read_errors(oerrs))
+        # both ways give the same streams and the same index
+        assert torch.equal(olens, alens) and torch.equal(oindex, aindex)
+        assert torch.equal(ofirst, afirst)
+        for i in (0, n // 2, n - 1):
+            assert out.stream_bytes(i, int(olens[i])) == \
+                again.stream_bytes(i, int(alens[i]))
+        res[key] = {"old_bytes": old, "appended_bytes": add,
+                    "append_blocks": ctx.info("append_blocks"),
+                    "append_blocks_decoded":
+                        ctx.info("append_blocks_decoded")}
+        if "append" in ways:
+            timers["append_" + key] = (lambda append=append:
+                                       time_it(append, args.steps, ctx))
+        if "whole" in ways:
+            timers["whole_" + key] = (lambda whole=whole:
+                                      time_it(whole, args.steps, ctx))
+    t = {k: [] for k in timers}
+    for _ in range(repeats):
+        for k, fn in timers.items():
+            t[k].append(fn() * 1e3)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    res["ms_median"] = {k: round(v, 4) for k, v in med.items()}
+    res["ms_spread"] = {k: round(max(v) - min(v), 4) for k, v in t.items()}
+    res["ms_repeats"] = {k: [round(x, 4) for x in v] for k, v in t.items()}
+    if not args.sets:
+        for key in shapes:
+            res[key]["over_whole"] = round(
+                med["append_" + key] / med["whole_" + key], 3)
+        (ROOT / "profiles" / "raw_appends.json").write_text(
+            json.dumps(res) + "\n")
+    return res
+
+
 class HostArena:
     """buffers of the given sizes, 64 bytes apart at least, in one
     pageable array or one snapmi_host_alloc allocation"""
@@ -2007,7 +2152,8 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--sets", default="",
                     help="frames_host_batch: only these data sets (a,b,...); "
-                         "raw_ranges, raw_writes: only these shapes, nothing "
+                         "raw_ranges, raw_writes, raw_appends: only these "
+                         "shapes, nothing "
                          "recorded")
     ap.add_argument("--plan", default="",
                     help="name:gib,... - run these configs at these sizes, "
@@ -2037,7 +2183,7 @@ def main():
              "frames_batch": frames_batch, "host_batch": host_batch,
              "frames_host_batch": frames_host_batch, "raw_index": raw_index,
              "raw_ranges": raw_ranges, "raw_index_build": raw_index_build,
-             "raw_writes": raw_writes}
+             "raw_writes": raw_writes, "raw_appends": raw_appends}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -2062,7 +2208,8 @@ def main():
                      ("raw_index", raw_index),
                      ("raw_ranges", raw_ranges),
                      ("raw_index_build", raw_index_build),
-                     ("raw_writes", raw_writes)):
+                     ("raw_writes", raw_writes),
+                     ("raw_appends", raw_appends)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
@@ -2070,7 +2217,8 @@ def main():
                                                          "raw_index",
                                                          "raw_ranges",
                                                          "raw_index_build",
-                                                         "raw_writes")):
+                                                         "raw_writes",
+                                                         "raw_appends")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

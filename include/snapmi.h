@@ -285,7 +285,9 @@ SNAPMI_API const char *snapmi_version(void);
  *                          64 KiB rooms (one an edge block)
  *                          snapmi_write_ranges_indexed may hold at once
  *                          (default 1 GiB, at least 142 032: one block's slot
- *                          and room; a bound on memory, not a tuned number)
+ *                          and room; a bound on memory, not a tuned number);
+ *                          snapmi_append_indexed holds the same scratch under
+ *                          the same cap: a slot a new block, a room a tail
  * The knobs of the test suite and of the experiment drivers are declared in
  * snapmi_test.h (snapmi_ctx_set_test_option).
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
@@ -349,6 +351,12 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *                           (snapmi_write_blocks of its lists),
  *   "write_blocks_decoded"  the edge blocks among them, which were decoded, and
  *   "write_streams_ok" / "write_streams_failed"  touched streams of it that
+ *                           succeeded / failed (these two wait for the call)
+ *   "append_blocks"         new blocks the last snapmi_append_indexed
+ *                           compressed, from the host's copies,
+ *   "append_blocks_decoded" the tails it decoded (named streams whose old
+ *                           length is no multiple of 65536), and
+ *   "append_streams_ok" / "append_streams_failed"  named streams of it that
  *                           succeeded / failed (these two wait for the call)
  *   "index_build_built" / "index_build_unaligned" / "index_build_corrupt" /
  *   "index_build_missized"  streams of the last snapmi_build_block_index by
@@ -736,6 +744,98 @@ SNAPMI_API int snapmi_write_ranges_indexed(
     size_t m, void *const *d_out_ptrs, const uint64_t *d_out_caps,
     uint64_t *d_out_lens, snapmi_error *d_errs /* may be NULL */,
     uint64_t *d_new_index /* out, [index_entries] */);
+
+/*
+ * APPENDS through the block index: stream i gets the h_app_len[i] bytes at
+ * h_app_src[i] (DEVICE memory) appended to its OUTPUT, and only the stream's
+ * short last block and the new bytes go through the codec - every full old
+ * block keeps its compressed bytes, which are copied.  h_app_len[i] == 0
+ * means "not named".
+ *
+ * Host copies.  h_out_lens[i] is the length stream i's header announces, as
+ * for snapmi_build_block_index; h_out_lens and h_app_len are required and
+ * size the new index, the scratch and every launch.  The device never trusts
+ * h_out_lens.  The append lists (h_app_src, h_app_len) are HOST arrays, read
+ * before the call returns; the device gets the host's own copy of them.
+ * New index.  Stream i owns ceil((h_out_lens[i] + h_app_len[i]) / 65536) + 1
+ * entries, whatever becomes of it; d_new_index_first [n + 1] is the prefix sum
+ * of those counts, written by the call, and their total is
+ * snapmi_block_index_entries of the summed lengths.  new_index_cap below the
+ * total is SNAPMI_E_ARGUMENT, and nothing is enqueued or written; entries at
+ * or behind the total are never written.
+ *   Host checks (SNAPMI_E_ARGUMENT with snapmi_last_error; nothing is
+ *     enqueued, nothing written): a NULL pointer other than d_errs; a named
+ *     stream with a NULL source; h_out_lens[i] + h_app_len[i] wraps;
+ *     n + index_entries + new entries + new blocks not below 2^31.  n == 0
+ *     enqueues nothing.  If every h_app_len is 0 the call still runs, and
+ *     every stream is one nobody names.
+ *   Blocks.  With dlen the old length and kf = dlen / 65536, blocks [0, kf)
+ *     are the old FULL blocks: their compressed bytes [entry 0, entry kf) are
+ *     copied, neither read as elements nor judged.  If dlen % 65536 != 0,
+ *     block kf is the TAIL: its piece (see the range reads) is decoded into a
+ *     64 KiB room of scratch, the first 65536 - dlen % 65536 appended bytes
+ *     are laid behind it, and the room is compressed as the first new block.
+ *     Every further new block is compressed straight from the source, 65536
+ *     bytes each, the last one maybe shorter.  A stream whose old length is a
+ *     multiple of 65536 - 0, the stream whose one entry is {1}, included -
+ *     decodes nothing.
+ *   A stream that succeeds: d_out_ptrs[i][0, d_out_lens[i]) is
+ *     varint(dlen + add), the copied old bytes and, for every new block, what
+ *     the compressor gives that block (without its varint); the new entries
+ *     are the new varint's length and the running sums, the last one
+ *     d_out_lens[i].  Exactly [0, d_out_lens[i]) is written.  For a stream
+ *     whose blocks are self-contained this is, bit for bit,
+ *     snapmi_compress_batch_indexed of the old data followed by the appended
+ *     data (the varint may grow a byte: every entry then shifts).
+ *   A stream nobody names: nothing of its buffer is written, d_out_lens[i] =
+ *     0 and the error kind is 0 ("keep the old one", as for the writes).  Its
+ *     old entries are copied to its place in the new index when d_index_first
+ *     gives it exactly its count of entries inside [0, index_entries);
+ *     otherwise its new entries are all 0.
+ *   A stream that fails: d_out_lens[i] = 0, NOT ONE BYTE of its buffer is
+ *     written, and all its new entries are 0 - the caller keeps the old
+ *     stream and the old index.  Why, in this order:
+ *       the header does not parse      the error snapmi_decompress_len_batch
+ *                                      gives the stream
+ *       it announces another length    SNAPMI_E_ARGUMENT {i, announced,
+ *                                      h_out_lens[i]}
+ *       dlen + add > 2^32 - 1          SNAPMI_TOO_BIG {dlen + add, 4294967295}
+ *                                      (reference src/compress.rs,
+ *                                      Encoder::compress)
+ *       no usable index                the stream's rule of the range reads
+ *         (SNAPMI_E_ARGUMENT {i, 0}), and entry k < entry k + 1 <= compressed
+ *         length for every old block (SNAPMI_E_ARGUMENT {i, first bad block})
+ *       the tail's piece fails or is not full   that piece's error as
+ *         snapmi_decompress_ranges_indexed reports it
+ *       cap < new length               SNAPMI_BUFFER_TOO_SMALL {cap, new
+ *                                      length}; an exact cap passes
+ *   Whatever the streams, d_in_lens, d_index_first and the index hold,
+ *   nothing is written outside d_out_ptrs[i][0, cap_i), d_out_lens[0, n),
+ *   d_errs[0, n), d_new_index_first[0, n] and d_new_index[0, total), no input
+ *   byte at or behind d_in_lens[i] and no entry at or behind index_entries is
+ *   read.
+ * Outputs must not overlap the inputs, the old index or the sources.
+ * Everything runs on the context's stream.  The host waits only for scratch
+ * that must grow, or for the event of its own earlier staging copy; capture
+ * into a hipGraph is not promised.  Scratch: a compress slot per new block and
+ * a 64 KiB room per tail; option "write_scratch_bytes" caps what is alive at
+ * once - the host cuts the named streams into consecutive groups of whole
+ * streams that fit (a stream that exceeds it alone is a group of its own),
+ * the groups run back to back and reuse the scratch.  Info "append_blocks",
+ * "append_blocks_decoded", "append_streams_ok" and "append_streams_failed"
+ * describe the last call; reading the last two waits for it.
+ */
+SNAPMI_API int snapmi_append_indexed(
+    snapmi_ctx *ctx, const void *const *d_in_ptrs, const uint64_t *d_in_lens,
+    const uint64_t *h_out_lens /* host copy: the length each header announces */,
+    size_t n, const uint64_t *d_index_first /* [n+1] */,
+    const uint64_t *d_index, uint64_t index_entries,
+    const void *const *h_app_src /* HOST array of DEVICE pointers */,
+    const uint64_t *h_app_len /* HOST */,
+    void *const *d_out_ptrs, const uint64_t *d_out_caps,
+    uint64_t *d_out_lens, snapmi_error *d_errs /* may be NULL */,
+    uint64_t *d_new_index_first /* out, [n+1] */,
+    uint64_t *d_new_index /* out */, uint64_t new_index_cap);
 
 /*
  * The block index of streams that came WITHOUT one - written by the

@@ -85,6 +85,9 @@ SYMBOLS = [
     ("snapmi_write_ranges_indexed", C.c_int,
      [_P, _P, _P, _SZ, _P, _P, C.c_uint64, _P, _P, _P, _P, _SZ, _P, _P, _P,
       _P, _P]),
+    ("snapmi_append_indexed", C.c_int,
+     [_P, _P, _P, _P, _SZ, _P, _P, C.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P,
+      C.c_uint64]),
     ("snapmi_build_block_index", C.c_int,
      [_P, _P, _P, _P, _P, _SZ, _P, _P, C.c_uint64, _P]),
     ("snapmi_decompress_len_batch", C.c_int, [_P, _P, _P, _P, _P, _SZ]),

@@ -257,3 +257,62 @@ def write_ranges(ctx, src: StreamBatch, index, writes):
             parts.append(torch.zeros(pad, dtype=torch.uint8, device=dev))
     merged = StreamBatch(torch.cat(parts), offs, lens)
     return merged, (index_first, new_index), read_errors(errs)
+
+
+def append(ctx, src: StreamBatch, index, appends):
+    """Appends to compressed streams: appends is a list of (stream, bytes),
+    a stream at most once; the bytes go behind the stream's OUTPUT.  index:
+    the (index_first, index) pair of the streams.  Only a stream's short last
+    block and the new bytes go through the codec, the full old blocks'
+    compressed bytes are copied (snapmi_append_indexed).  Returns (the new
+    StreamBatch - a stream nobody names, or whose append failed, is the old
+    one -, the new (index_first, index) pair, per-stream errors as (kind, a,
+    b, c)).  A stream that failed has all its new entries 0: its old index
+    is the caller's to keep."""
+    dev = src.data.device
+    index_first, index_tensor = index
+    add = [b""] * src.n
+    for s, b in appends:
+        assert not add[int(s)], f"stream {s} is named twice"
+        add[int(s)] = bytes(b)
+    dlens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+    raw.decompress_len_batch(ctx, src.d_ptrs, src.d_lens, dlens)
+    ctx.synchronize()
+    dlens = [int(d) & (2**64 - 1) for d in dlens.cpu().tolist()]
+    data = StreamBatch.from_bytes(add, dev)
+    # a named stream takes its old bytes, a header that may grow, and at most
+    # the worst case of every block the codec sees: the tail's and the new ones
+    caps = [int(src.lens[i]) + 5 + (len(b) // 65536 + 2) *
+            raw.max_compress_len(65536) if b else 0
+            for i, b in enumerate(add)]
+    dst = StreamBatch.empty(caps, dev)
+    out_lens = torch.zeros(src.n, dtype=torch.int64, device=dev)
+    errs = torch.zeros(32 * src.n, dtype=torch.uint8, device=dev)
+    entries = raw.block_index_entries([d + len(b)
+                                       for d, b in zip(dlens, add)])
+    new_first = torch.zeros(src.n + 1, dtype=torch.int64, device=dev)
+    new_index = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+    raw.append_indexed(
+        ctx, src.d_ptrs, src.d_lens, dlens, index_first, index_tensor,
+        [int(p) if b else 0
+         for p, b in zip(data.d_ptrs.cpu().tolist(), add)],
+        [len(b) for b in add], dst.d_ptrs, dst.d_lens, out_lens, errs,
+        new_first, new_index, index_entries=index_tensor.numel(),
+        new_index_cap=entries)
+    ctx.synchronize()
+    out_lens = out_lens.cpu().numpy()
+    # one slab of the streams to keep and the new ones
+    offs, lens, parts, pos = [], [], [], 0
+    for i in range(src.n):
+        from_, n = (dst, int(out_lens[i])) if out_lens[i] else \
+            (src, int(src.lens[i]))
+        o = int(from_.offsets[i])
+        parts.append(from_.data[o:o + n])
+        offs.append(pos)
+        lens.append(n)
+        pos += _align(max(n, 1))
+        pad = pos - offs[-1] - n
+        if pad:
+            parts.append(torch.zeros(pad, dtype=torch.uint8, device=dev))
+    merged = StreamBatch(torch.cat(parts), offs, lens)
+    return merged, (new_first, new_index[:entries]), read_errors(errs)

@@ -255,7 +255,7 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
         if (b->p)
             (void)hipFree(b->p);
     for (hipEvent_t ev :
-         {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1], ctx->ev_wr})
+         {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1], ctx->ev_wr, ctx->ev_ap})
         if (ev)
             (void)hipEventDestroy(ev);
     for (auto &ev : ctx->ev)
@@ -722,6 +722,21 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                                    hipMemcpyDeviceToHost));
         }
         *value = (int64_t)(name[14] == 'o' ? w[0] : w[1]);
+    } else if (strcmp(name, "append_blocks") == 0) {
+        *value = (int64_t)ctx->ap_blocks;
+    } else if (strcmp(name, "append_blocks_decoded") == 0) {
+        *value = (int64_t)ctx->ap_decoded;
+    } else if (strcmp(name, "append_streams_ok") == 0 ||
+               strcmp(name, "append_streams_failed") == 0) {
+        // of the last snapmi_append_indexed: wait for it
+        unsigned long long w[2] = {0, 0};
+        if (ctx->ap_stats_live && ctx->ap_stat.p) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(w, ctx->ap_stat.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        *value = (int64_t)(name[15] == 'o' ? w[0] : w[1]);
     } else if (strncmp(name, "index_build_", 12) == 0 &&
                (strcmp(name + 12, "built") == 0 ||
                 strcmp(name + 12, "unaligned") == 0 ||

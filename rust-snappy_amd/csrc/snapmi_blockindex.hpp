@@ -10,6 +10,7 @@
 //   bi_piece          input and output range of piece k of an indexed stream
 //   bi_range_*        the rules of a range read (snapmi_decompress_ranges_indexed)
 //   bi_write_*        the rules of a range write (snapmi_write_ranges_indexed)
+//   bi_append_*       the rules of an append (snapmi_append_indexed)
 //   bi_build          the index of a stream that came without one: the
 //                     sequential definition of snapmi_build_block_index
 //
@@ -400,6 +401,161 @@ SNAPMI_BI_HD inline uint64_t bi_write_entry(const uint64_t *e, uint64_t k,
 SNAPMI_BI_HD inline bool bi_write_fits(uint64_t cap, uint64_t new_len)
 {
     return new_len <= cap;
+}
+
+// ---------------------------------------------------------------------
+// Appends (snapmi_append_indexed): `add` bytes behind the dlen bytes of a
+// stream's OUTPUT.  The old FULL blocks [0, kf) keep their compressed bytes;
+// a short last block - the TAIL - is decoded into a room, the first source
+// bytes are laid behind it and the room is compressed as the first NEW block;
+// every further new block is compressed straight from the source.
+// ---------------------------------------------------------------------
+// Entries the stream owns in the new index, whatever becomes of it.
+SNAPMI_BI_HD inline uint64_t bi_append_entries(uint64_t dlen, uint64_t add)
+{
+    return bi_entries(dlen + add);
+}
+
+// kf: the old full blocks, which are copied.
+SNAPMI_BI_HD inline uint64_t bi_append_full(uint64_t dlen)
+{
+    return dlen / kBiBlock;
+}
+
+// Bytes of the tail (0: the old length is a multiple of 64 KiB - 0 included -
+// and nothing is decoded).
+SNAPMI_BI_HD inline uint64_t bi_append_tail(uint64_t dlen)
+{
+    return dlen % kBiBlock;
+}
+
+// Source bytes that fill the tail's room.
+SNAPMI_BI_HD inline uint64_t bi_append_fill(uint64_t dlen, uint64_t add)
+{
+    const uint64_t rem = bi_append_tail(dlen);
+    if (rem == 0)
+        return 0;
+    return add < kBiBlock - rem ? add : kBiBlock - rem;
+}
+
+// New blocks of a stream that `add` bytes are appended to (0 for add == 0:
+// nobody names the stream).  dlen + add does not wrap: bi_append_check.
+SNAPMI_BI_HD inline uint64_t bi_append_blocks(uint64_t dlen, uint64_t add)
+{
+    return add ? bi_blocks(dlen + add) - bi_append_full(dlen) : 0;
+}
+
+// New block j (j < bi_append_blocks): source bytes [off, off + len) go into
+// it.  room: it is the tail's block - the bytes are laid at byte in_len - len
+// of the room and the compressor reads room[0, in_len); else the compressor
+// reads them where they are, in_len == len.
+struct BiAppendBlock {
+    bool room;
+    uint64_t off, len, in_len;
+};
+
+SNAPMI_BI_HD inline BiAppendBlock bi_append_block(uint64_t dlen, uint64_t add,
+                                                  uint64_t j)
+{
+    const uint64_t rem = bi_append_tail(dlen);
+    const uint64_t fill = bi_append_fill(dlen, add);
+    BiAppendBlock b;
+    if (rem && j == 0) {
+        b.room = true;
+        b.off = 0;
+        b.len = fill;
+        b.in_len = rem + fill;
+        return b;
+    }
+    b.room = false;
+    b.off = fill + (rem ? j - 1 : j) * kBiBlock;
+    b.len = add - b.off < kBiBlock ? add - b.off : kBiBlock;
+    b.in_len = b.len;
+    return b;
+}
+
+// What is wrong with the host's lists, or 0: h_out_lens[i] + h_app_len[i]
+// wraps (*bad: the stream), or n + index_entries + new entries + new blocks
+// is not below 2^31.  *entries: the new index's total; *blocks: the new
+// blocks of the call (both saturate at 2^64 - 1).
+constexpr int kBiAppendOk = 0, kBiAppendWraps = 1, kBiAppendTooMany = 2;
+
+SNAPMI_BI_HD inline int bi_append_check(const uint64_t *out_lens,
+                                        const uint64_t *app_len, size_t n,
+                                        uint64_t index_entries,
+                                        uint64_t *entries, uint64_t *blocks,
+                                        size_t *bad)
+{
+    uint64_t e = 0, b = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (out_lens[i] + app_len[i] < out_lens[i]) {
+            *bad = i;
+            return kBiAppendWraps;
+        }
+        const uint64_t ce = bi_append_entries(out_lens[i], app_len[i]);
+        const uint64_t cb = bi_append_blocks(out_lens[i], app_len[i]);
+        e = e + ce < e ? ~0ull : e + ce;
+        b = b + cb < b ? ~0ull : b + cb;
+    }
+    *entries = e;
+    *blocks = b;
+    const uint64_t lim = 0x7FFFFFFFull;
+    if ((uint64_t)n > lim || index_entries > lim || e > lim || b > lim ||
+        (uint64_t)n + index_entries + e + b > lim)
+        return kBiAppendTooMany;
+    return kBiAppendOk;
+}
+
+// The index rule of an append: bi_range_stream_usable, and the block's part
+// for every OLD block - the full ones are copied, the tail is decoded.
+SNAPMI_BI_HD inline uint64_t bi_append_first_bad_block(const uint64_t *e,
+                                                       uint64_t in_len,
+                                                       uint64_t blocks)
+{
+    return bi_write_first_bad_block(e, in_len, blocks);
+}
+
+// The splice, by definition: the stream's new entries from its old ones e[]
+// (kf + 1 of them are looked at) and the compressed sizes nsize[nb] of its
+// new blocks (without a varint); hdr_new is the length of varint(dlen + add).
+// e_new has kf + nb + 1 places.  Returns the new length (the last new entry).
+SNAPMI_BI_HD inline uint64_t bi_append_splice(const uint64_t *e, uint64_t kf,
+                                              const uint64_t *nsize,
+                                              uint64_t nb, uint32_t hdr_new,
+                                              uint64_t *e_new)
+{
+    uint64_t pos = hdr_new;
+    for (uint64_t k = 0; k < kf; k++) {
+        e_new[k] = pos;
+        pos += e[k + 1] - e[k];
+    }
+    for (uint64_t j = 0; j < nb; j++) {
+        e_new[kf + j] = pos;
+        pos += nsize[j];
+    }
+    e_new[kf + nb] = pos;
+    return pos;
+}
+
+// ... and as the kernels compute it, an entry at a time: an old entry moves
+// by what the header grew; a new one lies behind the old full blocks by the
+// running sum of the new blocks in front of it.  ncum[j] is the sum of the
+// sizes of the new blocks [0, j), ncum[nb] their total.
+SNAPMI_BI_HD inline uint64_t bi_append_entry(const uint64_t *e, uint64_t k,
+                                             uint64_t kf,
+                                             const uint64_t *ncum,
+                                             uint32_t hdr_old,
+                                             uint32_t hdr_new)
+{
+    if (k <= kf)
+        return e[k] + hdr_new - hdr_old;
+    return e[kf] + hdr_new - hdr_old + ncum[k - kf];
+}
+
+// The last verdict: the new stream fits its buffer (an exact cap passes).
+SNAPMI_BI_HD inline bool bi_append_fits(uint64_t cap, uint64_t new_len)
+{
+    return bi_write_fits(cap, new_len);
 }
 
 // ---------------------------------------------------------------------

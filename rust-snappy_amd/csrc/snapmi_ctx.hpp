@@ -271,6 +271,19 @@ struct snapmi_ctx {
     uint64_t write_scratch_bytes = 1ull << 30;
     uint64_t wr_blocks = 0, wr_decoded = 0;
     bool wr_stats_live = false;
+    // snapmi_append_indexed: the device's copy of the host's append lists,
+    // the named streams' states and the new blocks' sums, the two counters;
+    // the pinned staging of the lists with the event of the copy that last
+    // read it; new blocks and tails of the last call; whether it ran its
+    // kernels.  (Its one-block streams, compress slots, tail rooms and piece
+    // descriptors are the writes': wr_z, wr_slot, wr_room, wr_desc - the calls
+    // follow each other on the stream, and write_scratch_bytes bounds both.)
+    snapmi::DevBuf ap_meta, ap_state, ap_stat;
+    snapmi::PinBuf pin_ap;
+    hipEvent_t ev_ap = nullptr;
+    bool ev_ap_live = false;
+    uint64_t ap_blocks = 0, ap_decoded = 0;
+    bool ap_stats_live = false;
     // test options: "index_build_route" (BuildArgs::route) and the most
     // streams a group of the scan route holds
     uint32_t index_build_route = 0;

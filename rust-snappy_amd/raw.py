@@ -111,8 +111,9 @@ class Context:
         "range_ranges_ok", "range_ranges_failed", "index_build_built",
         "index_build_unaligned", "index_build_corrupt",
         "index_build_missized", "index_build_walked", "write_blocks",
-        "write_blocks_decoded", "write_streams_ok", "write_streams_failed"
-        (include/snapmi.h)."""
+        "write_blocks_decoded", "write_streams_ok", "write_streams_failed",
+        "append_blocks", "append_blocks_decoded", "append_streams_ok",
+        "append_streams_failed" (include/snapmi.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:
@@ -456,6 +457,37 @@ def write_ranges_indexed(ctx, in_ptrs, in_lens, index_first, index,
         _u64_array(write_off), _u64_array(write_len), _u64_array(write_src),
         m, _ptr(out_ptrs), _ptr(out_caps), _ptr(out_lens), _ptr(errs),
         _ptr(new_index))
+    if rc:
+        _raise(ctx, rc)
+
+
+def append_indexed(ctx, in_ptrs, in_lens, host_out_lens, index_first, index,
+                   app_src, app_len, out_ptrs, out_caps, out_lens, errs,
+                   new_index_first, new_index, index_entries=None,
+                   new_index_cap=None):
+    """snapmi_append_indexed: app_src[i][0, app_len[i]) is appended to the
+    output of stream i (app_len[i] == 0: not named); only the stream's short
+    last block and the new bytes are decoded and compressed, the full old
+    blocks are copied.  in_ptrs / in_lens / index_first / index: the streams
+    and their block index (int64 CUDA tensors); host_out_lens: the lengths
+    the headers announce, app_len: sequences of ints; app_src: sequence of
+    device addresses (ints); out_ptrs / out_caps / out_lens: uint64-as-int64
+    CUDA tensors [n]; errs: optional uint8 CUDA tensor of 32*n bytes;
+    new_index_first [n + 1] and new_index (new_index_cap entries, default its
+    size; block_index_entries of the summed lengths are needed): int64 CUDA
+    tensors.  Enqueues on the context's stream."""
+    n = in_ptrs.numel() if in_ptrs is not None else 0
+    assert len(host_out_lens) == n and len(app_src) == n and len(app_len) == n
+    if index_entries is None:
+        index_entries = index.numel() if index is not None else 0
+    if new_index_cap is None:
+        new_index_cap = new_index.numel() if new_index is not None else 0
+    rc = _lib.of(ctx).snapmi_append_indexed(
+        ctx._h, _ptr(in_ptrs), _ptr(in_lens), _u64_array(host_out_lens), n,
+        _ptr(index_first), _ptr(index), int(index_entries),
+        _u64_array(app_src), _u64_array(app_len), _ptr(out_ptrs),
+        _ptr(out_caps), _ptr(out_lens), _ptr(errs), _ptr(new_index_first),
+        _ptr(new_index), int(new_index_cap))
     if rc:
         _raise(ctx, rc)
 

@@ -2143,6 +2143,94 @@ def frames_host_batch(args, ctx, dev):
     return res
 
 
+def crc(args, ctx, dev):
+    """Masked CRC32C on the device (snapmi_crc32c_masked_batch) over random
+    bytes: 16 384 buffers of 64 KiB (one wavefront a buffer: the route of the
+    frame codec's chunks), the same 1 GiB as one buffer and as 16 buffers of
+    64 MiB (cut into segments that the whole device shares), and 512 buffers
+    of 100 B .. 4 MiB mixed.  Five alternating repeats of 20 calls each
+    (medians, and the spread max - min over the repeats); beside each shape
+    the CPU codec's rate on the same bytes.  With SNAPMI_PARENT_LIB=<another
+    build of libsnapmi.so> the first shape - all that an older build can do -
+    is timed through that build as well, in this process, in turn with this
+    one: the yardstick.  Writes profiles/crc_long.json."""
+    import os
+    import random
+    import statistics
+    import oracle_lib as O
+    from rust_snappy_amd import _lib, frame, raw
+    steps, repeats = 20, 5
+    rng = random.Random(0x5EED)
+    torch.manual_seed(0x5EED)
+    gib = torch.randint(0, 256, (1 << 30,), dtype=torch.uint8, device=dev)
+    mixed_lens = [int(100 * (41943.04 ** rng.random())) for _ in range(512)]
+    mixed_offs = np.concatenate([[0], np.cumsum(mixed_lens)]).astype(np.int64)
+    assert int(mixed_offs[-1]) <= gib.numel()
+    base = gib.data_ptr()
+    shapes = {
+        "short_16384x64k": ([base + (i << 16) for i in range(16384)],
+                            [1 << 16] * 16384),
+        "one_1g": ([base], [1 << 30]),
+        "long_16x64m": ([base + (i << 26) for i in range(16)], [1 << 26] * 16),
+        "mixed_512_100b_4m": ([base + int(o) for o in mixed_offs[:-1]],
+                              mixed_lens),
+    }
+    host = gib.cpu().numpy()
+    parent = None
+    if os.environ.get("SNAPMI_PARENT_LIB"):
+        parent = raw.Context(ctx.device, lib=_lib._open(
+            Path(os.environ["SNAPMI_PARENT_LIB"])))
+    res = {"config": "crc: snapmi_crc32c_masked_batch, random bytes",
+           "steps": steps, "repeats": repeats,
+           "segment_bytes": frame.CRC_SEGMENT}
+    try:
+        for key, (ptrs, lens) in shapes.items():
+            n, nbytes = len(lens), sum(lens)
+            d_ptrs = torch.tensor(ptrs, dtype=torch.int64, device=dev)
+            d_lens = torch.tensor(lens, dtype=torch.int64, device=dev)
+            out = torch.zeros(n, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+
+            def run(c):
+                return lambda: frame.crc32c_masked_ptrs(c, d_ptrs, d_lens, out)
+            run(ctx)()
+            ctx.synchronize()
+            got = [int(v) & 0xFFFFFFFF for v in out.cpu().tolist()]
+            # the CPU codec on the same bytes: its rate, and the check (every
+            # buffer of the long shapes, a sample of the others)
+            sample = range(n) if n <= 16 else random.Random(1).sample(
+                range(n), 64)
+            t0, cpu_bytes = time.perf_counter(), 0
+            for i in sample:
+                o = ptrs[i] - base
+                assert got[i] == O.crc32c_masked(host[o:o + lens[i]]), (key, i)
+                cpu_bytes += lens[i]
+            cpu_s = time.perf_counter() - t0
+            timers = {"this": lambda: time_it(run(ctx), steps, ctx)}
+            if parent is not None and key == "short_16384x64k":
+                timers["parent"] = lambda: time_it(run(parent), steps, parent)
+            t = {k: [] for k in timers}
+            for _ in range(repeats):
+                for k, fn in timers.items():
+                    t[k].append(fn() * 1e3)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            res[key] = {
+                "buffers": n, "bytes": nbytes,
+                "ms_median": {k: round(v, 4) for k, v in med.items()},
+                "ms_spread": {k: round(max(v) - min(v), 4)
+                              for k, v in t.items()},
+                "ms_repeats": {k: [round(x, 4) for x in v]
+                               for k, v in t.items()},
+                "gibs": {k: round(nbytes / GIB / (v / 1e3), 1)
+                         for k, v in med.items()},
+                "cpu_codec_gibs": round(cpu_bytes / GIB / cpu_s, 3)}
+    finally:
+        if parent is not None:
+            parent.close()
+    (ROOT / "profiles" / "crc_long.json").write_text(json.dumps(res) + "\n")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=8.0)
@@ -2183,7 +2271,8 @@ def main():
              "frames_batch": frames_batch, "host_batch": host_batch,
              "frames_host_batch": frames_host_batch, "raw_index": raw_index,
              "raw_ranges": raw_ranges, "raw_index_build": raw_index_build,
-             "raw_writes": raw_writes, "raw_appends": raw_appends}
+             "raw_writes": raw_writes, "raw_appends": raw_appends,
+             "crc": crc}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -2209,7 +2298,8 @@ def main():
                      ("raw_ranges", raw_ranges),
                      ("raw_index_build", raw_index_build),
                      ("raw_writes", raw_writes),
-                     ("raw_appends", raw_appends)):
+                     ("raw_appends", raw_appends),
+                     ("crc", crc)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
@@ -2218,7 +2308,8 @@ def main():
                                                          "raw_ranges",
                                                          "raw_index_build",
                                                          "raw_writes",
-                                                         "raw_appends")):
+                                                         "raw_appends",
+                                                         "crc")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

@@ -1247,7 +1247,27 @@ SNAPMI_API int snapmi_frame_index_host(const void *h_in, uint64_t in_len,
                             uint64_t *n_chunks);
 
 /* Masked CRC32C (reference CheckSummer::crc32c_masked, src/crc32.rs:35-38)
- * of n buffers of at most 65536 bytes each. */
+ * of n buffers of any length: d_out[i] is the masked CRC32C of
+ * d_ptrs[i][0, d_lens[i]) for any d_lens[i] below 2^64 that the memory really
+ * holds.  The pointer may have any alignment; length 0 is valid (the pointer
+ * is then not used).
+ *   Buffers of at most 65536 bytes are computed by the kernel of the frame
+ * codec's chunks, one wavefront a buffer.  A longer buffer is cut into
+ * segments of 128 KiB that the whole device shares, one wavefront a segment
+ * at a time: 1 GiB in one buffer runs as wide as 1 GiB in 16 384.
+ *   Host: the call only enqueues on the context's stream.  d_ptrs, d_lens and
+ * d_out are device memory and the host never reads them: no copy to the host,
+ * no wait, no look at the batch.  Every launch and the call's scratch (12
+ * bytes a buffer) are sized from n and the device's CU count alone; the host
+ * waits only when that scratch must grow (and, in a context's first frame or
+ * CRC call, for the CRC tables), before the first launch, as in every call of
+ * this section.
+ *   Graphs: once a call with this n or more has run, the call can be captured
+ * into a hipGraph; a replay over other lengths (and pointers, and bytes) in
+ * the same arrays gives the CRCs of those.  The launches form one serial
+ * chain on the context's stream; there is no side stream.
+ *   No byte outside [d_ptrs[i], d_ptrs[i] + d_lens[i]) is read and nothing
+ * outside d_out[0, n) is written.  n < 2^31; n == 0 enqueues nothing. */
 SNAPMI_API int snapmi_crc32c_masked_batch(snapmi_ctx *ctx, const void *const *d_ptrs,
                                const uint64_t *d_lens, uint32_t *d_out,
                                size_t n);

@@ -294,6 +294,9 @@ struct snapmi_ctx {
     uint32_t stream_scan_segs = 0; // test option: 0 = by size
     // frame layer scratch (snapmi_frame.hip)
     snapmi::DevBuf fr_tables, fr_desc, fr_scan, fr_slots, fr_chunk_off;
+    // snapmi_crc32c_masked_batch: the long buffers' segment scan and
+    // accumulators (sized from n alone)
+    snapmi::DevBuf fr_crc;
     // frame decode: per-stream and per-chunk scratch
     snapmi::DevBuf fb_streams, fb_chunks;
     bool fr_tables_ready = false;

@@ -457,22 +457,62 @@ def index_host(data):
     return offs.astype(np.int64)
 
 
-def crc32c_masked(ctx, data):
-    """CheckSummer::crc32c_masked (reference src/crc32.rs:35-38) of one
-    buffer of at most 65536 bytes, on the device."""
-    data = bytes(data)
-    dev = torch.device("cuda", ctx.device)
-    buf = torch.frombuffer(bytearray(data or b"\0"), dtype=torch.uint8).to(dev)
-    ptrs = torch.tensor([buf.data_ptr()], dtype=torch.int64, device=dev)
-    lens = torch.tensor([len(data)], dtype=torch.int64, device=dev)
-    out = torch.zeros(1, dtype=torch.int32, device=dev)
+# snapmi_crc32c_masked_batch cuts a buffer of more than 65536 bytes into
+# segments of this many bytes (kCrcSegment, csrc/snapmi_crc.hpp); the result
+# does not depend on it
+CRC_SEGMENT = 128 * 1024
+
+
+def crc32c_masked_ptrs(ctx, ptrs, lens, out):
+    """snapmi_crc32c_masked_batch over device tensors: ptrs and lens (int64,
+    n entries each: addresses and byte counts, any length, any alignment) and
+    out (int32, n entries; entry i becomes the masked CRC32C of buffer i).
+    Enqueue-only on the context's stream: the lengths are never read by the
+    host, and the call can be captured into a graph once it has run."""
+    n = ptrs.numel()
+    assert lens.numel() == n and out.numel() >= n
     rc = _lib.of(ctx).snapmi_crc32c_masked_batch(
-        ctx._h, C.c_void_p(ptrs.data_ptr()), C.c_void_p(lens.data_ptr()),
-        C.c_void_p(out.data_ptr()), 1)
+        ctx._h, raw._ptr(ptrs), raw._ptr(lens), raw._ptr(out), n)
     if rc:
         raw._raise(ctx, rc)
+
+
+def crc32c_masked_many(ctx, buffers):
+    """CheckSummer::crc32c_masked (reference src/crc32.rs:35-38) of every
+    buffer of a list, in one device call: uint8 device tensors where they
+    lie, bytes-like objects uploaded first.  Any lengths.  Returns a list of
+    ints."""
+    dev = torch.device("cuda", ctx.device)
+    held = []
+    for b in buffers:
+        if not isinstance(b, torch.Tensor):
+            data = bytes(b)
+            b = torch.frombuffer(bytearray(data or b"\0"),
+                                 dtype=torch.uint8).to(dev)[:len(data)]
+        assert b.dtype == torch.uint8 and b.is_cuda and b.is_contiguous()
+        held.append(b)
+    n = len(held)
+    if n == 0:
+        return []
+    ptrs = torch.tensor([b.data_ptr() for b in held], dtype=torch.int64,
+                        device=dev)
+    lens = torch.tensor([b.numel() for b in held], dtype=torch.int64,
+                        device=dev)
+    out = torch.zeros(n, dtype=torch.int32, device=dev)
+    # (the tensors may still be being written on torch's stream, which need
+    # not be the context's)
+    torch.cuda.current_stream(dev).synchronize()
+    crc32c_masked_ptrs(ctx, ptrs, lens, out)
     ctx.synchronize()
-    return int(out.item()) & 0xFFFFFFFF
+    del held
+    return [int(v) & 0xFFFFFFFF for v in out.cpu().tolist()]
+
+
+def crc32c_masked(ctx, data):
+    """CheckSummer::crc32c_masked (reference src/crc32.rs:35-38) of one
+    buffer of any length (bytes-like, or a uint8 device tensor), on the
+    device."""
+    return crc32c_masked_many(ctx, [data])[0]
 
 
 BATCH_BYTES = 64 << 20  # what the streaming adapters hand the device at once

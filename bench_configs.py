@@ -2231,6 +2231,166 @@ def crc(args, ctx, dev):
     return res
 
 
+def frame_nowait(args, ctx, dev):
+    """snapmi_frame_decompress_ex with SNAPMI_FRAME_NO_WAIT against the call
+    without the flag, on this build and - with SNAPMI_PARENT_LIB=<the parent
+    commit's libsnapmi.so> - on the parent's, in this process, in turn:
+    (a) 4 096 framed streams of 16 KiB of text, decoded by a loop of
+    one-stream calls with one wait at the end; (b) one 1 GiB framed text
+    stream, with its index and without (bound exact); (c) the same without
+    an index under a bound of four times the count, beside the scratch the
+    context then holds.  Five alternating repeats (medians, and the spread
+    max - min over the repeats).  Writes profiles/frame_nowait.json."""
+    import ctypes as C
+    import os
+    import statistics
+    from rust_snappy_amd import _lib, frame, raw
+    repeats = 5
+    V = C.c_void_p
+    parent = None
+    if os.environ.get("SNAPMI_PARENT_LIB"):
+        parent = raw.Context(ctx.device, lib=_lib._open(
+            Path(os.environ["SNAPMI_PARENT_LIB"])))
+    res = {"config": "frame_nowait: SNAPMI_FRAME_NO_WAIT against the "
+                     "unflagged call, synthetic text", "repeats": repeats,
+           "parent": parent is not None}
+
+    def timed(timers):
+        t = {k: [] for k in timers}
+        for _ in range(repeats):
+            for k, fn in timers.items():
+                t[k].append(fn() * 1e3)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        return med, {
+            "ms_median": {k: round(v, 3) for k, v in med.items()},
+            "ms_spread": {k: round(max(v) - min(v), 3) for k, v in t.items()},
+            "ms_repeats": {k: [round(x, 3) for x in v] for k, v in t.items()}}
+
+    def decode(c, d_in, n_in, out, cap, out_len, err, idx, n_chunks, flags):
+        rc = c._L.snapmi_frame_decompress_ex(c._h, d_in, n_in, out, cap,
+                                             out_len, err, idx, n_chunks,
+                                             flags, None)
+        if rc:
+            raw._raise(c, rc)
+
+    try:
+        # (a) many small streams, one call each
+        n, piece = 4096, 16 << 10
+        text = synth_text(dev, n * piece)
+        cap = frame.frame_max_len(piece)
+        mid = torch.zeros(n * cap, dtype=torch.uint8, device=dev)
+        ar = torch.arange(n, dtype=torch.int64, device=dev)
+        in_ptrs = text.data_ptr() + ar * piece
+        in_lens = torch.full((n,), piece, dtype=torch.int64, device=dev)
+        mid_ptrs = mid.data_ptr() + ar * cap
+        mid_lens = torch.zeros(n, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        frame.compress_many_ptrs(ctx, in_ptrs, in_lens, mid_ptrs, None,
+                                 mid_lens, None, host_in_lens=in_lens.cpu())
+        ctx.synchronize()
+        flens = mid_lens.cpu().tolist()
+        index = torch.tensor([[10, f] for f in flens], dtype=torch.int64,
+                             device=dev)
+        out = torch.zeros(n * piece, dtype=torch.uint8, device=dev)
+        out_lens = torch.zeros(n, dtype=torch.int64, device=dev)
+        errs = torch.zeros(n * 32, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        argv = [(V(mid.data_ptr() + i * cap), flens[i],
+                 V(out.data_ptr() + i * piece), piece,
+                 V(out_lens.data_ptr() + 8 * i), V(errs.data_ptr() + 32 * i),
+                 V(index.data_ptr() + 16 * i), 1) for i in range(n)]
+
+        def loop(c, flags):
+            def run():
+                out_lens.zero_()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for a in argv:
+                    decode(c, *a, flags)
+                c.synchronize()
+                return time.perf_counter() - t0
+            run()
+            assert out_lens.cpu().tolist() == [piece] * n
+            assert not errs.any().item() and torch.equal(out, text)
+            return run
+        timers = {"flagged": loop(ctx, 4), "unflagged": loop(ctx, 0)}
+        if parent is not None:
+            timers["parent"] = loop(parent, 0)
+        med, rec = timed(timers)
+        rec.update(streams=n, stream_bytes=piece,
+                   us_per_call={k: round(v * 1e3 / n, 2)
+                                for k, v in med.items()})
+        if parent is not None:
+            rec["flagged_over_parent"] = round(med["flagged"] / med["parent"],
+                                               4)
+        res["a_4096x16k"] = rec
+        del text, mid, out, argv
+        torch.cuda.empty_cache()
+
+        # (b), (c) one long stream
+        nbytes = 1 << 30
+        text = synth_text(dev, nbytes)
+        framed, flen, index = frame.compress_device(ctx, text,
+                                                    want_index=True)
+        chunks = index.numel() - 1
+        out = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        out_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        err = torch.zeros(32, dtype=torch.uint8, device=dev)
+        wide = raw.Context(ctx.device, lib=ctx._L)   # (c): its own scratch
+        torch.cuda.synchronize()
+
+        def one(c, idx, bound, flags):
+            a = (V(framed.data_ptr()), flen, V(out.data_ptr()), nbytes,
+                 V(out_len.data_ptr()), V(err.data_ptr()),
+                 V(index.data_ptr()) if idx else None, bound, flags)
+
+            def run():
+                out_len.zero_()
+                out[:4096].zero_()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(3):
+                    decode(c, *a)
+                c.synchronize()
+                return (time.perf_counter() - t0) / 3
+            run()
+            assert int(out_len.item()) == nbytes and not err.any().item()
+            assert torch.equal(out, text)
+            return run
+        timers = {"flagged_index": one(ctx, True, chunks, 4),
+                  "flagged_bound": one(ctx, False, chunks, 4),
+                  "unflagged_index": one(ctx, True, chunks, 0),
+                  "unflagged_walk": one(ctx, False, 0, 0)}
+        scratch_exact = ctx.info("scratch_bytes")
+        timers["flagged_bound_x4"] = one(wide, False, 4 * chunks, 4)
+        scratch_wide = wide.info("scratch_bytes")
+        tight = raw.Context(ctx.device, lib=ctx._L)
+        one(tight, False, chunks, 4)
+        scratch_tight = tight.info("scratch_bytes")
+        tight.close()
+        if parent is not None:
+            timers["parent_index"] = one(parent, True, chunks, 0)
+            timers["parent_walk"] = one(parent, False, 0, 0)
+        med, rec = timed(timers)
+        rec.update(bytes=nbytes, framed_bytes=flen, chunks=chunks,
+                   gibs={k: round(nbytes / GIB / (v / 1e3), 1)
+                         for k, v in med.items()},
+                   scratch_bytes={"bound_exact": scratch_tight,
+                                  "bound_x4": scratch_wide,
+                                  "bench_context": scratch_exact,
+                                  "per_extra_chunk": round(
+                                      (scratch_wide - scratch_tight)
+                                      / (3 * chunks), 1)})
+        res["b_c_one_1g"] = rec
+        wide.close()
+    finally:
+        if parent is not None:
+            parent.close()
+    (ROOT / "profiles" / "frame_nowait.json").write_text(
+        json.dumps(res) + "\n")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=8.0)
@@ -2272,7 +2432,7 @@ def main():
              "frames_host_batch": frames_host_batch, "raw_index": raw_index,
              "raw_ranges": raw_ranges, "raw_index_build": raw_index_build,
              "raw_writes": raw_writes, "raw_appends": raw_appends,
-             "crc": crc}
+             "crc": crc, "frame_nowait": frame_nowait}
     if args.plan:
         for item in args.plan.split(","):
             name, gib = item.split(":")
@@ -2299,7 +2459,8 @@ def main():
                      ("raw_index_build", raw_index_build),
                      ("raw_writes", raw_writes),
                      ("raw_appends", raw_appends),
-                     ("crc", crc)):
+                     ("crc", crc),
+                     ("frame_nowait", frame_nowait)):
         if args.only != name and (args.only or name in ("cfg4",
                                                          "frames_batch",
                                                          "host_batch",
@@ -2309,7 +2470,8 @@ def main():
                                                          "raw_index_build",
                                                          "raw_writes",
                                                          "raw_appends",
-                                                         "crc")):
+                                                         "crc",
+                                                         "frame_nowait")):
             continue  # cfg4 (the multi-rank config), *_batch: on request
         res = fn(args, ctx, dev)
         if res is not None:

@@ -264,7 +264,9 @@ SNAPMI_API const char *snapmi_version(void);
  *                          cross-check of the test build]
  *   "frame_parallel_walk_min"  framed streams of at least this many bytes
  *                          decoded without a side index get their chunk
- *                          headers found in parallel (default 4 MiB)
+ *                          headers found in parallel (default 4 MiB); the
+ *                          chained fronts of a SNAPMI_FRAME_NO_WAIT decode
+ *                          follow it too
  *   "host_encode_slice"    input bytes per slice of snapmi_frame_encode_host
  *                          (default 2 GiB: the match finder wants few, large
  *                          launches)
@@ -363,6 +365,11 @@ SNAPMI_API int snapmi_ctx_prepare(snapmi_ctx *ctx, uint64_t blocks,
  *                           verdict, and
  *   "index_build_walked"    streams of it the sequential walker handled (all
  *                           five wait for the call)
+ *   "frame_nowait_front"    the front that decided the last
+ *                           SNAPMI_FRAME_NO_WAIT decode: 1 the side index, 2
+ *                           the parallel walk, 3 the sequential walk, 4 the
+ *                           bound was exceeded; -1 before the first (waits
+ *                           for the call)
  * SNAPMI_E_ARGUMENT for a name that is not in this list. */
 SNAPMI_API int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name,
                                    int64_t *value);
@@ -1171,7 +1178,45 @@ SNAPMI_API int snapmi_frame_compress_chunks(snapmi_ctx *ctx, const void *d_in,
  * reader has returned them before it reports the error.  The side index is
  * a hint: if it does not tile [identifier, in_len) with plain data chunks,
  * or a chunk needs the stale-buffer rule, the headers are walked instead.
+ *
+ * Without SNAPMI_FRAME_NO_WAIT the call waits for the context's stream once
+ * or more: the host sizes the chunk table and the launches from a chunk count
+ * that only the device knows.  With it the caller bounds that count and the
+ * call only enqueues:
+ *   n_chunks  a promise: the stream holds at most n_chunks data chunks (types
+ *             0x00 and 0x01) in front of its first structural error - from
+ *             the index snapmi_frame_compress wrote, snapmi_frame_index_host,
+ *             snapmi_frame_scan_host, or ceil(decoded length / 65536).  At
+ *             most 2^31 - 1 (else SNAPMI_E_ARGUMENT, nothing is enqueued).
+ *   d_chunk_offsets  may be NULL (n_chunks is then only the bound); if given
+ *             it has n_chunks + 1 entries and is the hint it always is,
+ *             checked and never trusted.  No entry behind n_chunks is read.
+ * While the promise holds, d_out_len[0], d_err[0] and the bytes d_out[0,
+ * d_out_len[0]) are those of the same call without the flag - whatever the
+ * index contains and however generous the bound: the bytes in front of a
+ * failing chunk, BufferTooSmall {cap, total}, SNAPMI_FRAME_CONTINUATION,
+ * stale10 and d_out == NULL (lengths only) included.  When it is broken -
+ * more data chunks than n_chunks - d_err[0] = {SNAPMI_E_ARGUMENT, a = the
+ * data chunks counted, b = n_chunks}, d_out_len[0] = 0 and d_out[0, out_cap)
+ * is unspecified; this verdict wins over every other.  Nothing outside
+ * d_out[0, out_cap), d_out_len[0] and d_err[0] is written and no input byte
+ * at or behind in_len is read, either way.
+ * The fronts that find the chunks are enqueued back to back and the order on
+ * the stream alone lets the first that decides win: the side index if one is
+ * given, else the parallel walk for in_len >= "frame_parallel_walk_min",
+ * then the sequential walk (behind an index that fails its check it is the
+ * sequential walk alone that decides, whatever in_len).  Info
+ * "frame_nowait_front" tells which it was.  The host waits only for scratch
+ * that must grow and, in a context's first frame call, for the CRC tables; a
+ * call that has run once eagerly can be captured into a hipGraph, and a
+ * replay decodes whatever bytes and index values then lie in the same buffers
+ * at that in_len.  A generous bound costs scratch and empty threads: 153
+ * bytes of chunk table and 4 of the raw decoder's plan per chunk of the bound,
+ * used or not - 177 measured, with the eighth the grow-only buffers add (a
+ * 1 GiB stream of 16 384 chunks under a bound of 65 536: 11.9 MB of scratch
+ * instead of 3.2 MB, and 3.96 ms instead of 3.86 ms).
  */
+#define SNAPMI_FRAME_NO_WAIT 4u   /* decode: n_chunks bounds the data chunks; the call only enqueues */
 SNAPMI_API int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
                                uint64_t in_len, void *d_out, uint64_t out_cap,
                                uint64_t *d_out_len, snapmi_error *d_err,

@@ -754,6 +754,16 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
         const char c = name[12];
         *value = (int64_t)w[c == 'b' ? 0 : c == 'u' ? 1 : c == 'c' ? 2
                             : c == 'm' ? 3 : 4];
+    } else if (strcmp(name, "frame_nowait_front") == 0) {
+        // of the last SNAPMI_FRAME_NO_WAIT decode: wait for it
+        uint32_t w = 0;
+        if (ctx->fr_nowait_live) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(&w, ctx->fr_nowait.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        *value = ctx->fr_nowait_live ? (int64_t)w : -1;
     } else if (strcmp(name, "host_batch_slices") == 0) {
         *value = (int64_t)ctx->hb_slices;
     } else if (strcmp(name, "host_batch_h2d_bytes") == 0) {

@@ -299,6 +299,10 @@ struct snapmi_ctx {
     snapmi::DevBuf fr_crc;
     // frame decode: per-stream and per-chunk scratch
     snapmi::DevBuf fb_streams, fb_chunks;
+    // the front that decided the last no-wait decode (info
+    // "frame_nowait_front"); whether there has been one
+    snapmi::DevBuf fr_nowait;
+    bool fr_nowait_live = false;
     bool fr_tables_ready = false;
     // framed streams of at least this many bytes without a side index get
     // their chunk headers found in parallel (k_fw_*); shorter ones are walked

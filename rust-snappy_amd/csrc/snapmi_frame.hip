@@ -257,7 +257,11 @@ struct FrameDecodeArgs {
     uint8_t stale[10];
     uint32_t *meta; // for the host: [0] data chunks found, [1] overflow flag,
                     // [2] 1: the side index met a chunk only a walk can
-                    // judge, 2: so did the parallel walk
+                    // judge, 2: so did the parallel walk; a no-wait decode's
+                    // own: [3] kFrontWalk when its sequential walk ran
+    // 1: the sequential walk of a no-wait decode, enqueued behind another
+    // front (snapmi_framewalk.hpp); 0 in every other launch
+    uint32_t chained;
     // the batch of one
     FrameChunk *chunks;
     uint32_t *c_stream; // [cap_chunks], all 0
@@ -462,6 +466,12 @@ __global__ void k_frame_walk(FrameDecodeArgs a)
 {
     if (blockIdx.x || threadIdx.x)
         return;
+    if (a.chained) { // the front before this launch may have decided
+        const bool decided = frame_front_decided(a.meta[2]);
+        a.meta[3] = decided ? 0 : kFrontWalk;
+        if (decided)
+            return;
+    }
     a.meta[1] = 0;
     a.meta[2] = 0;
     uint32_t nd;
@@ -486,57 +496,47 @@ __global__ void k_frame_index(FrameDecodeArgs a)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     gcptr in = (gcptr)a.in;
     // (k_frame_meta_init runs before this launch)
-    if (i == 0 && !(a.flags & SNAPMI_FRAME_CONTINUATION)) {
-        const uint8_t ident[10] = {0xFF, 0x06, 0x00, 0x00, 's',
-                                   'N',  'a',  'P',  'p',  'Y'};
-        bool ok = a.in_len >= 10;
-        for (int k = 0; ok && k < 10; k++)
-            ok = in[k] == ident[k];
-        if (!ok)
-            a.meta[2] = 1; // the walk reports what is wrong with the start
-    }
-    // an index without entries tiles nothing: only a stream that ends right
-    // behind its identifier (or an empty continuation) has no chunks
-    if (i == 0 && a.n_index == 0 &&
-        a.in_len != ((a.flags & SNAPMI_FRAME_CONTINUATION) ? 0u : 10u))
+    // (the rules: snapmi_framewalk.hpp; whatever fails them sends the whole
+    // stream to the walk, which owns every error report)
+    if (i == 0 && !frame_index_start(in, a.in_len, a.flags, a.n_index))
         a.meta[2] = 1;
     if (i >= a.n_index)
         return;
-    const uint64_t r = a.index[i];
     FrameChunk c;
-    c.type = 0xFF;
-    c.payload_len = 0;
-    c.crc = 0;
-    c.payload_off = 0;
-    c.pad = 0;
-    // The index is the caller's: it is taken as a hint, never trusted.  A
-    // header that is not an in-bounds data chunk ending exactly at the next
-    // index entry (the entries must tile the stream from the identifier to
-    // its end: other chunk types in between are the walk's business), or a
-    // chunk only the walk can judge (frame_short_varint), sends the whole
-    // stream to the walk, which owns every error report.
-    bool good = a.in_len >= 8 && r <= a.in_len - 8;
-    if (good) {
-        const uint32_t hd = ld32u(in + r);
-        const uint32_t ty = hd & 0xFF, len = hd >> 8;
-        good = ty <= 1 && len >= 4 && len <= kMaxChunk &&
-               len <= a.in_len - r - 4 && !(ty == 1 && len - 4 > kMaxBlock) &&
-               a.index[i + 1] == r + 4 + len && // nothing unseen in between
-               (i + 1 < a.n_index || a.index[i + 1] == a.in_len) &&
-               (i > 0 ||
-                r == ((a.flags & SNAPMI_FRAME_CONTINUATION) ? 0u : 10u)) &&
-               !(ty == 0 && short_varint(in + r + 8, len - 4));
-        if (good) {
-            c.type = ty;
-            c.payload_len = len - 4;
-            c.crc = ld32u(in + r + 4);
-            c.payload_off = r + 8;
-        }
-    }
-    if (!good)
+    if (!frame_index_entry(in, a.in_len, a.flags, a.index, a.n_index, i, c))
         a.meta[2] = 1;
     a.chunks[i] = c;
     a.c_stream[i] = 0;
+}
+
+// Behind the fronts of a no-wait decode (rules: snapmi_framewalk.hpp).  The
+// host has sized the chunk table and every launch behind this one for
+// cap_chunks records; the deciding front left meta[0] of them.  A broken
+// promise becomes the stream's one verdict, over a stream of no chunks; what
+// is left of the table is filled with records that decode to nothing (and
+// that k_fbd_verify_chunks passes over).  One thread per record; thread 0
+// also notes the front for info "frame_nowait_front".
+__global__ __launch_bounds__(256) void k_frame_nowait_seal(
+    FrameDecodeArgs a, uint32_t first_front, uint32_t *front_out)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    // (thread 0 writes neither word: every block reads the same two)
+    const FrameNowait x = frame_nowait_rule(
+        first_front, a.chained && a.meta[3] == kFrontWalk, a.meta[0],
+        a.cap_chunks);
+    if (t >= x.pad_lo && t < a.cap_chunks) {
+        a.chunks[t] = frame_no_chunk();
+        a.c_stream[t] = 0;
+    }
+    if (t != 0)
+        return;
+    front_out[0] = x.front;
+    if (x.exceeded) {
+        a.counts[0] = 0;
+        a.first[1] = 0;
+        a.serr[0] = frame_nowait_exceeded(a.meta[0], a.cap_chunks);
+        a.sidx[0] = 0;
+    }
 }
 
 // Final verdict of one framed stream of n data chunks: its first error in
@@ -1014,6 +1014,11 @@ __global__ void k_fbd_verify_chunks(FrameBatchDecodeArgs a)
     if (c >= a.total)
         return;
     const uint32_t s = a.c_stream[c];
+    // A record behind its stream's chunks is no chunk of it: the padding of
+    // a no-wait decode (k_frame_nowait_seal), whose error kind is not OK,
+    // must not become the stream's first bad chunk.
+    if (c - a.first[s] >= a.first[s + 1] - a.first[s])
+        return;
     bool bad = a.cerrs[c].kind != SNAPMI_OK;
     if (!bad && a.out_ptrs && fbd_fits(a, s))
         bad = frame_chunk_decode_err(a.derrs[c], a.chunks[c].crc, a.crcs[c],
@@ -1693,13 +1698,21 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
 {
     const char *what = "frame";
     if (!ctx || !d_out_len || !d_err || (in_len && !d_in) ||
-        (flags & ~(uint32_t)SNAPMI_FRAME_CONTINUATION))
+        (flags &
+         ~(uint32_t)(SNAPMI_FRAME_CONTINUATION | SNAPMI_FRAME_NO_WAIT)))
         return SNAPMI_E_ARGUMENT;
+    const bool nowait = (flags & SNAPMI_FRAME_NO_WAIT) != 0;
+    if (nowait && n_chunks > 0x7FFFFFFFu)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT,
+                        "frame: a bound of %llu chunks (at most 2^31 - 1)",
+                        (unsigned long long)n_chunks);
+    flags &= SNAPMI_FRAME_CONTINUATION; // what the kernels know
     // capacity for the chunk table: exact with an index, else an estimate
-    // that is retried once with the exact count
+    // that is retried once with the exact count (no-wait: the caller's bound)
     bool use_index = d_chunk_offsets != nullptr;
     // long streams without an index: find the headers in parallel (k_fw_*)
-    bool parallel_walk = in_len >= ctx->frame_parallel_walk_min;
+    bool parallel_walk =
+        in_len >= ctx->frame_parallel_walk_min && !(nowait && use_index);
     uint64_t cap = use_index ? n_chunks : in_len / 2048 + 64;
     const uint64_t fw_seg = ctx->frame_walk_segment;
     const uint64_t nseg64 = (in_len + fw_seg - 1) / fw_seg;
@@ -1719,10 +1732,11 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
     a.out = (uint8_t *)d_out;
     a.out_cap = out_cap;
     a.flags = flags;
+    a.chained = 0;
     for (int k = 0; k < 10; k++)
         a.stale[k] = stale10 ? stale10[k] : 0;
     int rc = fbd_streams(ctx, b, 1, front_bytes, &p);
-    if (rc || (rc = mailbox(ctx)))
+    if (rc || (!nowait && (rc = mailbox(ctx))))
         return rc;
     hipStream_t s = ctx->stream;
     a.in_ptrs = carve<const void *>(p, 1);
@@ -1747,6 +1761,47 @@ int snapmi_frame_decompress_ex(snapmi_ctx *ctx, const void *d_in,
     b.out_caps = a.out_caps;
     b.out_lens = d_out_len;
     b.errs = d_err;
+    if (nowait) {
+        // Nothing comes back to the host: the table, the fronts and every
+        // launch behind them are sized from in_len and the caller's bound,
+        // the fronts are enqueued back to back and the order on the stream
+        // lets the first that decides win (snapmi_framewalk.hpp).  Scratch
+        // that must grow is the only wait, here and in fbd_finish.
+        if ((rc = reserve(ctx, ctx->fr_nowait, sizeof(uint32_t))) ||
+            (rc = fbd_table(ctx, what, b, n_chunks)))
+            return rc;
+        a.chunks = b.chunks;
+        a.c_stream = b.c_stream;
+        a.index = d_chunk_offsets;
+        a.n_index = use_index ? (uint32_t)n_chunks : 0;
+        a.cap_chunks = (uint32_t)n_chunks;
+        const uint32_t tb = 256;
+        const uint32_t gb =
+            n_chunks ? (uint32_t)((n_chunks + tb - 1) / tb) : 1;
+        uint32_t first_front = kFrontWalk;
+        if (use_index) {
+            first_front = kFrontIndex;
+            hipLaunchKernelGGL(k_frame_meta_init, dim3(1), dim3(1), 0, s, a);
+            hipLaunchKernelGGL(k_frame_index, dim3(gb), dim3(tb), 0, s, a);
+        } else if (parallel_walk) {
+            first_front = kFrontParallel;
+            HIP_TRY(ctx, hipMemsetAsync(a.fw_ncand, 0, a.nseg * 4, s));
+            hipLaunchKernelGGL(k_fw_candidates,
+                               dim3((kFwScan + 255) / 256, a.nseg), dim3(256),
+                               0, s, a);
+            hipLaunchKernelGGL(k_fw_resolve, dim3(1), dim3(1), 0, s, a);
+            hipLaunchKernelGGL(k_fw_emit, dim3((a.nseg + 63) / 64), dim3(64),
+                               0, s, a);
+        }
+        a.chained = first_front != kFrontWalk;
+        hipLaunchKernelGGL(k_frame_walk, dim3(1), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_frame_nowait_seal, dim3(gb), dim3(tb), 0, s, a,
+                           first_front, (uint32_t *)ctx->fr_nowait.p);
+        HIP_TRY(ctx, hipGetLastError());
+        ctx->fr_nowait_live = true;
+        b.total = (uint32_t)n_chunks;
+        return fbd_finish(ctx, b);
+    }
     for (int attempt = 0; attempt < 4; attempt++) {
         if (cap > 0x7FFFFFFFu)
             return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "frame: too many chunks");

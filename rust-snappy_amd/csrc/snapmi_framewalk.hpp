@@ -9,6 +9,9 @@
 //   frame_walk       hop by hop to the first header the reader rejects
 //   frame_chunk_len  the length a data chunk announces
 //   frame_index_walk the regular cases only (snapmi_frame_index_host)
+//   frame_index_*    the check of a lone stream's side index, entry by entry
+//   frame_nowait_*   the rules of the no-wait decode: which front decides,
+//                    when the caller's bound is exceeded, what pads the table
 //   frame_walk_host  what the host learns of a stream while it stages it: the
 //                    walk's verdict, a list entry per data chunk and the
 //                    room - an upper bound on what the device may write
@@ -349,6 +352,143 @@ inline int frame_index_walk(const uint8_t *in, uint64_t in_len,
     }
     *n_chunks = nd;
     return 0;
+}
+
+// ---------------------------------------------------------------------
+// The side index of a lone stream (snapmi_frame_decompress[_ex]).  The index
+// is the caller's: it is taken as a hint, never trusted.  A header that is not
+// an in-bounds data chunk ending exactly at the next index entry (the entries
+// must tile the stream from the identifier to its end: other chunk types in
+// between are the walk's business), or a chunk only the walk can judge
+// (frame_short_varint), sends the whole stream to the walk, which owns every
+// error report.
+// ---------------------------------------------------------------------
+
+// a record that decodes to nothing: what stands in the chunk table for an
+// index entry that failed its check and, in a no-wait decode, behind the
+// stream's last chunk (frame_chunk_len answers type 0xFF with length 0 and
+// reads no payload byte)
+SNAPMI_FW_HD inline FrameChunk frame_no_chunk()
+{
+    FrameChunk c;
+    c.payload_off = 0;
+    c.payload_len = 0;
+    c.crc = 0;
+    c.type = 0xFF;
+    c.pad = 0;
+    return c;
+}
+
+// What the index as a whole must get right, besides its entries: the stream
+// begins with the identifier (unless it was seen before), and an index
+// without entries tiles nothing - only a stream that ends right behind its
+// identifier (or an empty continuation) has no chunks.
+template <class P>
+SNAPMI_FW_HD inline bool frame_index_start(P in, uint64_t in_len,
+                                           uint32_t flags, uint32_t n_index)
+{
+    const bool cont = (flags & SNAPMI_FRAME_CONTINUATION) != 0;
+    if (!cont) {
+        const uint8_t ident[10] = {0xFF, 0x06, 0x00, 0x00, 's',
+                                   'N',  'a',  'P',  'p',  'Y'};
+        bool ok = in_len >= 10;
+        for (int k = 0; ok && k < 10; k++)
+            ok = in[k] == ident[k];
+        if (!ok)
+            return false; // the walk reports what is wrong with the start
+    }
+    return n_index != 0 || in_len == (cont ? 0u : 10u);
+}
+
+// Entry i < n_index (index has n_index + 1 entries; none behind index[i + 1]
+// is read): true and the chunk c when it passes, false and a record that
+// decodes to nothing when not.
+template <class P>
+SNAPMI_FW_HD inline bool frame_index_entry(P in, uint64_t in_len,
+                                           uint32_t flags,
+                                           const uint64_t *index,
+                                           uint32_t n_index, uint32_t i,
+                                           FrameChunk &c)
+{
+    const uint64_t r = index[i];
+    c = frame_no_chunk();
+    if (!(in_len >= 8 && r <= in_len - 8))
+        return false;
+    const uint32_t hd = fw_ld32(in + r);
+    const uint32_t ty = hd & 0xFF, len = hd >> 8;
+    const bool good =
+        ty <= 1 && len >= 4 && len <= kMaxChunk && len <= in_len - r - 4 &&
+        !(ty == 1 && len - 4 > kFwMaxBlock) &&
+        index[i + 1] == r + 4 + len && // nothing unseen in between
+        (i + 1 < n_index || index[i + 1] == in_len) &&
+        (i > 0 || r == ((flags & SNAPMI_FRAME_CONTINUATION) ? 0u : 10u)) &&
+        !(ty == 0 && short_varint(in + r + 8, len - 4));
+    if (good) {
+        c.type = ty;
+        c.payload_len = len - 4;
+        c.crc = fw_ld32(in + r + 4);
+        c.payload_off = r + 8;
+    }
+    return good;
+}
+
+// ---------------------------------------------------------------------
+// The no-wait decode (SNAPMI_FRAME_NO_WAIT): the caller bounds the data
+// chunks by n_chunks, the host sizes the chunk table and every launch from
+// that bound and enqueues the fronts back to back - the side index if one
+// was given, else the parallel walk if the stream is long enough, then the
+// sequential walk.  A front decides when it ends without handing the stream
+// on (meta[2] == 0); a front behind one that has decided leaves at once.  The
+// order on the stream is the only synchronisation.
+// ---------------------------------------------------------------------
+enum FrameFront : uint32_t {
+    kFrontIndex = 1,    // the side index
+    kFrontParallel = 2, // the parallel walk
+    kFrontWalk = 3,     // the sequential walk
+    kFrontExceeded = 4, // the deciding front counted more than n_chunks
+};
+
+// `handed_on`: meta[2] as a front left it (0, or who must judge instead)
+SNAPMI_FW_HD inline bool frame_front_decided(uint32_t handed_on)
+{
+    return handed_on == 0;
+}
+
+// What a no-wait decode's fronts came to.  first_front: the front the host
+// enqueued first (kFrontWalk when the walk was the only one); walk_ran: the
+// sequential walk did not find the stream decided; found: data chunks the
+// deciding front counted in front of the stream's first structural error;
+// cap: n_chunks.
+struct FrameNowait {
+    uint32_t front;  // FrameFront, for info "frame_nowait_front"
+    bool exceeded;   // the promise is broken: {SNAPMI_E_ARGUMENT, found, cap}
+                     // wins over every other verdict, nothing is decoded
+    uint32_t chunks; // records [0, chunks) of the table are the stream's
+    uint32_t pad_lo; // records [pad_lo, cap) become frame_no_chunk()
+};
+
+SNAPMI_FW_HD inline FrameNowait frame_nowait_rule(uint32_t first_front,
+                                                  bool walk_ran,
+                                                  uint32_t found, uint32_t cap)
+{
+    FrameNowait x;
+    x.exceeded = found > cap;
+    x.front = x.exceeded                               ? kFrontExceeded
+              : first_front == kFrontWalk || walk_ran ? kFrontWalk
+                                                       : first_front;
+    // (a front that counted too many has left records undefined - the
+    // parallel walk emits none, the sequential walk those below cap: none
+    // may reach the kernels behind)
+    x.chunks = x.exceeded ? 0 : found;
+    x.pad_lo = x.chunks;
+    return x;
+}
+
+// the verdict of a broken promise
+SNAPMI_FW_HD inline snapmi_error frame_nowait_exceeded(uint32_t found,
+                                                       uint32_t cap)
+{
+    return frame_err(SNAPMI_E_ARGUMENT, found, cap);
 }
 
 // What the host learns of one fresh stream before the device sees it.

@@ -170,6 +170,34 @@ def decompress_batch_device(ctx, d_in, n_in, n_chunks, index=None,
     return good, (Error(*e) if e[0] else None)
 
 
+NO_WAIT = 4  # SNAPMI_FRAME_NO_WAIT
+
+
+def decompress_nowait(ctx, d_in, n_in, out, out_cap, out_len, err,
+                      max_chunks, index=None, continuation=False, stale=None):
+    """snapmi_frame_decompress_ex with SNAPMI_FRAME_NO_WAIT: enqueues the
+    decode of d_in[:n_in] on the context's stream and returns - nothing is
+    synchronised, the results are valid once the stream has got there.
+    `max_chunks` bounds the stream's data chunks (the promise of
+    include/snapmi.h); `index` (int64 device tensor of max_chunks + 1 chunk
+    header offsets) is optional.  out: uint8 device tensor of at least out_cap
+    bytes, or None (lengths only); out_len: int64[1] and err: uint8[32] device
+    tensors the call writes.  ctx.info("frame_nowait_front") tells which front
+    found the chunks (it waits)."""
+    if index is not None:
+        assert index.numel() >= int(max_chunks) + 1
+    st = (C.c_uint8 * 10)(*stale) if stale is not None else None
+    rc = _lib.of(ctx).snapmi_frame_decompress_ex(
+        ctx._h, C.c_void_p(d_in.data_ptr()) if n_in else None, int(n_in),
+        C.c_void_p(out.data_ptr()) if out is not None else None,
+        int(out_cap), C.c_void_p(out_len.data_ptr()),
+        C.c_void_p(err.data_ptr()),
+        C.c_void_p(index.data_ptr()) if index is not None else None,
+        int(max_chunks), NO_WAIT | (1 if continuation else 0), st)
+    if rc:
+        raw._raise(ctx, rc)
+
+
 def compress_many_ptrs(ctx, in_ptrs, in_lens, out_ptrs, out_caps, out_lens,
                        errs=None, host_in_lens=None):
     """snapmi_frame_compress_batch: n independent framed streams, arguments as

@@ -30,6 +30,9 @@ pub struct SnapmiCtx {
 pub const SNAPMI_FRAME_NO_IDENT: u32 = 1;
 pub const SNAPMI_FRAME_CONTINUATION: u32 = 1;
 pub const SNAPMI_FRAME_FINAL: u32 = 2;
+/// `snapmi_frame_decompress_ex`: `n_chunks` bounds the data chunks and the
+/// call only enqueues (include/snapmi.h)
+pub const SNAPMI_FRAME_NO_WAIT: u32 = 4;
 pub const SNAPMI_E_UNEXPECTED_EOF: i32 = 64;
 pub const SNAPMI_E_DEVICE: i32 = 100;
 /// `snapmi_ctx_prepare`: place the tables at the far end of the device's

@@ -2,7 +2,8 @@
 // context (create, destroy, options, info, errors) and the scalar calls.  The
 // launchers are in snapmi_launch.hip, the lane tables in
 // snapmi_lanetables.hip, long streams in snapmi_longstream.hip, the block
-// index in snapmi_index.hip, the libsnappy seam in snapmi_seam.hip.
+// index in snapmi_index.hip, writes and appends through it in
+// snapmi_update.hip, the libsnappy seam in snapmi_seam.hip.
 //
 // Nothing here computes Snappy on the CPU: the only host-side arithmetic is
 // the header varint parse (decompress_len) and max_compress_len, which the
@@ -255,7 +256,7 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
         if (b->p)
             (void)hipFree(b->p);
     for (hipEvent_t ev :
-         {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1], ctx->ev_wr, ctx->ev_ap})
+         {ctx->ev_ib, ctx->ev_ibg[0], ctx->ev_ibg[1], ctx->wr.ev, ctx->ap.ev})
         if (ev)
             (void)hipEventDestroy(ev);
     for (auto &ev : ctx->ev)
@@ -645,10 +646,26 @@ int snapmi_decompress_len(const uint8_t *input, size_t input_len,
     return SNAPMI_OK;
 }
 
+// The k counters the kernels of a call keep in `stat`: waits for the call and
+// fetches them; all 0 when the last call ran none of its kernels.
+static int fetch_counters(snapmi_ctx *ctx, bool live, const DevBuf &stat,
+                          unsigned long long *w, size_t k)
+{
+    memset(w, 0, k * sizeof *w);
+    if (live && stat.p) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(w, stat.p, k * sizeof *w,
+                               hipMemcpyDeviceToHost));
+    }
+    return SNAPMI_OK;
+}
+
 int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value)
         return SNAPMI_E_ARGUMENT;
+    int rc;
     if (strcmp(name, "scratch_bytes") == 0) {
         uint64_t sum = ctx->lane_tables.cap;
         for (const DevBuf *b : ctx->dev_bufs)
@@ -699,43 +716,31 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
     } else if (strcmp(name, "range_ranges_ok") == 0 ||
                strcmp(name, "range_ranges_failed") == 0) {
         // of the last snapmi_decompress_ranges_indexed: wait for it
-        unsigned long long w[2] = {0, 0};
-        if (ctx->rg_stats_live && ctx->rg_stat.p) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(w, ctx->rg_stat.p, sizeof w,
-                                   hipMemcpyDeviceToHost));
-        }
+        unsigned long long w[2];
+        if ((rc = fetch_counters(ctx, ctx->rg_stats_live, ctx->rg_stat, w, 2)))
+            return rc;
         *value = (int64_t)(name[13] == 'o' ? w[0] : w[1]);
     } else if (strcmp(name, "write_blocks") == 0) {
-        *value = (int64_t)ctx->wr_blocks;
+        *value = (int64_t)ctx->wr.blocks;
     } else if (strcmp(name, "write_blocks_decoded") == 0) {
-        *value = (int64_t)ctx->wr_decoded;
+        *value = (int64_t)ctx->wr.decoded;
     } else if (strcmp(name, "write_streams_ok") == 0 ||
                strcmp(name, "write_streams_failed") == 0) {
         // of the last snapmi_write_ranges_indexed: wait for it
-        unsigned long long w[2] = {0, 0};
-        if (ctx->wr_stats_live && ctx->wr_stat.p) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(w, ctx->wr_stat.p, sizeof w,
-                                   hipMemcpyDeviceToHost));
-        }
+        unsigned long long w[2];
+        if ((rc = fetch_counters(ctx, ctx->wr.stats_live, ctx->wr.stat, w, 2)))
+            return rc;
         *value = (int64_t)(name[14] == 'o' ? w[0] : w[1]);
     } else if (strcmp(name, "append_blocks") == 0) {
-        *value = (int64_t)ctx->ap_blocks;
+        *value = (int64_t)ctx->ap.blocks;
     } else if (strcmp(name, "append_blocks_decoded") == 0) {
-        *value = (int64_t)ctx->ap_decoded;
+        *value = (int64_t)ctx->ap.decoded;
     } else if (strcmp(name, "append_streams_ok") == 0 ||
                strcmp(name, "append_streams_failed") == 0) {
         // of the last snapmi_append_indexed: wait for it
-        unsigned long long w[2] = {0, 0};
-        if (ctx->ap_stats_live && ctx->ap_stat.p) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(w, ctx->ap_stat.p, sizeof w,
-                                   hipMemcpyDeviceToHost));
-        }
+        unsigned long long w[2];
+        if ((rc = fetch_counters(ctx, ctx->ap.stats_live, ctx->ap.stat, w, 2)))
+            return rc;
         *value = (int64_t)(name[15] == 'o' ? w[0] : w[1]);
     } else if (strncmp(name, "index_build_", 12) == 0 &&
                (strcmp(name + 12, "built") == 0 ||
@@ -744,13 +749,9 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                 strcmp(name + 12, "missized") == 0 ||
                 strcmp(name + 12, "walked") == 0)) {
         // of the last snapmi_build_block_index: wait for it
-        unsigned long long w[5] = {0, 0, 0, 0, 0};
-        if (ctx->ib_stats_live && ctx->ib_stat.p) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(w, ctx->ib_stat.p, sizeof w,
-                                   hipMemcpyDeviceToHost));
-        }
+        unsigned long long w[5];
+        if ((rc = fetch_counters(ctx, ctx->ib_stats_live, ctx->ib_stat, w, 5)))
+            return rc;
         const char c = name[12];
         *value = (int64_t)w[c == 'b' ? 0 : c == 'u' ? 1 : c == 'c' ? 2
                             : c == 'm' ? 3 : 4];

@@ -11,6 +11,7 @@
 //   bi_range_*        the rules of a range read (snapmi_decompress_ranges_indexed)
 //   bi_write_*        the rules of a range write (snapmi_write_ranges_indexed)
 //   bi_append_*       the rules of an append (snapmi_append_indexed)
+//   bi_update_groups  how both cut their named streams into groups
 //   bi_build          the index of a stream that came without one: the
 //                     sequential definition of snapmi_build_block_index
 //
@@ -556,6 +557,63 @@ SNAPMI_BI_HD inline uint64_t bi_append_entry(const uint64_t *e, uint64_t k,
 SNAPMI_BI_HD inline bool bi_append_fits(uint64_t cap, uint64_t new_len)
 {
     return bi_write_fits(cap, new_len);
+}
+
+// ---------------------------------------------------------------------
+// The groups of an update (a range write or an append): the named streams -
+// those a write touches, those bytes are appended to - are cut, in order, into
+// groups of whole streams whose compress slots (kBiSlot bytes for every block
+// that goes through the compressor) and rooms (64 KiB for every block that is
+// decoded first) fit `scratch_bytes`; a stream that needs more than that is a
+// group of its own.  The groups follow each other on the stream and reuse the
+// scratch, so the rooms of a group are numbered from 0.
+// ---------------------------------------------------------------------
+// max_compress_len(64 KiB), rounded up to 16 (kSlotBytes of the device code)
+constexpr uint64_t kBiSlot = 76496;
+
+// named streams [t0, t0 + tg), their blocks [b0, b0 + bg), and their rooms
+struct BiUpdateGroup {
+    uint32_t t0, tg, b0, bg, rooms;
+};
+
+// the most streams, blocks and rooms any group holds
+struct BiUpdateMax {
+    uint64_t tg, bg, rooms;
+};
+
+// b0[ts + 1]: the first block of every named stream (b0[ts]: all blocks);
+// rooms[ts]: the rooms of each.  groups[] has ts places; room0[t] becomes the
+// first room of stream t inside its group - its rooms take the numbers from
+// there, ascending in block order.  Returns the number of groups (0 for
+// ts == 0).
+SNAPMI_BI_HD inline size_t bi_update_groups(const uint32_t *b0,
+                                            const uint32_t *rooms, size_t ts,
+                                            uint64_t scratch_bytes,
+                                            BiUpdateGroup *groups,
+                                            uint32_t *room0, BiUpdateMax *max)
+{
+    max->tg = max->bg = max->rooms = 0;
+    size_t count = 0;
+    uint64_t bytes = 0;
+    for (size_t t = 0; t < ts; t++) {
+        const uint32_t nt = b0[t + 1] - b0[t];
+        const uint64_t need =
+            (uint64_t)nt * kBiSlot + (uint64_t)rooms[t] * kBiBlock;
+        if (count == 0 || bytes + need > scratch_bytes) {
+            groups[count++] = BiUpdateGroup{(uint32_t)t, 0, b0[t], 0, 0};
+            bytes = 0;
+        }
+        BiUpdateGroup &g = groups[count - 1];
+        room0[t] = g.rooms;
+        g.tg++;
+        g.bg += nt;
+        g.rooms += rooms[t];
+        bytes += need;
+        max->tg = g.tg > max->tg ? g.tg : max->tg;
+        max->bg = g.bg > max->bg ? g.bg : max->bg;
+        max->rooms = g.rooms > max->rooms ? g.rooms : max->rooms;
+    }
+    return count;
 }
 
 // ---------------------------------------------------------------------

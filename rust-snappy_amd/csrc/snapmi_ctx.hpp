@@ -25,6 +25,23 @@ struct PinBuf { // pinned, device-mapped host memory (grow-only)
     bool listed = false; // in snapmi_ctx::pin_bufs (pin_reserve)
 };
 
+// What a range write, or an append, of indexed streams keeps between calls
+// (snapmi_update.hip): the device's copy of the host's lists, the named
+// streams' states and the blocks' running sums, the two counters of its
+// kernels; the pinned staging of the lists with the event of the copy that
+// last read it - the next call waits for that event, never for the stream,
+// before it writes there again; the blocks that went through the compressor
+// and those that were decoded first in the last call; whether it ran its
+// kernels.
+struct UpdateScratch {
+    DevBuf meta, state, stat;
+    PinBuf pin;
+    hipEvent_t ev = nullptr;
+    bool ev_live = false;
+    uint64_t blocks = 0, decoded = 0;
+    bool stats_live = false;
+};
+
 } // namespace snapmi
 
 struct snapmi_host_pipe; // snapmi_frame.hip: staging of the host-buffer calls
@@ -256,34 +273,16 @@ struct snapmi_ctx {
     bool ev_ib_live = false, ev_ibg_live[2] = {false, false};
     uint64_t ib_groups = 0;
     bool ib_stats_live = false;
-    // snapmi_write_ranges_indexed: the device's copy of the host's write
-    // lists, the touched streams' states and the touched blocks' sums, the
-    // one-block streams of a group's compress launch, its compress slots, edge
-    // rooms (slots and rooms together at most write_scratch_bytes a group,
-    // unless one stream takes more) and piece descriptors, the two counters;
-    // the pinned staging of the lists with the event of the copy that last
-    // read it; touched blocks and edge blocks of the last call; whether it
-    // ran its kernels
-    snapmi::DevBuf wr_meta, wr_state, wr_z, wr_slot, wr_room, wr_desc, wr_stat;
-    snapmi::PinBuf pin_wr;
-    hipEvent_t ev_wr = nullptr;
-    bool ev_wr_live = false;
+    // snapmi_write_ranges_indexed and snapmi_append_indexed
+    // (snapmi_update.hip), each its own UpdateScratch: a write's list copy
+    // and an append's never wait for each other's event.  What a group of
+    // either runs in - the one-block streams of its compress launch, its
+    // compress slots, its rooms (slots and rooms together at most
+    // write_scratch_bytes a group, unless one stream takes more) and its piece
+    // descriptors - is one set: the calls follow each other on the stream.
+    snapmi::UpdateScratch wr, ap;
+    snapmi::DevBuf up_z, up_slot, up_room, up_desc;
     uint64_t write_scratch_bytes = 1ull << 30;
-    uint64_t wr_blocks = 0, wr_decoded = 0;
-    bool wr_stats_live = false;
-    // snapmi_append_indexed: the device's copy of the host's append lists,
-    // the named streams' states and the new blocks' sums, the two counters;
-    // the pinned staging of the lists with the event of the copy that last
-    // read it; new blocks and tails of the last call; whether it ran its
-    // kernels.  (Its one-block streams, compress slots, tail rooms and piece
-    // descriptors are the writes': wr_z, wr_slot, wr_room, wr_desc - the calls
-    // follow each other on the stream, and write_scratch_bytes bounds both.)
-    snapmi::DevBuf ap_meta, ap_state, ap_stat;
-    snapmi::PinBuf pin_ap;
-    hipEvent_t ev_ap = nullptr;
-    bool ev_ap_live = false;
-    uint64_t ap_blocks = 0, ap_decoded = 0;
-    bool ap_stats_live = false;
     // test options: "index_build_route" (BuildArgs::route) and the most
     // streams a group of the scan route holds
     uint32_t index_build_route = 0;

@@ -50,48 +50,6 @@ namespace snapmi {
 namespace {
 
 
-// reference bytes::read_varu64, src/bytes.rs:73-90 (returns header length,
-// 0 = invalid).  Executed redundantly by every lane on uniform data.
-__device__ __forceinline__ uint32_t read_varint(gcptr p, uint64_t n,
-                                                uint64_t *value)
-{
-    uint64_t acc = 0;
-    uint32_t shift = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint32_t b = p[i];
-        if (shift >= 64)
-            return 0;
-        if (b < 0x80) {
-            *value = acc | ((uint64_t)b << shift);
-            return (uint32_t)i + 1;
-        }
-        acc |= (uint64_t)(b & 0x7F) << shift;
-        shift += 7;
-    }
-    return 0;
-}
-
-// Header::read + the checks of Decoder::decompress, reference
-// src/decompress.rs:75-95,362-374.  Returns kind; on success fills hdr/dlen.
-__device__ __forceinline__ int read_header(gcptr in, uint64_t in_len,
-                                           uint32_t *hdr, uint64_t *dlen,
-                                           snapmi_error *errs, uint64_t i)
-{
-    uint64_t v = 0;
-    const uint32_t h = read_varint(in, in_len, &v);
-    if (h == 0) {
-        set_error(errs, i, SNAPMI_HEADER, 0, 0, 0);
-        return SNAPMI_HEADER;
-    }
-    if (v > kMaxInput) {
-        set_error(errs, i, SNAPMI_TOO_BIG, v, kMaxInput, 0);
-        return SNAPMI_TOO_BIG;
-    }
-    *hdr = h;
-    *dlen = v;
-    return SNAPMI_OK;
-}
-
 #define SNAPMI_FAIL(kind, fa, fb, fc)                                         \
     do {                                                                      \
         if (lane == 0) {                                                      \
@@ -3358,730 +3316,6 @@ __global__ __launch_bounds__(64) void k_index_walk(BuildArgs x)
         if (lane == 0)
             build_verdict(x, i, st);
     }
-}
-
-// ---------------------------------------------------------------------
-// snapmi_write_ranges_indexed: bytes [off, off + len) of a stream's output
-// replaced, only the touched blocks going through the codec
-// (snapmi_blockindex.hpp has the rules, WriteArgs the lists).  The host cuts
-// the touched streams into groups whose compress slots and edge rooms fit the
-// scratch and runs, per group: k_write_plan (a wavefront per touched stream:
-// header, writes against dlen, the index rule over EVERY block), k_write_blocks
-// (a thread per touched block: the piece of an edge block into its room, and
-// the block as a one-block stream of the compress launch - from its room, or
-// straight from the write that covers it), the batch decoder over the pieces,
-// k_write_patch (a wavefront per edge block: the writes' bytes over the
-// room), the batch compressor over the blocks, k_write_sizes (a workgroup per
-// touched stream: its pieces OK and full, the running sum of what its touched
-// blocks grew, the cap, out_lens and errs), k_write_jobs (the splice jobs of
-// the streams that passed, one per block) and k_write_splice (the copies).
-// Behind the last group k_write_index writes the new index.
-// The output of a stream is written by k_write_sizes (the varint) and
-// k_write_splice alone, both only for a stream in state 2: new length <= cap
-// is known by then, and the jobs' destinations [new entry k, new entry k + 1)
-// tile [varint, new length).  The write lists are the host's own; what the
-// device reads of the caller's - in_lens, first[], the index - is checked in
-// k_write_plan before anything is addressed with it: a stream in state 1 has
-// its entries inside the index and e[k] < e[k + 1] <= in_len for every block.
-// ---------------------------------------------------------------------
-namespace {
-__device__ __forceinline__ void write_fail(const WriteArgs &x, uint32_t t,
-                                           uint32_t s, int kind, uint64_t a,
-                                           uint64_t b, uint64_t c)
-{
-    x.out_lens[s] = 0;
-    set_error(x.errs, s, kind, a, b, c);
-    x.st_state[t] = 0;
-    atomicAdd(&x.stat[1], 1ull);
-}
-
-__device__ __forceinline__ uint64_t wave_min64(uint64_t v)
-{
-    for (uint32_t o = 32; o; o >>= 1) {
-        const uint64_t t = __shfl_xor(v, o);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-} // namespace
-
-// a thread per stream: "no write names it" until a later kernel says more
-__global__ __launch_bounds__(256) void k_write_init(WriteArgs x)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= x.n)
-        return;
-    x.out_lens[i] = 0;
-    set_error(x.errs, i, SNAPMI_OK, 0, 0, 0);
-}
-
-// a wavefront per touched stream of the group
-__global__ __launch_bounds__(256) void k_write_plan(WriteArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-    if (i >= x.tg)
-        return;
-    const uint32_t t = x.t0 + (uint32_t)i;
-    const uint32_t s = x.ts_stream[t];
-    const uint64_t in_len = x.in_lens[s];
-    uint32_t hdr = 0;
-    uint64_t dlen = 0;
-    // (an empty stream announces nothing, as for snapmi_decompress_len_batch)
-    if (in_len != 0) {
-        snapmi_error he;
-        if (read_header((gcptr)x.in_ptrs[s], in_len, &hdr, &dlen, &he, 0) !=
-            SNAPMI_OK) {
-            if (lane == 0)
-                write_fail(x, t, s, he.kind, he.a, he.b, he.c);
-            return;
-        }
-    }
-    // the first write that passes the stream's end
-    uint64_t bad = ~0ull;
-    for (uint32_t w = x.ts_w0[t] + lane; w < x.ts_w0[t + 1] && bad == ~0ull;
-         w += 64)
-        if (x.w_off[w] + x.w_len[w] > dlen)
-            bad = w;
-    bad = wave_min64(bad);
-    if (bad != ~0ull) {
-        if (lane == 0)
-            write_fail(x, t, s, SNAPMI_E_ARGUMENT, x.w_off[bad], x.w_len[bad],
-                       dlen);
-        return;
-    }
-    const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
-    if (!bi_range_stream_usable(in_len, hdr, dlen, x.index, f0, f1,
-                                x.entries)) {
-        if (lane == 0)
-            write_fail(x, t, s, SNAPMI_E_ARGUMENT, s, 0, 0);
-        return;
-    }
-    // (bi_write_first_bad_block, the lanes taking a block each)
-    const uint64_t *e = x.index + f0;
-    const uint64_t blocks = f1 - f0 - 1;
-    bad = ~0ull;
-    for (uint64_t k = lane; k < blocks && bad == ~0ull; k += 64)
-        if (!bi_range_block_usable(e, in_len, k))
-            bad = k;
-    bad = wave_min64(bad);
-    if (bad != ~0ull) {
-        if (lane == 0)
-            write_fail(x, t, s, SNAPMI_E_ARGUMENT, s, bad, 0);
-        return;
-    }
-    if (lane == 0) {
-        x.st_dlen[t] = dlen;
-        x.st_hdr[t] = hdr;
-        x.st_state[t] = 1;
-    }
-}
-
-// a thread per touched block of the group
-__global__ __launch_bounds__(256) void k_write_blocks(WriteArgs x)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= x.bg)
-        return;
-    const uint32_t b = x.b0 + (uint32_t)j;
-    const uint32_t t = x.tb_ts[b], r = x.tb_room[b];
-    uint8_t *const slot = x.slot + j * kSlotBytes;
-    // the block of a failed stream: an empty stream of the compress launch,
-    // and a piece that is not the decoder's (mode 3)
-    const void *zin = slot, *pin = nullptr;
-    void *pout = nullptr;
-    uint64_t zlen = 0, pinlen = 0;
-    uint8_t mode = 3;
-    if (x.st_state[t] == 1) {
-        // (state 1: every write lies inside dlen, so k < 65 536; the entries
-        // lie inside the index and inside the stream)
-        const uint32_t s = x.ts_stream[t];
-        const uint64_t k = x.tb_k[b];
-        const uint64_t rest = x.st_dlen[t] - k * kBiBlock;
-        zlen = rest < kBiBlock ? rest : kBiBlock;
-        if (r != 0xFFFFFFFFu) {
-            const uint64_t *e = x.index + x.first[s];
-            pin = (const uint8_t *)x.in_ptrs[s] + e[k];
-            pinlen = e[k + 1] - e[k];
-            pout = x.room + (uint64_t)r * kBiBlock;
-            mode = 2;
-            zin = pout;
-        } else {
-            const uint32_t w = x.tb_w[b];
-            zin = (const uint8_t *)x.w_src[w] + (k * kBiBlock - x.w_off[w]);
-        }
-    }
-    x.z_in[j] = zin;
-    x.z_inlen[j] = zlen;
-    x.z_out[j] = slot;
-    x.z_outlen[j] = 0;
-    if (r != 0xFFFFFFFFu) {
-        x.c_in[r] = pin;
-        x.c_inlen[r] = pinlen;
-        x.c_out[r] = pout;
-        x.c_cap[r] = mode == 2 ? zlen : 0;
-        x.c_outlen[r] = 0;
-        set_error(x.c_err, r, SNAPMI_OK, 0, 0, 0);
-        x.c_mode[r] = mode;
-    }
-}
-
-// a wavefront per touched block of the group: every write that touches an
-// edge block, over its room.  (A room whose piece failed is patched too: its
-// stream fails in k_write_sizes and what the block compresses to is dropped.)
-__global__ __launch_bounds__(256) void k_write_patch(WriteArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t j = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-    if (j >= x.bg)
-        return;
-    const uint32_t b = x.b0 + (uint32_t)j;
-    const uint32_t t = x.tb_ts[b], r = x.tb_room[b];
-    if (r == 0xFFFFFFFFu || x.st_state[t] != 1)
-        return;
-    const uint64_t k = x.tb_k[b];
-    const gptr room = (gptr)(x.room + (uint64_t)r * kBiBlock);
-    // its first write, and those behind it that start inside the block
-    for (uint32_t w = x.tb_w[b]; w < x.ts_w0[t + 1]; w++) {
-        const uint64_t off = x.w_off[w], len = x.w_len[w];
-        if (off / kBiBlock > k)
-            break;
-        const BiSpan sp = bi_write_span(off, len, k);
-        wave_copy<false>(room + sp.from, (gcptr)x.w_src[w] + sp.to, sp.n,
-                         lane);
-    }
-}
-
-// a workgroup per touched stream of the group
-__global__ __launch_bounds__(256) void k_write_sizes(WriteArgs x)
-{
-    __shared__ uint64_t wave_bad[4];
-    const uint32_t t = x.t0 + blockIdx.x;
-    if (x.st_state[t] != 1) // k_write_plan wrote its out_lens and errs
-        return;
-    const uint32_t s = x.ts_stream[t];
-    const uint32_t ba = x.ts_b0[t], nt = x.ts_b0[t + 1] - ba;
-    // the first piece, in block order, that is not OK and full
-    uint64_t bad = ~0ull;
-    for (uint32_t i = threadIdx.x; i < nt && bad == ~0ull; i += blockDim.x) {
-        const uint32_t r = x.tb_room[ba + i];
-        if (r != 0xFFFFFFFFu &&
-            (x.c_mode[r] != 2 || x.c_err[r].kind != SNAPMI_OK ||
-             x.c_outlen[r] != x.c_cap[r]))
-            bad = i;
-    }
-    bad = wave_min64(bad);
-    if ((threadIdx.x & 63) == 0)
-        wave_bad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    for (uint32_t w = 0; w < 4; w++)
-        bad = wave_bad[w] < bad ? wave_bad[w] : bad;
-    if (bad != ~0ull) {
-        if (threadIdx.x == 0) {
-            const snapmi_error e = x.c_err[x.tb_room[ba + bad]];
-            if (e.kind != SNAPMI_OK)
-                write_fail(x, t, s, e.kind, e.a, e.b, e.c);
-            // not reached, kept as the guard of an invariant (see
-            // k_range_finish): a mode-2 piece that reports OK is full
-            else
-                write_fail(x, t, s, SNAPMI_E_ARGUMENT, s, x.tb_k[ba + bad], 0);
-        }
-        return;
-    }
-    // the running sum of what the touched blocks grew (bi_write_entry's tcum),
-    // blockDim.x blocks a stride
-    const uint64_t *e = x.index + x.first[s];
-    uint64_t *cum = x.tb_cum + ba + t;
-    uint64_t carry[1] = {0};
-    wg_scan_strided(
-        nt, carry,
-        [&](uint32_t i, uint64_t (&d)[1]) {
-            const uint32_t j = ba + i - x.b0;
-            const uint64_t k = x.tb_k[ba + i];
-            d[0] = x.z_outlen[j] - varint_len(x.z_inlen[j]) - (e[k + 1] - e[k]);
-        },
-        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
-            cum[i] = ex[0];
-        });
-    if (threadIdx.x != 0)
-        return;
-    cum[nt] = carry[0];
-    const uint64_t dlen = x.st_dlen[t];
-    const uint32_t hn = varint_len(dlen);
-    // (the last old entry is in_len: bi_range_stream_usable)
-    const uint64_t new_len = x.in_lens[s] + hn - x.st_hdr[t] + carry[0];
-    const uint64_t cap = x.out_caps[s];
-    if (!bi_write_fits(cap, new_len)) {
-        write_fail(x, t, s, SNAPMI_BUFFER_TOO_SMALL, cap, new_len, 0);
-        return;
-    }
-    gptr out = (gptr)x.out_ptrs[s];
-    uint64_t v = dlen;
-    for (uint32_t q = 0; q < hn; q++) {
-        out[q] = (uint8_t)((v & 0x7F) | (q + 1 < hn ? 0x80 : 0));
-        v >>= 7;
-    }
-    x.out_lens[s] = new_len;
-    set_error(x.errs, s, SNAPMI_OK, 0, 0, 0);
-    x.st_state[t] = 2;
-    atomicAdd(&x.stat[0], 1ull);
-}
-
-// one workgroup: the first splice job of every touched stream of the group -
-// a job per block for a stream that passed, none for the others
-__global__ __launch_bounds__(1024) void k_write_jobs(WriteArgs x)
-{
-    uint64_t carry[1] = {0};
-    wg_scan_strided(
-        x.tg, carry,
-        [&](uint32_t i, uint64_t (&c)[1]) {
-            if (x.st_state[x.t0 + i] == 2)
-                c[0] = bi_blocks(x.st_dlen[x.t0 + i]);
-        },
-        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
-            x.jobs_first[i] = ex[0];
-        });
-    if (threadIdx.x == 0)
-        x.jobs_first[x.tg] = carry[0];
-}
-
-// The copies: the wavefronts of a fixed grid take the jobs in turn (the host
-// does not know how many there are: dlen lives here).  Job (stream, block k):
-// the block's bytes - the old ones, or the slot's behind its varint - to the
-// stream's new entry k.
-__global__ __launch_bounds__(256) void k_write_splice(WriteArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    const uint64_t total = x.jobs_first[x.tg];
-    for (uint64_t id = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-         id < total; id += waves) {
-        // the last stream of the group whose jobs start at or in front of id
-        uint32_t lo = 0, hi = x.tg;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (x.jobs_first[mid] <= id)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const uint32_t t = x.t0 + lo;
-        const uint64_t k = id - x.jobs_first[lo];
-        const uint32_t s = x.ts_stream[t];
-        const uint32_t ba = x.ts_b0[t], nt = x.ts_b0[t + 1] - ba;
-        const uint64_t *tk = x.tb_k + ba;
-        const uint64_t *e = x.index + x.first[s];
-        const uint64_t below = bi_write_below(tk, nt, k);
-        const gptr dst = (gptr)x.out_ptrs[s] + e[k] +
-                         varint_len(x.st_dlen[t]) - x.st_hdr[t] +
-                         x.tb_cum[ba + t + below];
-        gcptr src;
-        uint64_t len;
-        if (below < nt && tk[below] == k) {
-            const uint32_t j = ba + (uint32_t)below - x.b0;
-            const uint32_t vl = varint_len(x.z_inlen[j]);
-            src = (gcptr)(x.slot + (uint64_t)j * kSlotBytes) + vl;
-            len = x.z_outlen[j] - vl;
-        } else {
-            src = (gcptr)x.in_ptrs[s] + e[k];
-            len = e[k + 1] - e[k];
-        }
-        wave_copy<true>(dst, src, len, lane);
-    }
-}
-
-// a thread per entry: the old entry, moved where a stream that passed owns it
-__global__ __launch_bounds__(256) void k_write_index(WriteArgs x)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= x.entries)
-        return;
-    uint64_t v = x.index[e];
-    const uint32_t s = bi_find_stream(x.first, x.n, e);
-    const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
-    if (f0 <= e && e < f1) {
-        uint32_t lo = 0, hi = x.ts; // the touched stream s is, if any
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (x.ts_stream[mid] < s)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        // (state 2: [f0, f1) lies inside the index, blocks + 1 entries)
-        if (lo < x.ts && x.ts_stream[lo] == s && x.st_state[lo] == 2) {
-            const uint32_t ba = x.ts_b0[lo], nt = x.ts_b0[lo + 1] - ba;
-            v = bi_write_entry(x.index + f0, e - f0, x.tb_k + ba,
-                               x.tb_cum + ba + lo, nt, x.st_hdr[lo],
-                               varint_len(x.st_dlen[lo]));
-        }
-    }
-    x.new_index[e] = v;
-}
-
-// ---------------------------------------------------------------------
-// snapmi_append_indexed: bytes appended to a stream's output, only the short
-// last block - the tail - and the new bytes going through the codec
-// (snapmi_blockindex.hpp has the rules, AppendArgs the lists).  The host cuts
-// the named streams into groups whose compress slots and tail rooms fit the
-// scratch and runs, per group: k_append_plan (a wavefront per named stream:
-// header, the announced length against the host's copy, the new length, the
-// index rule over every old block), k_append_blocks (a thread per new block:
-// the block as a one-block stream of the compress launch - from the tail's
-// room or straight from the source - and the tail's piece into its room), the
-// batch decoder over the pieces, k_append_fill (a wavefront per named stream:
-// the first source bytes behind the decoded tail), the batch compressor over
-// the blocks, k_append_sizes (a workgroup per named stream: its piece OK and
-// full, the running sum of its new blocks' sizes, the cap, out_lens and
-// errs, the new varint), k_append_jobs (the splice jobs of the streams that
-// passed: the old full blocks' bytes in pieces of kAppendCopyBytes, then a
-// job per new block) and k_append_splice (the copies).  Behind the last group
-// k_append_index writes the new first[] and the new index.
-// A stream's output is written by k_append_sizes and k_append_splice alone,
-// both only for a stream in state 2, as for the writes.  The lists are the
-// host's, laid out by ITS copy of what a stream announces: k_append_plan
-// fails a stream that announces anything else, so for a stream in state 1 the
-// lists describe the stream - and its entries lie inside the index with
-// e[k] < e[k + 1] <= in_len for every old block.
-// ---------------------------------------------------------------------
-namespace {
-__device__ __forceinline__ void append_fail(const AppendArgs &x, uint32_t t,
-                                            uint32_t s, int kind, uint64_t a,
-                                            uint64_t b, uint64_t c)
-{
-    x.out_lens[s] = 0;
-    set_error(x.errs, s, kind, a, b, c);
-    x.st_state[t] = 0;
-    atomicAdd(&x.stat[1], 1ull);
-}
-} // namespace
-
-// a thread per stream: "nobody names it" until a later kernel says more
-__global__ __launch_bounds__(256) void k_append_init(AppendArgs x)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= x.n)
-        return;
-    x.out_lens[i] = 0;
-    set_error(x.errs, i, SNAPMI_OK, 0, 0, 0);
-}
-
-// a wavefront per named stream of the group
-__global__ __launch_bounds__(256) void k_append_plan(AppendArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-    if (i >= x.tg)
-        return;
-    const uint32_t t = x.t0 + (uint32_t)i;
-    const uint32_t s = x.ns_stream[t];
-    const uint64_t in_len = x.in_lens[s];
-    uint32_t hdr = 0;
-    uint64_t dlen = 0;
-    // (an empty stream announces nothing, as for snapmi_decompress_len_batch)
-    if (in_len != 0) {
-        snapmi_error he;
-        if (read_header((gcptr)x.in_ptrs[s], in_len, &hdr, &dlen, &he, 0) !=
-            SNAPMI_OK) {
-            if (lane == 0)
-                append_fail(x, t, s, he.kind, he.a, he.b, he.c);
-            return;
-        }
-    }
-    if (dlen != x.ns_dlen[t]) {
-        if (lane == 0)
-            append_fail(x, t, s, SNAPMI_E_ARGUMENT, s, dlen, x.ns_dlen[t]);
-        return;
-    }
-    // (dlen <= 2^32 - 1, and dlen + add does not wrap: the host's check)
-    if (dlen + x.ns_add[t] > kMaxInput) {
-        if (lane == 0)
-            append_fail(x, t, s, SNAPMI_TOO_BIG, dlen + x.ns_add[t], kMaxInput,
-                        0);
-        return;
-    }
-    const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
-    if (!bi_range_stream_usable(in_len, hdr, dlen, x.index, f0, f1,
-                                x.entries)) {
-        if (lane == 0)
-            append_fail(x, t, s, SNAPMI_E_ARGUMENT, s, 0, 0);
-        return;
-    }
-    // (bi_append_first_bad_block, the lanes taking a block each)
-    const uint64_t *e = x.index + f0;
-    const uint64_t blocks = f1 - f0 - 1;
-    uint64_t bad = ~0ull;
-    for (uint64_t k = lane; k < blocks && bad == ~0ull; k += 64)
-        if (!bi_range_block_usable(e, in_len, k))
-            bad = k;
-    bad = wave_min64(bad);
-    if (bad != ~0ull) {
-        if (lane == 0)
-            append_fail(x, t, s, SNAPMI_E_ARGUMENT, s, bad, 0);
-        return;
-    }
-    if (lane == 0) {
-        x.st_hdr[t] = hdr;
-        x.st_state[t] = 1;
-    }
-}
-
-// a thread per new block of the group
-__global__ __launch_bounds__(256) void k_append_blocks(AppendArgs x)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= x.bg)
-        return;
-    const uint32_t b = x.b0 + (uint32_t)j;
-    const uint32_t t = x.nb_ns[b];
-    const uint64_t q = b - x.ns_b0[t]; // the block among its stream's new ones
-    const uint32_t r = q == 0 ? x.ns_room[t] : 0xFFFFFFFFu;
-    uint8_t *const slot = x.slot + j * kSlotBytes;
-    // the block of a failed stream: an empty stream of the compress launch,
-    // and a piece that is not the decoder's (mode 3)
-    const void *zin = slot, *pin = nullptr;
-    void *pout = nullptr;
-    uint64_t zlen = 0, pinlen = 0, pcap = 0;
-    uint8_t mode = 3;
-    if (x.st_state[t] == 1) {
-        // (state 1: the stream announces ns_dlen[t]; its entries lie inside
-        // the index and inside the stream)
-        const uint32_t s = x.ns_stream[t];
-        const uint64_t dlen = x.ns_dlen[t];
-        const BiAppendBlock nb = bi_append_block(dlen, x.ns_add[t], q);
-        zlen = nb.in_len;
-        if (nb.room) {
-            const uint64_t *e = x.index + x.first[s];
-            const uint64_t kf = bi_append_full(dlen);
-            pin = (const uint8_t *)x.in_ptrs[s] + e[kf];
-            pinlen = e[kf + 1] - e[kf];
-            pout = x.room + (uint64_t)r * kBiBlock;
-            pcap = bi_append_tail(dlen);
-            mode = 2;
-            zin = pout;
-        } else {
-            zin = (const uint8_t *)x.ns_src[t] + nb.off;
-        }
-    }
-    x.z_in[j] = zin;
-    x.z_inlen[j] = zlen;
-    x.z_out[j] = slot;
-    x.z_outlen[j] = 0;
-    if (r != 0xFFFFFFFFu) {
-        x.c_in[r] = pin;
-        x.c_inlen[r] = pinlen;
-        x.c_out[r] = pout;
-        x.c_cap[r] = pcap;
-        x.c_outlen[r] = 0;
-        set_error(x.c_err, r, SNAPMI_OK, 0, 0, 0);
-        x.c_mode[r] = mode;
-    }
-}
-
-// a wavefront per named stream of the group: the source bytes that fill the
-// tail's room, behind the decoded piece.  (A room whose piece failed is filled
-// too: its stream fails in k_append_sizes and what the block compresses to is
-// dropped.)
-__global__ __launch_bounds__(256) void k_append_fill(AppendArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-    if (i >= x.tg)
-        return;
-    const uint32_t t = x.t0 + (uint32_t)i;
-    const uint32_t r = x.ns_room[t];
-    if (r == 0xFFFFFFFFu || x.st_state[t] != 1)
-        return;
-    const uint64_t dlen = x.ns_dlen[t];
-    wave_copy<false>((gptr)(x.room + (uint64_t)r * kBiBlock) +
-                         bi_append_tail(dlen),
-                     (gcptr)x.ns_src[t], bi_append_fill(dlen, x.ns_add[t]),
-                     lane);
-}
-
-// a workgroup per named stream of the group
-__global__ __launch_bounds__(256) void k_append_sizes(AppendArgs x)
-{
-    const uint32_t t = x.t0 + blockIdx.x;
-    if (x.st_state[t] != 1) // k_append_plan wrote its out_lens and errs
-        return;
-    const uint32_t s = x.ns_stream[t];
-    const uint32_t ba = x.ns_b0[t], nb = x.ns_b0[t + 1] - ba;
-    const uint32_t r = x.ns_room[t];
-    // the tail's piece: OK and full
-    if (r != 0xFFFFFFFFu &&
-        (x.c_mode[r] != 2 || x.c_err[r].kind != SNAPMI_OK ||
-         x.c_outlen[r] != x.c_cap[r])) {
-        if (threadIdx.x == 0) {
-            const snapmi_error e = x.c_err[r];
-            if (e.kind != SNAPMI_OK)
-                append_fail(x, t, s, e.kind, e.a, e.b, e.c);
-            // not reached, kept as the guard of an invariant (see
-            // k_range_finish): a mode-2 piece that reports OK is full
-            else
-                append_fail(x, t, s, SNAPMI_E_ARGUMENT, s,
-                            bi_append_full(x.ns_dlen[t]), 0);
-        }
-        return;
-    }
-    // the running sum of the new blocks' sizes (bi_append_entry's ncum),
-    // blockDim.x blocks a stride
-    uint64_t *cum = x.nb_cum + ba + t;
-    uint64_t carry[1] = {0};
-    wg_scan_strided(
-        nb, carry,
-        [&](uint32_t i, uint64_t (&d)[1]) {
-            const uint32_t j = ba + i - x.b0;
-            d[0] = x.z_outlen[j] - varint_len(x.z_inlen[j]);
-        },
-        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
-            cum[i] = ex[0];
-        });
-    if (threadIdx.x != 0)
-        return;
-    cum[nb] = carry[0];
-    const uint64_t dlen = x.ns_dlen[t], total = dlen + x.ns_add[t];
-    const uint32_t hn = varint_len(total);
-    const uint64_t *e = x.index + x.first[s];
-    // (the old full blocks' bytes are [e[0], e[kf]), e[0] the old header)
-    const uint64_t new_len =
-        e[bi_append_full(dlen)] + hn - x.st_hdr[t] + carry[0];
-    const uint64_t cap = x.out_caps[s];
-    if (!bi_append_fits(cap, new_len)) {
-        append_fail(x, t, s, SNAPMI_BUFFER_TOO_SMALL, cap, new_len, 0);
-        return;
-    }
-    gptr out = (gptr)x.out_ptrs[s];
-    uint64_t v = total;
-    for (uint32_t q = 0; q < hn; q++) {
-        out[q] = (uint8_t)((v & 0x7F) | (q + 1 < hn ? 0x80 : 0));
-        v >>= 7;
-    }
-    x.out_lens[s] = new_len;
-    set_error(x.errs, s, SNAPMI_OK, 0, 0, 0);
-    x.st_state[t] = 2;
-    atomicAdd(&x.stat[0], 1ull);
-}
-
-namespace {
-// splice jobs that copy the old full blocks' bytes of named stream t (state 2)
-__device__ __forceinline__ uint64_t append_copy_jobs(const AppendArgs &x,
-                                                     uint32_t t)
-{
-    const uint64_t *e = x.index + x.first[x.ns_stream[t]];
-    const uint64_t bytes = e[bi_append_full(x.ns_dlen[t])] - e[0];
-    return (bytes + kAppendCopyBytes - 1) / kAppendCopyBytes;
-}
-} // namespace
-
-// one workgroup: the first splice job of every named stream of the group -
-// the copies of its old bytes and a job per new block for a stream that
-// passed, none for the others
-__global__ __launch_bounds__(1024) void k_append_jobs(AppendArgs x)
-{
-    uint64_t carry[1] = {0};
-    wg_scan_strided(
-        x.tg, carry,
-        [&](uint32_t i, uint64_t (&c)[1]) {
-            const uint32_t t = x.t0 + i;
-            if (x.st_state[t] == 2)
-                c[0] = append_copy_jobs(x, t) + (x.ns_b0[t + 1] - x.ns_b0[t]);
-        },
-        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
-            x.jobs_first[i] = ex[0];
-        });
-    if (threadIdx.x == 0)
-        x.jobs_first[x.tg] = carry[0];
-}
-
-// The copies: the wavefronts of a fixed grid take the jobs in turn (the host
-// does not know how many there are: the compressed lengths live here).
-__global__ __launch_bounds__(256) void k_append_splice(AppendArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    const uint64_t total = x.jobs_first[x.tg];
-    for (uint64_t id = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-         id < total; id += waves) {
-        // the last stream of the group whose jobs start at or in front of id
-        uint32_t lo = 0, hi = x.tg;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (x.jobs_first[mid] <= id)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const uint32_t t = x.t0 + lo;
-        const uint64_t q = id - x.jobs_first[lo];
-        const uint32_t s = x.ns_stream[t];
-        const uint64_t *e = x.index + x.first[s];
-        const uint64_t dlen = x.ns_dlen[t];
-        const uint64_t old_end = e[bi_append_full(dlen)];
-        const uint64_t copies = append_copy_jobs(x, t);
-        const uint32_t hn = varint_len(dlen + x.ns_add[t]);
-        const gptr out = (gptr)x.out_ptrs[s];
-        if (q < copies) {
-            const uint64_t from = e[0] + q * kAppendCopyBytes;
-            const uint64_t len = old_end - from < kAppendCopyBytes
-                                     ? old_end - from
-                                     : kAppendCopyBytes;
-            wave_copy<true>(out + hn + q * kAppendCopyBytes,
-                            (gcptr)x.in_ptrs[s] + from, len, lane);
-        } else {
-            const uint32_t ba = x.ns_b0[t];
-            const uint32_t j = ba + (uint32_t)(q - copies) - x.b0;
-            const uint32_t vl = varint_len(x.z_inlen[j]);
-            wave_copy<true>(out + hn + (old_end - e[0]) +
-                                x.nb_cum[ba + t + (q - copies)],
-                            (gcptr)(x.slot + (uint64_t)j * kSlotBytes) + vl,
-                            x.z_outlen[j] - vl, lane);
-        }
-    }
-}
-
-// a thread per new entry, and per place of the new first[]: the entries of a
-// stream that passed by bi_append_entry; the old ones of a stream nobody
-// names when first[] gives it just as many inside the index; else 0
-__global__ __launch_bounds__(256) void k_append_index(AppendArgs x)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g <= x.n)
-        x.new_first[g] = x.nf[g];
-    if (g >= x.new_entries)
-        return;
-    // (nf is the host's prefix sum, nf[0] = 0: s owns g)
-    const uint32_t s = bi_find_stream(x.nf, x.n, g);
-    const uint64_t k = g - x.nf[s], cnt = x.nf[s + 1] - x.nf[s];
-    uint32_t lo = 0, hi = x.ns; // the named stream s is, if any
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (x.ns_stream[mid] < s)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    uint64_t v = 0;
-    if (lo < x.ns && x.ns_stream[lo] == s) {
-        // (state 2: its old entries lie inside the index)
-        if (x.st_state[lo] == 2) {
-            const uint64_t dlen = x.ns_dlen[lo];
-            v = bi_append_entry(x.index + x.first[s], k, bi_append_full(dlen),
-                                x.nb_cum + x.ns_b0[lo] + lo, x.st_hdr[lo],
-                                varint_len(dlen + x.ns_add[lo]));
-        }
-    } else {
-        const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
-        if (f1 <= x.entries && f0 <= f1 && f1 - f0 == cnt)
-            v = x.index[f0 + k];
-    }
-    x.new_index[g] = v;
 }
 
 } // namespace snapmi

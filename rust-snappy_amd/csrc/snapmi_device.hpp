@@ -157,6 +157,48 @@ __device__ __forceinline__ void set_error(snapmi_error *errs, uint64_t i,
     }
 }
 
+// reference bytes::read_varu64, src/bytes.rs:73-90 (returns header length,
+// 0 = invalid).  Executed redundantly by every lane on uniform data.
+__device__ __forceinline__ uint32_t read_varint(gcptr p, uint64_t n,
+                                                uint64_t *value)
+{
+    uint64_t acc = 0;
+    uint32_t shift = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t b = p[i];
+        if (shift >= 64)
+            return 0;
+        if (b < 0x80) {
+            *value = acc | ((uint64_t)b << shift);
+            return (uint32_t)i + 1;
+        }
+        acc |= (uint64_t)(b & 0x7F) << shift;
+        shift += 7;
+    }
+    return 0;
+}
+
+// Header::read + the checks of Decoder::decompress, reference
+// src/decompress.rs:75-95,362-374.  Returns kind; on success fills hdr/dlen.
+__device__ __forceinline__ int read_header(gcptr in, uint64_t in_len,
+                                           uint32_t *hdr, uint64_t *dlen,
+                                           snapmi_error *errs, uint64_t i)
+{
+    uint64_t v = 0;
+    const uint32_t h = read_varint(in, in_len, &v);
+    if (h == 0) {
+        set_error(errs, i, SNAPMI_HEADER, 0, 0, 0);
+        return SNAPMI_HEADER;
+    }
+    if (v > kMaxInput) {
+        set_error(errs, i, SNAPMI_TOO_BIG, v, kMaxInput, 0);
+        return SNAPMI_TOO_BIG;
+    }
+    *hdr = h;
+    *dlen = v;
+    return SNAPMI_OK;
+}
+
 // A 256-byte window of a byte stream held in one VGPR: lane i owns the dword
 // at stream offset base + 4*i.  A wave-uniform position inside the window is
 // read with two v_readlane + one 64-bit scalar shift, i.e. without a memory

@@ -415,142 +415,6 @@ __global__ void k_range_scan_c(RangeArgs x);
 __global__ void k_range_plan(RangeArgs x);
 __global__ void k_range_pieces(RangeArgs x);
 __global__ void k_range_finish(RangeArgs x);
-// snapmi_write_ranges_indexed (bi_write_* of snapmi_blockindex.hpp): the
-// streams and their index, which the device distrusts; the write lists, which
-// the HOST built from its own arrays and which are trusted - the non-empty
-// writes, the touched streams (ascending) and the touched blocks of the call -
-// and ONE GROUP of consecutive touched streams [t0, t0 + tg) whose touched
-// blocks [b0, b0 + bg) have their compress slots, and the edge blocks among
-// them their rooms, in the scratch.
-struct WriteArgs {
-    const void *const *in_ptrs;
-    const uint64_t *in_lens;
-    const uint64_t *first; // [n + 1]
-    const uint64_t *index; // [entries]
-    uint64_t entries;
-    uint32_t n;
-    void *const *out_ptrs;
-    const uint64_t *out_caps;
-    uint64_t *out_lens;
-    snapmi_error *errs; // or nullptr
-    uint64_t *new_index; // [entries]
-    // the writes: [writes]
-    const uint64_t *w_off, *w_len, *w_src;
-    // the touched streams: [ts], and [ts + 1] the first write and the first
-    // touched block of each
-    const uint32_t *ts_stream, *ts_w0, *ts_b0;
-    uint32_t ts;
-    // the touched blocks: [tb] the block, its first write, its room inside
-    // its group (~0: covered) and its touched stream
-    const uint64_t *tb_k;
-    const uint32_t *tb_w, *tb_room, *tb_ts;
-    // [ts]: 0 failed (out_lens and errs are written), 1 planned, 2 passed:
-    // its blocks are spliced; the length its header announces and the bytes
-    // of that header; [tg + 1], of the group: the first splice job of each
-    uint8_t *st_state;
-    uint64_t *st_dlen;
-    uint32_t *st_hdr;
-    uint64_t *jobs_first;
-    // [tb + ts]: touched block b of touched stream t has its sum of changes
-    // (bi_write_entry's tcum) at b + t, the stream's total at ts_b0[t + 1] + t
-    uint64_t *tb_cum;
-    // the group
-    uint32_t t0, tg, b0, bg, rooms;
-    // [bg]: the one-block streams of the group's compress launch
-    const void **z_in;
-    uint64_t *z_inlen;
-    void **z_out;
-    uint64_t *z_outlen;
-    uint8_t *slot; // [bg * kSlotBytes]
-    uint8_t *room; // [rooms * 64 KiB]
-    // [rooms]
-    const void **c_in;
-    uint64_t *c_inlen;
-    void **c_out;
-    uint64_t *c_cap;
-    uint64_t *c_outlen;
-    snapmi_error *c_err;
-    uint8_t *c_mode;
-    unsigned long long *stat; // [0] streams that succeeded, [1] that failed
-};
-__global__ void k_write_init(WriteArgs x);
-__global__ void k_write_plan(WriteArgs x);
-__global__ void k_write_blocks(WriteArgs x);
-__global__ void k_write_patch(WriteArgs x);
-__global__ void k_write_sizes(WriteArgs x);
-__global__ void k_write_jobs(WriteArgs x);
-__global__ void k_write_splice(WriteArgs x);
-__global__ void k_write_index(WriteArgs x);
-// snapmi_append_indexed (bi_append_* of snapmi_blockindex.hpp): the streams and
-// their index, which the device distrusts; the append lists, which the HOST
-// built from its own arrays and which are trusted - the named streams
-// (ascending), what each announces by the host's copy (a stream that
-// announces anything else fails before the lists are used for it), its new
-// blocks - and ONE GROUP of consecutive named streams [t0, t0 + tg) whose new
-// blocks [b0, b0 + bg) have their compress slots, and the tails among them
-// their rooms, in the scratch.
-struct AppendArgs {
-    const void *const *in_ptrs;
-    const uint64_t *in_lens;
-    const uint64_t *first; // [n + 1]
-    const uint64_t *index; // [entries]
-    uint64_t entries;
-    uint32_t n;
-    void *const *out_ptrs;
-    const uint64_t *out_caps;
-    uint64_t *out_lens;
-    snapmi_error *errs;  // or nullptr
-    uint64_t *new_first; // [n + 1], the caller's
-    uint64_t *new_index; // [new_entries]
-    uint64_t new_entries;
-    const uint64_t *nf; // [n + 1] the prefix sum the host made
-    // the named streams: [ns] the stream, the host's copy of what it
-    // announces, the bytes appended and their source; [ns + 1] the first new
-    // block of each; [ns] its room inside its group (~0: no tail)
-    const uint32_t *ns_stream;
-    const uint64_t *ns_dlen, *ns_add, *ns_src;
-    const uint32_t *ns_b0, *ns_room;
-    uint32_t ns;
-    const uint32_t *nb_ns; // [new blocks] the named stream of each
-    // [ns]: 0 failed (out_lens and errs are written), 1 planned, 2 passed:
-    // its bytes are spliced; the bytes of its old header; [tg + 1], of the
-    // group: the first splice job of each
-    uint8_t *st_state;
-    uint32_t *st_hdr;
-    uint64_t *jobs_first;
-    // [new blocks + ns]: new block b of named stream t has the sum of the
-    // sizes of the stream's new blocks in front of it (bi_append_entry's
-    // ncum) at b + t, the stream's total at ns_b0[t + 1] + t
-    uint64_t *nb_cum;
-    // the group
-    uint32_t t0, tg, b0, bg, rooms;
-    // [bg]: the one-block streams of the group's compress launch
-    const void **z_in;
-    uint64_t *z_inlen;
-    void **z_out;
-    uint64_t *z_outlen;
-    uint8_t *slot; // [bg * kSlotBytes]
-    uint8_t *room; // [rooms * 64 KiB]
-    // [rooms]
-    const void **c_in;
-    uint64_t *c_inlen;
-    void **c_out;
-    uint64_t *c_cap;
-    uint64_t *c_outlen;
-    snapmi_error *c_err;
-    uint8_t *c_mode;
-    unsigned long long *stat; // [0] streams that succeeded, [1] that failed
-};
-// old bytes a splice job of an append copies at most
-constexpr uint64_t kAppendCopyBytes = 16384;
-__global__ void k_append_init(AppendArgs x);
-__global__ void k_append_plan(AppendArgs x);
-__global__ void k_append_blocks(AppendArgs x);
-__global__ void k_append_fill(AppendArgs x);
-__global__ void k_append_sizes(AppendArgs x);
-__global__ void k_append_jobs(AppendArgs x);
-__global__ void k_append_splice(AppendArgs x);
-__global__ void k_append_index(AppendArgs x);
 // snapmi_build_block_index (bi_build of snapmi_blockindex.hpp on the device):
 // the batch, the device's copies of the host's arrays - which size the index
 // and every launch and are trusted for nothing else -, and what the kernels

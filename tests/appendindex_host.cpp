@@ -13,6 +13,11 @@
 //                             same by bi_append_entry (2 * (kf + nb + 1)
 //                             numbers)
 //   F cap new_len          -> 0 / 1
+//   G scratch n (dlen add) * n
+//                          -> bi_update_groups as the entry point calls it:
+//                             the count, "t0 tg b0 bg rooms" for every group,
+//                             the three maxima, then the room of every named
+//                             stream (4294967295: no tail)
 // (it has a main of its own so that it can also be built with
 // -fsanitize=address,undefined and run as it is)
 #include <inttypes.h>
@@ -101,6 +106,35 @@ int main()
                        k == kf + nb ? '\n' : ' ');
         } else if (op == 'F' && a.size() == 2) {
             printf("%d\n", bi_append_fits(a[0], a[1]) ? 1 : 0);
+        } else if (op == 'G' && a.size() >= 2 && a.size() == 2 + 2 * a[1]) {
+            // the named streams: the first new block and the rooms of each
+            std::vector<uint32_t> ts_b0, ts_rooms;
+            uint32_t b = 0;
+            for (size_t i = 0; i < (size_t)a[1]; i++) {
+                const uint64_t dlen = a[2 + 2 * i], add = a[3 + 2 * i];
+                if (add == 0)
+                    continue;
+                ts_b0.push_back(b);
+                ts_rooms.push_back(bi_append_tail(dlen) ? 1 : 0);
+                b += (uint32_t)bi_append_blocks(dlen, add);
+            }
+            ts_b0.push_back(b);
+            const size_t ts = ts_rooms.size();
+            std::vector<BiUpdateGroup> groups(ts);
+            std::vector<uint32_t> room0(ts);
+            BiUpdateMax max;
+            const size_t count =
+                bi_update_groups(ts_b0.data(), ts_rooms.data(), ts, a[0],
+                                 groups.data(), room0.data(), &max);
+            printf("%zu", count);
+            for (size_t q = 0; q < count; q++)
+                printf(" %u %u %u %u %u", groups[q].t0, groups[q].tg,
+                       groups[q].b0, groups[q].bg, groups[q].rooms);
+            printf(" %" PRIu64 " %" PRIu64 " %" PRIu64, max.tg, max.bg,
+                   max.rooms);
+            for (size_t t = 0; t < ts; t++)
+                printf(" %u", ts_rooms[t] ? room0[t] : 0xFFFFFFFFu);
+            printf("\n");
         } else {
             return 2;
         }

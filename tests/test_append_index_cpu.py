@@ -248,6 +248,67 @@ def test_model_precedence_of_failures(case):
                       [(b"x",), (None,), (None,)]) == (2, 1, 1, 1)
 
 
+def groups_row(lens, adds, scratch):
+    """What the program's G command answers, from the model: A.groups names
+    the streams of every group; a named stream with a tail has one room, and
+    the rooms of a group count from 0."""
+    gs = A.groups(lens, adds, scratch)
+    row, rooms_of = [len(gs)], []
+    t0 = b0 = 0
+    top = [0, 0, 0]
+    for g in gs:
+        bg = sum(A.blocks(lens[s], adds[s]) for s in g)
+        tails = [int(A.tail(lens[s]) != 0) for s in g]
+        row += [t0, len(g), b0, bg, sum(tails)]
+        top = [max(a, b) for a, b in zip(top, (len(g), bg, sum(tails)))]
+        r = 0
+        for tail in tails:
+            rooms_of.append(r if tail else 2**32 - 1)
+            r += tail
+        t0 += len(g)
+        b0 += bg
+    return row + top + rooms_of
+
+
+def test_groups_of_named_streams(prog):
+    """bi_update_groups, as snapmi_append_indexed calls it, against A.groups:
+    whole named streams until the scratch is full, a stream that needs more
+    than the scratch alone in its group, the rooms numbered from 0 in every
+    group."""
+    six = ([200000] * 6, [200000] * 6)
+    lone = ([1, 65536, 10, 5, 70000], [1, 0, 65536 * 5, 1, 1])
+    cases = [(*six, A.FLOOR), (*six, 1 << 30),
+             ([65536, 1, 0], [1, 0, 1], 2 * A.SLOT), (*lone, A.FLOOR),
+             (*lone, 2 * A.FLOOR), ([7, 8], [0, 0], A.FLOOR)]
+    rng = random.Random(22)
+    for _ in range(300):
+        n = rng.randrange(1, 9)
+        lens = [rng.choice(A.OLD_LENS + [rng.randrange(1 << 18)])
+                for _ in range(n)]
+        adds = [rng.choice([0, 1, 65536, rng.randrange(1, 1 << 18)])
+                for _ in range(n)]
+        cases.append((lens, adds, rng.randrange(A.FLOOR, 8 * A.FLOOR + 1)))
+    rows = prog([f"G {scratch} {len(lens)} " +
+                 " ".join(f"{d} {a}" for d, a in zip(lens, adds))
+                 for lens, adds, scratch in cases])
+    for (lens, adds, scratch), row in zip(cases, rows):
+        assert row == groups_row(lens, adds, scratch), (lens, adds, scratch)
+    # 200 000 more bytes behind 200 000: the tail's room and four new blocks
+    assert rows[0] == [6] + [v for t in range(6) for v in (t, 1, 4 * t, 4, 1)
+                             ] + [1, 4, 1] + [0] * 6
+    assert rows[1] == [1, 0, 6, 0, 24, 6, 6, 24, 6, 0, 1, 2, 3, 4, 5]
+    assert rows[2] == [1, 0, 2, 0, 2, 0, 2, 2, 0, 2**32 - 1, 2**32 - 1]
+    # six new blocks behind ten bytes: more than the scratch, a group of its
+    # own between its neighbours, which share theirs when they fit
+    assert A.groups(*lone, A.FLOOR) == [[0], [2], [3], [4]]
+    assert A.groups(*lone, 2 * A.FLOOR) == [[0], [2], [3, 4]]
+    assert rows[4] == [3, 0, 1, 0, 1, 1, 1, 1, 1, 6, 1, 2, 2, 7, 2, 2,
+                       2, 6, 2, 0, 0, 0, 1]
+    assert rows[5] == [0, 0, 0, 0]
+    assert sum(len(A.groups(*c)) > 1 for c in cases[6:]) > 50
+    assert sum(len(A.groups(*c)) == 1 for c in cases[6:]) > 50
+
+
 def test_binding_exposes_the_call(built):
     from rust_snappy_amd import _lib, batch, raw
     L = _lib.load()

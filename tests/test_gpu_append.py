@@ -10,6 +10,7 @@ appended bytes and every output sit between guard bands (gpu_buffers.Slab)
 that are checked after every call, and the outputs are filled with the guard
 byte, so a byte written behind a stream's new length shows as well."""
 import ctypes as C
+import random
 
 import pytest
 import torch
@@ -389,6 +390,72 @@ def test_groups_at_the_floor(ctx):
         ctx.set_option("write_scratch_bytes", 1 << 30)
     exact(c, grouped, range(6), "a group per stream")
     assert grouped[:3] == plain[:3]
+
+
+# --------------------------------------------------------------- 6b. scale
+class Streams:
+    """Any inputs as a case: the oracle's streams and index of them."""
+
+    def __init__(self, inputs):
+        self.inputs = list(inputs)
+        self.old_lens = [len(d) for d in self.inputs]
+        self.comps = [O.compress(d) for d in self.inputs]
+        self.index = [B.expected_index(d) for d in self.inputs]
+        self.first = [0]
+        for idx in self.index:
+            self.first.append(self.first[-1] + len(idx))
+        self.flat = [e for idx in self.index for e in idx]
+        self.n = len(self.comps)
+
+
+def test_long_stream_strides(ctx):
+    """One stream of 70 full blocks and a tail of 100 bytes, 260 blocks and 5
+    bytes appended: more old blocks than the 64 a stride of k_append_plan
+    checks, old bytes for several splice jobs of 16 384, more new blocks than
+    the 256 a stride of k_append_sizes sums - the first of them rebuilt from
+    the tail's room."""
+    pattern = bytes(range(256)) * 4
+    old = (pattern * (71 * 64))[:70 * 65536 + 100]
+    extra = (bytes(reversed(pattern)) * (261 * 64))[:260 * 65536 + 5]
+    one = Streams([old])
+    e = one.index[0]
+    assert len(e) == 72 and e[70] - e[0] > 3 * 16384
+    assert A.blocks(len(old), len(extra)) == 261
+    assert A.block(len(old), len(extra), 0) == (True, 0, 65436, 65536)
+    c, res = run(ctx, one, [extra], "331 blocks")
+    exact(c, res, [0], "331 blocks")
+    assert ctx.info("append_blocks") == 261
+    assert ctx.info("append_blocks_decoded") == 1
+    assert ctx.info("append_streams_ok") == 1
+
+
+def test_more_named_streams_than_one_stride_of_the_job_scan(ctx):
+    """1 100 streams of 20 to 120 bytes, 1 to 9 bytes appended to each, in one
+    group, so k_append_jobs walks a second stride of its scan - whose first
+    stream (the group's 1 025th) has a cap one byte short: it fails, is
+    written nothing and has no splice job, and the streams behind it find
+    their jobs past its empty place in the list."""
+    rng = random.Random(1100)
+    n = 1100
+    many = Streams([A.text(rng.randrange(20, 121), 977 * i)
+                    for i in range(n)])
+    appends = [rng.randbytes(rng.randrange(1, 10)) for _ in range(n)]
+    assert A.groups(many.old_lens, [len(b) for b in appends],
+                    1 << 30) == [list(range(n))]
+    res, _, _ = A.expect(many.comps, many.flat, many.first, many.old_lens,
+                         appends, [1 << 40] * n, O.compress, A.decode_piece,
+                         A.header_error)
+    need = [len(r[0]) for r in res]
+    caps = [v + SLACK for v in need]
+    caps[1024] = need[1024] - 1
+    c, r = run(ctx, many, appends, "1 100 streams", caps=caps)
+    lens, errs, index, _ = r
+    assert (lens[1024], errs[1024]) == (0, (2, need[1024] - 1, need[1024], 0))
+    assert c.out.bytes(1024, caps[1024]) == bytes([GUARD]) * caps[1024]
+    assert sum(1 for e in errs if e != OK) == 1
+    exact(c, r, [s for s in range(n) if s != 1024], "1 100 streams")
+    assert ctx.info("append_streams_ok") == n - 1
+    assert ctx.info("append_streams_failed") == 1
 
 
 # --------------------------------------------------------------- 7. refusals

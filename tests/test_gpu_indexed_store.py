@@ -406,8 +406,8 @@ def test_chain_step_by_step(ctx, played, request):
 
 # (The "small_tables*" configurations are left out: k_match_spans_8k takes the
 # blocks of at most 8 KiB that the caller counted, and the writes and appends
-# hand launch_compress no such count - cnt8 is 0 at both call sites of
-# snapmi_index.hip, so compress_route never sets `small`.  "spans", "spans_lds",
+# hand launch_compress no such count - cnt8 is 0 at the call site in
+# snapmi_update.hip, so compress_route never sets `small`.  "spans", "spans_lds",
 # "waves*" are the window kernels the ctx parameters above already reach.)
 ROUTES = ["product", "lanes", "lanes_segmented", "lanes_overlap", "both",
           "spans_match", "coresident", "spans_sched", "lanes_spill",

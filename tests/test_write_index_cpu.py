@@ -215,6 +215,62 @@ def test_splice_entries(prog):
     assert prog(lines) == want
 
 
+def groups_row(ws, scratch):
+    """What the program's G command answers, from the model: W.groups names
+    the streams of every group; the touched blocks, in order, give the rest.
+    The rooms of a group's edge blocks count from 0 in block order."""
+    t = W.touched([w for w in ws if w[2]])
+    gs = W.groups(ws, scratch)
+    assert [s for g in gs for s in g] == sorted({q[0] for q in t})
+    row, rooms_of = [len(gs)], []
+    t0 = b0 = 0
+    top = [0, 0, 0]
+    for g in gs:
+        edges = [q[3] for q in t if q[0] in g]
+        row += [t0, len(g), b0, len(edges), sum(edges)]
+        top = [max(a, b) for a, b in zip(top, (len(g), len(edges),
+                                               sum(edges)))]
+        r = 0
+        for edge in edges:
+            rooms_of.append(r if edge else 2**32 - 1)
+            r += edge
+        t0 += len(g)
+        b0 += len(edges)
+    return row + top + rooms_of
+
+
+def test_groups_of_touched_streams(prog):
+    """bi_update_groups, as snapmi_write_ranges_indexed calls it, against
+    W.groups: whole touched streams until the scratch is full, a stream that
+    needs more than the scratch alone in its group, the rooms numbered from 0
+    in every group."""
+    three = [(1, 0, 5), (4, 1000, 140000), (5, 0, 65536)]
+    lone = [(1, 0, 5), (4, 0, 200000), (5, 0, 1), (6, 7, 1)]
+    cases = [(three, W.FLOOR), (three, 1 << 30), (lone, W.FLOOR),
+             (lone, 2 * W.FLOOR), ([(4, 0, 200000)], W.FLOOR), ([], W.FLOOR),
+             ([(3, 9, 0)], W.FLOOR)]
+    rng = random.Random(21)
+    cases += [(ws, rng.randrange(W.FLOOR, 8 * W.FLOOR + 1))
+              for ws in draws(7, 300)]
+    rows = prog([f"G {scratch} " + fmt(ws) for ws, scratch in cases])
+    for (ws, scratch), row in zip(cases, rows):
+        assert row == groups_row(ws, scratch), (ws, scratch)
+    assert rows[0] == [3, 0, 1, 0, 1, 1, 1, 1, 1, 3, 2, 2, 1, 4, 1, 0,
+                       1, 3, 2,
+                       0, 0, 2**32 - 1, 1, 2**32 - 1]
+    assert rows[1][:6] == [1, 0, 3, 0, 5, 3] and rows[1][6:9] == [3, 5, 3]
+    assert rows[1][9:] == [0, 1, 2**32 - 1, 2, 2**32 - 1]
+    # 200 000 bytes: four slots and the short last block's room, in a group
+    # of its own between its neighbours, which share theirs when they fit
+    assert W.groups(lone, W.FLOOR) == [[1], [4], [5], [6]]
+    assert W.groups(lone, 2 * W.FLOOR) == [[1], [4], [5, 6]]
+    assert rows[3][:16] == [3, 0, 1, 0, 1, 1, 1, 1, 1, 4, 1, 2, 2, 5, 2, 2]
+    assert rows[3][-2:] == [0, 1]
+    assert rows[5] == [0, 0, 0, 0] and rows[6] == [0, 0, 0, 0]
+    assert sum(len(W.groups(ws, sc)) > 1 for ws, sc in cases[7:]) > 50
+    assert sum(len(W.groups(ws, sc)) == 1 for ws, sc in cases[7:]) > 50
+
+
 @pytest.fixture(scope="module")
 def case():
     return W.Case()

@@ -13,6 +13,10 @@
 //                          -> the new entries by bi_write_splice, then the
 //                             same by bi_write_entry (2 * (blocks + 1) numbers)
 //   F cap new_len          -> 0 / 1
+//   G scratch m writes...  -> bi_update_groups of a CHECKED list, as the entry
+//                             point calls it: the count, "t0 tg b0 bg rooms"
+//                             for every group, the three maxima, then the
+//                             room of every touched block (4294967295: covered)
 // (it has a main of its own so that it can also be built with
 // -fsanitize=address,undefined and run as it is)
 #include <inttypes.h>
@@ -143,6 +147,47 @@ int main()
                        k == blocks ? '\n' : ' ');
         } else if (op == 'F' && a.size() == 2) {
             printf("%d\n", bi_write_fits(a[0], a[1]) ? 1 : 0);
+        } else if (op == 'G' && writes_at(a, 1, &w)) {
+            // the touched streams: the first block and the rooms of each
+            BiWriteWalk walk;
+            std::vector<uint32_t> ts_stream, ts_b0, ts_rooms;
+            std::vector<uint8_t> edge;
+            for (size_t i = 0; i < w.off.size(); i++) {
+                if (w.len[i] == 0)
+                    continue;
+                if (ts_stream.empty() || ts_stream.back() != w.stream[i]) {
+                    ts_stream.push_back(w.stream[i]);
+                    ts_b0.push_back((uint32_t)edge.size());
+                    ts_rooms.push_back(0);
+                }
+                uint64_t k0;
+                const uint64_t c = bi_write_touch(walk, w.stream[i], w.off[i],
+                                                  w.len[i], &k0);
+                for (uint64_t k = k0; k < k0 + c; k++) {
+                    edge.push_back(bi_write_edge(w.off[i], w.len[i], k));
+                    ts_rooms.back() += edge.back();
+                }
+            }
+            ts_b0.push_back((uint32_t)edge.size());
+            const size_t ts = ts_stream.size();
+            std::vector<BiUpdateGroup> groups(ts);
+            std::vector<uint32_t> room0(ts);
+            BiUpdateMax max;
+            const size_t count =
+                bi_update_groups(ts_b0.data(), ts_rooms.data(), ts, a[0],
+                                 groups.data(), room0.data(), &max);
+            printf("%zu", count);
+            for (size_t q = 0; q < count; q++)
+                printf(" %u %u %u %u %u", groups[q].t0, groups[q].tg,
+                       groups[q].b0, groups[q].bg, groups[q].rooms);
+            printf(" %" PRIu64 " %" PRIu64 " %" PRIu64, max.tg, max.bg,
+                   max.rooms);
+            for (size_t t = 0; t < ts; t++) {
+                uint32_t r = room0[t];
+                for (uint32_t b = ts_b0[t]; b < ts_b0[t + 1]; b++)
+                    printf(" %u", edge[b] ? r++ : 0xFFFFFFFFu);
+            }
+            printf("\n");
         } else {
             return 2;
         }

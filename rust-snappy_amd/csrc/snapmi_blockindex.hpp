@@ -8,7 +8,8 @@
 //                     given pass the rule (a hint is never trusted: anything
 //                     else is an ordinary stream of the batch launch)
 //   bi_piece          input and output range of piece k of an indexed stream
-//   bi_range_*        the rules of a range read (snapmi_decompress_ranges_indexed)
+//   bi_range_*        the rules of a range read (snapmi_decompress_ranges_indexed),
+//                     bi_range_groups how the host cuts a call into groups
 //   bi_write_*        the rules of a range write (snapmi_write_ranges_indexed)
 //   bi_append_*       the rules of an append (snapmi_append_indexed)
 //   bi_update_groups  how both cut their named streams into groups
@@ -242,6 +243,62 @@ SNAPMI_BI_HD inline BiSpan bi_range_span(uint64_t off, uint64_t len,
     s.to = lo - off;
     s.n = hi - lo;
     return s;
+}
+
+// Pieces of a call of m ranges, from the host's arrays: the touched blocks of
+// all of them (saturates at 2^64 - 1).
+SNAPMI_BI_HD inline uint64_t bi_range_pieces(const uint64_t *off,
+                                             const uint64_t *len, size_t m)
+{
+    uint64_t pieces = 0;
+    for (size_t r = 0; r < m; r++) {
+        uint64_t k0;
+        const uint64_t c = bi_range_blocks(off[r], len[r], &k0);
+        pieces = pieces + c < pieces ? ~0ull : pieces + c;
+    }
+    return pieces;
+}
+
+// The groups of a range call: the ranges are cut, in order, into groups whose
+// edge rooms (64 KiB each) fit `scratch_bytes`; a range has at most two, which
+// the floor of the option holds, and a range that alone needs more than the
+// scratch is a group of its own.  The groups follow each other on the stream
+// and reuse the rooms and the descriptor list.
+// ranges [r0, r0 + mg), their pieces and their edge rooms
+struct BiRangeGroup {
+    uint32_t r0, mg;
+    uint64_t pieces, rooms;
+};
+
+// the most pieces and rooms any group holds
+struct BiRangeMax {
+    uint64_t pieces, rooms;
+};
+
+// groups[] has m places.  Returns the number of groups (0 for m == 0).
+SNAPMI_BI_HD inline size_t bi_range_groups(const uint64_t *off,
+                                           const uint64_t *len, size_t m,
+                                           uint64_t scratch_bytes,
+                                           BiRangeGroup *groups,
+                                           BiRangeMax *max)
+{
+    max->pieces = max->rooms = 0;
+    const uint64_t room_cap = scratch_bytes / kBiBlock;
+    size_t count = 0;
+    for (size_t r = 0; r < m; r++) {
+        uint64_t k0;
+        const uint64_t c = bi_range_blocks(off[r], len[r], &k0);
+        const uint32_t e = bi_range_edges(off[r], len[r]);
+        if (count == 0 || groups[count - 1].rooms + e > room_cap)
+            groups[count++] = BiRangeGroup{(uint32_t)r, 0, 0, 0};
+        BiRangeGroup &g = groups[count - 1];
+        g.mg++;
+        g.pieces += c;
+        g.rooms += e;
+        max->pieces = g.pieces > max->pieces ? g.pieces : max->pieces;
+        max->rooms = g.rooms > max->rooms ? g.rooms : max->rooms;
+    }
+    return count;
 }
 
 // ---------------------------------------------------------------------
@@ -620,8 +677,8 @@ SNAPMI_BI_HD inline size_t bi_update_groups(const uint32_t *b0,
 // Building the index of a stream that came without one
 // (snapmi_build_block_index): a walk from element to element that notes where
 // the chain stands when exactly k * 64 KiB have been produced.  bi_build is
-// the definition; the kernels (the scan's cuts and k_index_walk in
-// snapmi_decompress.hip) must reproduce it.
+// the definition; the kernels (the scan's cuts in snapmi_decompress.hip and
+// k_index_walk in snapmi_index.hip) must reproduce it.
 //
 // The walk reads tag bytes and literal length bytes only.  Copy offsets are
 // not looked at: the builder finds boundaries, it does not say whether the

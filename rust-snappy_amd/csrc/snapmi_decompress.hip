@@ -35,9 +35,8 @@
 //       element boundaries at every 64 KiB of output (cuts), and the pieces
 //       between them through k_decompress_streams3; all long streams of a
 //       small batch in the same launches, a lone stream as a batch of one.
-//   k_index_build_* + k_index_walk   no decode at all: the block index of
-//       streams that came without one (snapmi_build_block_index), from the
-//       same scan's cuts, and by a sequential walk where the scan gives up.
+// (What cuts pieces from a block index, and what builds one from the scan's
+// cuts, decodes nothing and lives beside its host code: snapmi_index.hip.)
 //
 // DESIGN.md section 4.2 has the history (byte-per-lane kernel of round 1,
 // gone; 354 -> 16 ms at cfg2) and what bounds each of them.
@@ -2601,13 +2600,7 @@ __device__ __forceinline__ void stream_pieces(const StreamArgs &a, const uint32_
                    d0 = live ? a.cuts[k * 2 + 1] : 0;
     const uint64_t s1 = live ? a.cuts[k * 2 + 2] : 0,
                    d1 = live ? a.cuts[k * 2 + 3] : 0;
-    a.c_in[k] = a.in + s0;
-    a.c_inlen[k] = s1 - s0;
-    a.c_out[k] = a.out + d0;
-    a.c_cap[k] = d1 - d0;
-    a.c_mode[k] = 2;
-    a.c_outlen[k] = 0;
-    a.c_err[k].kind = SNAPMI_OK;
+    piece_put(a.c, k, a.in + s0, s1 - s0, a.out + d0, d1 - d0, 2);
 }
 
 __device__ __forceinline__ void stream_finish(const StreamArgs &a, const uint32_t wg)
@@ -2619,7 +2612,7 @@ __device__ __forceinline__ void stream_finish(const StreamArgs &a, const uint32_
     const uint64_t K = a.meta[3];
     if (!bad)
         for (uint64_t k = threadIdx.x; k < K; k += blockDim.x)
-            if (a.c_err[k].kind != SNAPMI_OK || a.c_outlen[k] != a.c_cap[k])
+            if (!piece_whole(a.c, k))
                 atomicOr(&bad, 1u);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -2716,605 +2709,6 @@ __global__ __launch_bounds__(1024) void k_long_plan(
             }
         }
         modes[i] = mode;
-    }
-}
-
-// ---------------------------------------------------------------------
-// snapmi_decompress_batch_indexed: the caller hands the block boundaries in
-// (snapmi_blockindex.hpp), so nothing is scanned and the host waits for
-// nothing.  ONE descriptor list holds the batch: slot i < n is stream i -
-// whole (mode 0) when its entries do not pass the rule, not this launch's
-// (mode 3) when they do (k_index_plan) - and slot n + e is index entry e:
-// for every entry of an indexed stream but its last a piece in mode 2,
-// exactly its room, so a piece writes only its own 64 KiB whatever the
-// entries say (k_index_pieces).  One launch of the batch decoder runs over
-// all of it, the short streams beside the pieces.  k_index_finish carries
-// the results of the whole streams to the caller's arrays and applies
-// stream_finish's rule to the indexed ones - every piece is this stream's,
-// reports OK and filled its room; a stream that fails it is decoded whole by
-// a second, gated launch over the caller's arrays (modes 0 for it, 3 for
-// every other stream), which names the error.
-// ---------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_index_plan(IndexArgs x)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        x.gate[1] = 0; // streams delivered by pieces
-        x.gate[2] = 0; // ... handed back
-    }
-    if (i >= x.n)
-        return;
-    const bool indexed = bi_stream_indexed(
-        (const uint8_t *)x.in_ptrs[i], x.in_lens[i], x.out_caps[i], x.index,
-        x.first[i], x.first[i + 1], x.entries);
-    x.modes[i] = 3; // of the launch behind: k_index_finish says who needs it
-    x.c_in[i] = x.in_ptrs[i];
-    x.c_inlen[i] = x.in_lens[i];
-    x.c_out[i] = x.out_ptrs[i];
-    x.c_cap[i] = x.out_caps[i];
-    x.c_outlen[i] = 0;
-    x.c_err[i].kind = SNAPMI_OK;
-    x.c_mode[i] = indexed ? 3 : 0;
-    if (indexed)
-        x.gate[0] = x.seq; // (every writer stores the same value)
-}
-
-__global__ __launch_bounds__(256) void k_index_pieces(IndexArgs x)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= x.entries)
-        return;
-    // a slot that is no piece: not the launch's (mode 3)
-    const void *in = nullptr;
-    void *out = nullptr;
-    uint64_t in_len = 0, room = 0;
-    uint32_t owner = 0xFFFFFFFFu;
-    uint8_t mode = 3;
-    if (x.gate[0] == x.seq) { // (else no stream is indexed)
-        const uint32_t s = bi_find_stream(x.first, x.n, e);
-        const uint64_t f0 = x.first[s], f1 = x.first[s + 1];
-        // (first[] is the caller's too: the search may land anywhere)
-        if (x.c_mode[s] == 3 && f0 <= e && e + 1 < f1 && f1 <= x.entries) {
-            uint64_t dlen = 0;
-            const uint8_t *sin = (const uint8_t *)x.in_ptrs[s];
-            if (bi_header(sin, x.in_lens[s], &dlen)) {
-                const BiPiece p = bi_piece(x.index + f0, dlen, e - f0);
-                in = sin + p.in_off;
-                in_len = p.in_len;
-                out = (uint8_t *)x.out_ptrs[s] + p.out_off;
-                room = p.out_len;
-                owner = s;
-                mode = 2;
-            }
-        }
-    }
-    const uint64_t k = (uint64_t)x.n + e;
-    x.c_in[k] = in;
-    x.c_inlen[k] = in_len;
-    x.c_out[k] = out;
-    x.c_cap[k] = room;
-    x.c_outlen[k] = 0;
-    x.c_err[k].kind = SNAPMI_OK;
-    x.c_owner[e] = owner;
-    x.c_mode[k] = mode;
-}
-
-// a wavefront per stream
-__global__ __launch_bounds__(256) void k_index_finish(IndexArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-    if (i >= x.n)
-        return;
-    if (x.c_mode[i] != 3) { // decoded whole, as slot i: its results home
-        if (lane == 0) {
-            x.out_lens[i] = x.c_outlen[i];
-            if (x.errs)
-                x.errs[i] = x.c_err[i];
-        }
-        return;
-    }
-    const uint64_t f0 = x.first[i], f1 = x.first[i + 1];
-    bool bad = false;
-    for (uint64_t e = f0 + lane; e + 1 < f1; e += 64) {
-        const uint64_t k = (uint64_t)x.n + e;
-        if (x.c_owner[e] != (uint32_t)i || x.c_mode[k] != 2 ||
-            x.c_err[k].kind != SNAPMI_OK || x.c_outlen[k] != x.c_cap[k])
-            bad = true;
-    }
-    const bool any_bad = __ballot(bad) != 0;
-    if (lane != 0)
-        return;
-    if (any_bad) {
-        x.modes[i] = 0;    // the launch behind decodes it whole
-        x.gate[3] = x.seq; // ... and has something to do
-        atomicAdd(&x.gate[2], 1ull);
-        return;
-    }
-    uint64_t dlen = 0;
-    bi_header((const uint8_t *)x.in_ptrs[i], x.in_lens[i], &dlen);
-    x.out_lens[i] = dlen;
-    set_error(x.errs, i, SNAPMI_OK, 0, 0, 0);
-    atomicAdd(&x.gate[1], 1ull);
-}
-
-// ---------------------------------------------------------------------
-// snapmi_decompress_ranges_indexed: bytes [off, off + len) of a stream's
-// output from the pieces of the blocks the range touches, nothing else of the
-// stream being read (snapmi_blockindex.hpp has the rules).  The host cuts the
-// ranges into consecutive groups whose edge rooms fit the scratch and runs,
-// per group: the scan (a) (b) (c) of what the DEVICE arrays ask for - pieces
-// and edge rooms per range, so every range knows its slots -, k_range_plan
-// (a thread per range: its verdict), k_range_pieces (a thread per piece slot:
-// a descriptor in mode 2, straight into the caller's buffer for a block that
-// lies wholly inside the range, into a room for an edge block; mode 3 for
-// a slot that is nobody's), one launch of the batch decoder over the list,
-// and k_range_finish (a wavefront per range: all pieces OK and full, the
-// wanted span of the rooms copied out, got and err).  A piece writes exactly
-// its room and a room or a block inside the buffer is all it is ever given,
-// so nothing outside [r_out[r], + r_len[r]) and the scratch is written
-// whatever the index, first[] and the range arrays hold; slots are bounded by
-// what the HOST sized (pieces, rooms), which bounds every list and the
-// scratch.
-// ---------------------------------------------------------------------
-namespace {
-// what range r of the device arrays asks for (the count clamped: the sums of
-// m < 2^31 of them cannot wrap)
-__device__ __forceinline__ uint64_t range_count(const RangeArgs &x, uint64_t r,
-                                                uint64_t *k0, uint32_t *edges)
-{
-    const uint64_t off = x.r_off[r], len = x.r_len[r];
-    const uint64_t cnt = bi_range_blocks(off, len, k0);
-    *edges = bi_range_edges(off, len);
-    return cnt < kRangeCountClamp ? cnt : kRangeCountClamp;
-}
-
-// ... and the slots it is given in the scans: none when it asks for more
-// than the whole group was sized for - it fails wherever it stands, and the
-// ranges behind it keep their places
-__device__ __forceinline__ void range_slots(const RangeArgs &x, uint64_t r,
-                                            uint64_t *cnt, uint64_t *edges)
-{
-    uint64_t k0;
-    uint32_t e;
-    const uint64_t c = range_count(x, r, &k0, &e);
-    const bool fits = c <= x.pieces && e <= x.rooms;
-    *cnt = fits ? c : 0;
-    *edges = fits ? e : 0;
-}
-
-__device__ __forceinline__ void range_fail(const RangeArgs &x, uint64_t r,
-                                           int kind, uint64_t a, uint64_t b,
-                                           uint64_t c)
-{
-    x.r_got[r] = 0;
-    set_error(x.r_errs, r, kind, a, b, c);
-    x.state[r] = 0;
-    if (kind != SNAPMI_OK)
-        atomicAdd(&x.stat[1], 1ull);
-    else
-        atomicAdd(&x.stat[0], 1ull);
-}
-} // namespace
-
-// (the three launches of snapmi_scan.hpp; part: pieces and rooms per
-// workgroup, and nobody wants the totals)
-__global__ __launch_bounds__(1024) void k_range_scan_a(RangeArgs x)
-{
-    wg_scan_a<uint64_t, 2>(
-        x.mg, x.part,
-        [&](uint32_t i, uint64_t (&v)[2]) {
-            range_slots(x, (uint64_t)x.r0 + i, &v[0], &v[1]);
-        },
-        [&](uint32_t i, const uint64_t (&)[2], const uint64_t (&ex)[2]) {
-            x.slot[x.r0 + i] = ex[0];
-            x.eslot[x.r0 + i] = ex[1];
-        });
-}
-
-__global__ __launch_bounds__(1024) void k_range_scan_b(RangeArgs x,
-                                                       uint32_t nparts)
-{
-    uint64_t carry[2] = {0, 0};
-    wg_scan_b(x.part, nparts, carry);
-}
-
-__global__ __launch_bounds__(1024) void k_range_scan_c(RangeArgs x)
-{
-    wg_scan_c<uint64_t, 2>(x.mg, x.part,
-                           [&](uint32_t i, const uint64_t (&off)[2]) {
-                               x.slot[x.r0 + i] += off[0];
-                               x.eslot[x.r0 + i] += off[1];
-                           });
-}
-
-// a thread per range: everything that can be said without its pieces
-__global__ __launch_bounds__(256) void k_range_plan(RangeArgs x)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= x.mg)
-        return;
-    const uint64_t r = (uint64_t)x.r0 + i;
-    const uint32_t s = x.r_stream[r];
-    const uint64_t off = x.r_off[r], len = x.r_len[r];
-    if (s >= x.n) {
-        range_fail(x, r, SNAPMI_E_ARGUMENT, s, x.n, 0);
-        return;
-    }
-    const uint64_t in_len = x.in_lens[s];
-    uint32_t hdr = 0;
-    uint64_t dlen = 0;
-    // (an empty stream announces nothing, as for snapmi_decompress_len_batch)
-    if (in_len != 0) {
-        snapmi_error he;
-        if (read_header((gcptr)x.in_ptrs[s], in_len, &hdr, &dlen, &he, 0) !=
-            SNAPMI_OK) {
-            range_fail(x, r, he.kind, he.a, he.b, he.c);
-            return;
-        }
-    }
-    if (off + len < off || off + len > dlen) {
-        range_fail(x, r, SNAPMI_E_ARGUMENT, off, len, dlen);
-        return;
-    }
-    if (len == 0) {
-        range_fail(x, r, SNAPMI_OK, 0, 0, 0); // (nothing to fetch: done)
-        return;
-    }
-    // its slots, inside what the host sized
-    uint64_t k0;
-    uint32_t edges;
-    const uint64_t cnt = range_count(x, r, &k0, &edges);
-    if (cnt > x.pieces || edges > x.rooms || x.slot[r] > x.pieces ||
-        cnt > x.pieces - x.slot[r] ||
-        x.eslot[r] > x.rooms || edges > x.rooms - x.eslot[r]) {
-        range_fail(x, r, SNAPMI_E_ARGUMENT, x.slot[r], cnt, x.pieces);
-        return;
-    }
-    if (!bi_range_stream_usable(in_len, hdr, dlen, x.index, x.first[s],
-                                x.first[s + 1], x.entries)) {
-        range_fail(x, r, SNAPMI_E_ARGUMENT, s, k0, 0);
-        return;
-    }
-    x.state[r] = 1;
-}
-
-// a thread per piece slot of the group
-__global__ __launch_bounds__(256) void k_range_pieces(RangeArgs x)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= x.pieces)
-        return;
-    // the range whose slots hold j: the last one of the group that starts at
-    // or in front of it (a range without pieces starts where the next does)
-    uint32_t lo = 0, hi = x.mg;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (x.slot[x.r0 + mid] <= j)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const uint64_t r = (uint64_t)x.r0 + lo;
-    const void *in = nullptr;
-    void *out = nullptr;
-    uint64_t in_len = 0, room = 0;
-    uint8_t mode = 3; // nobody's, or a failed range's: not the launch's
-    snapmi_error err;
-    err.kind = SNAPMI_OK;
-    err.reserved = 0;
-    err.a = err.b = err.c = 0;
-    if (x.state[r] == 1 && x.slot[r] <= j) {
-        const uint64_t off = x.r_off[r], len = x.r_len[r];
-        uint64_t k0;
-        uint32_t edges;
-        const uint64_t cnt = range_count(x, r, &k0, &edges);
-        if (j - x.slot[r] < cnt) {
-            // (state 1: the stream exists, its header parses, the range lies
-            // inside it, its entries inside the index)
-            const uint32_t s = x.r_stream[r];
-            const uint64_t k = k0 + (j - x.slot[r]);
-            const uint8_t *sin = (const uint8_t *)x.in_ptrs[s];
-            const uint64_t s_len = x.in_lens[s];
-            const uint64_t *e = x.index + x.first[s];
-            uint64_t dlen = 0;
-            bi_header(sin, s_len, &dlen);
-            if (!bi_range_block_usable(e, s_len, k)) {
-                err.kind = SNAPMI_E_ARGUMENT;
-                err.a = s;
-                err.b = k;
-            } else {
-                const BiPiece p = bi_piece(e, dlen, k);
-                in = sin + p.in_off;
-                in_len = p.in_len;
-                room = p.out_len;
-                if (bi_range_edge(off, len, k))
-                    out = x.room + (x.eslot[r] +
-                                    bi_range_edge_slot(off, len, k)) *
-                                       kBiBlock;
-                else
-                    out = (uint8_t *)x.r_out[r] + (k * kBiBlock - off);
-                mode = 2;
-            }
-        }
-    }
-    x.c_in[j] = in;
-    x.c_inlen[j] = in_len;
-    x.c_out[j] = out;
-    x.c_cap[j] = room;
-    x.c_outlen[j] = 0;
-    x.c_err[j] = err;
-    x.c_mode[j] = mode;
-}
-
-// a wavefront per range
-__global__ __launch_bounds__(256) void k_range_finish(RangeArgs x)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t i = (uint64_t)blockIdx.x * (blockDim.x >> 6) +
-                       (threadIdx.x >> 6);
-    if (i >= x.mg)
-        return;
-    const uint64_t r = (uint64_t)x.r0 + i;
-    if (x.state[r] != 1) // k_range_plan wrote its got and err
-        return;
-    const uint64_t off = x.r_off[r], len = x.r_len[r];
-    uint64_t k0;
-    uint32_t edges;
-    const uint64_t cnt = range_count(x, r, &k0, &edges);
-    const uint64_t j0 = x.slot[r];
-    // the first piece, in block order, that is not OK and full
-    uint64_t bad = ~0ull;
-    for (uint64_t t = lane; t < cnt && bad == ~0ull; t += 64) {
-        const uint64_t j = j0 + t;
-        if (x.c_mode[j] != 2 || x.c_err[j].kind != SNAPMI_OK ||
-            x.c_outlen[j] != x.c_cap[j])
-            bad = j;
-    }
-    for (uint32_t o = 32; o; o >>= 1) {
-        const uint64_t t = __shfl_xor(bad, o);
-        bad = t < bad ? t : bad;
-    }
-    if (bad != ~0ull) {
-        if (lane == 0) {
-            const snapmi_error e = x.c_err[bad];
-            x.r_got[r] = 0;
-            if (e.kind != SNAPMI_OK)
-                set_error(x.r_errs, r, e.kind, e.a, e.b, e.c);
-            // not reached, kept as the guard of an invariant: every decoder
-            // takes a mode-2 piece's room for the announced length, writes
-            // out_lens = room only beside OK and reports HEADER_MISMATCH
-            // {room, produced} when the elements end short of it, so a piece
-            // that reports OK is full - and a state-1 range's slots are all
-            // mode 2 or carry k_range_pieces' own error
-            else
-                set_error(x.r_errs, r, SNAPMI_E_ARGUMENT,
-                          x.r_stream[r], k0 + (bad - j0), 0);
-            atomicAdd(&x.stat[1], 1ull);
-        }
-        return;
-    }
-    // the wanted span of the edge rooms: bytes up to the destination's next
-    // 16-byte boundary, 16-byte stores fed by unaligned 16-byte loads, bytes
-    typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-    uint8_t *const dst0 = (uint8_t *)x.r_out[r];
-    for (uint32_t q = 0; q < 2; q++) {
-        const uint64_t k = q == 0 ? k0 : k0 + cnt - 1;
-        if ((q == 1 && cnt == 1) || !bi_range_edge(off, len, k))
-            continue;
-        const BiSpan sp = bi_range_span(off, len, k);
-        const uint8_t *from =
-            x.room +
-            (x.eslot[r] + bi_range_edge_slot(off, len, k)) * kBiBlock +
-            sp.from;
-        uint8_t *to = dst0 + sp.to;
-        const uint32_t n = (uint32_t)sp.n; // <= 64 KiB
-        uint32_t head = (uint32_t)((16 - ((uintptr_t)to & 15)) & 15);
-        if (head > n)
-            head = n;
-        if (lane < head)
-            to[lane] = from[lane];
-        const uint32_t body = (n - head) & ~15u;
-        for (uint32_t b = 16 * lane; b < body; b += 16 * 64) {
-            u32x4 v;
-            __builtin_memcpy(&v, from + head + b, 16);
-            *(g_u32x4 *)(to + head + b) = v;
-        }
-        const uint32_t tail = n - head - body;
-        if (lane < tail)
-            to[head + body + lane] = from[head + body + lane];
-    }
-    if (lane == 0) {
-        x.r_got[r] = len;
-        set_error(x.r_errs, r, SNAPMI_OK, 0, 0, 0);
-        atomicAdd(&x.stat[0], 1ull);
-    }
-}
-
-// ---------------------------------------------------------------------
-// snapmi_build_block_index: bi_build (snapmi_blockindex.hpp) for every stream
-// of a batch that came without an index.  The host's copies of the lengths
-// size the index, the scratch and every launch; the device checks them and
-// trusts them for nothing else.
-//   k_index_build_plan     a thread per stream: the caller's length and the
-//       header against the host's copies (MISSIZED), the entries of a stream
-//       of at most one block; a stream of two blocks and more stays pending
-//       (state 0) - or goes straight to the walk list (route 1, or too long
-//       for the scan's plan).  The index is all 0 when it runs.
-//   per group of pending streams: k_index_build_adopt hands the descriptors
-//       the host laid out their input pointers (a stream that is no longer
-//       pending gets an empty input: stream_head leaves it alone with
-//       meta[2] = 1 and no kernel behind it reads a byte), k_bstream_head ..
-//       k_bstream_cuts as for the decoder, and k_index_build_entries (a
-//       wavefront per stream) turns cuts[] into entries: BUILT when every
-//       interior cut stands exactly on its boundary, UNALIGNED when one
-//       stands behind it; a stream the scan gave up on (meta[2] != 0) joins
-//       the walk list.
-//   k_index_walk           a wavefront per listed stream runs bi_walk.  The
-//       list and its count are device memory: the launch reads them, the host
-//       never does.
-// Every writer of entries writes inside [first[i], first[i + 1]) of its own
-// stream, whose count is bi_entries(h_out[i]): what the host sized.
-// ---------------------------------------------------------------------
-namespace {
-__device__ __forceinline__ void build_verdict(const BuildArgs &x, uint32_t i,
-                                              int st)
-{
-    x.state[i] = (uint8_t)st;
-    if (x.status)
-        x.status[i] = (uint8_t)st;
-    atomicAdd(&x.stat[st - 1], 1ull);
-}
-__device__ __forceinline__ void build_to_walker(const BuildArgs &x, uint32_t i)
-{
-    // (at most one entry per stream: the list holds n)
-    const unsigned long long slot = atomicAdd(&x.stat[4], 1ull);
-    x.walk[slot] = i;
-}
-} // namespace
-
-__global__ __launch_bounds__(256) void k_index_build_plan(BuildArgs x)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= x.n)
-        return;
-    const uint32_t i = (uint32_t)t;
-    const uint64_t in_len = x.h_in[i], dlen = x.h_out[i];
-    if (x.in_lens[i] != in_len) {
-        build_verdict(x, i, kBiMissized);
-        return;
-    }
-    const uint8_t *in = (const uint8_t *)x.in_ptrs[i];
-    uint64_t announced = 0;
-    const uint32_t hdr = bi_header(in, in_len, &announced);
-    if (hdr && announced != dlen) {
-        build_verdict(x, i, kBiMissized);
-        return;
-    }
-    if (dlen > kBiBlock) {
-        // (a header that does not parse included: its walk says CORRUPT)
-        x.state[i] = 0;
-        if (x.route == 2 && in_len > x.scan_max_len)
-            build_verdict(x, i, kBiCorrupt); // (no walker under route 2)
-        else if (x.route == 1 || in_len > x.scan_max_len)
-            build_to_walker(x, i);
-        return;
-    }
-    if (hdr == 0 || (dlen == 0 && in_len != hdr)) {
-        build_verdict(x, i, kBiCorrupt);
-        return;
-    }
-    uint64_t *e = x.index + x.first[i];
-    e[0] = hdr;
-    if (dlen)
-        e[1] = in_len;
-    build_verdict(x, i, kBiBuilt);
-}
-
-__global__ __launch_bounds__(256) void k_index_build_adopt(BuildArgs x,
-                                                           BuildGroup g)
-{
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= g.mg)
-        return;
-    const uint32_t i = g.idx[j];
-    const bool pending = x.state[i] == 0;
-    g.descs[j].in = pending ? (const uint8_t *)x.in_ptrs[i] : nullptr;
-    if (!pending)
-        g.descs[j].in_len = 0;
-}
-
-// a wavefront per stream of the group
-__global__ __launch_bounds__(256) void k_index_build_entries(BuildArgs x,
-                                                             BuildGroup g)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (j >= g.mg)
-        return;
-    const uint32_t i = g.idx[j];
-    if (x.state[i] != 0)
-        return;
-    const StreamArgs &a = g.descs[j];
-    if (a.meta[2] != 0) { // the scan gave up
-        if (lane == 0) {
-            if (x.route == 2)
-                build_verdict(x, i, kBiCorrupt);
-            else
-                build_to_walker(x, i);
-        }
-        return;
-    }
-    // (stream_head: meta[1] == h_out[i], meta[3] its blocks)
-    const uint64_t K = bi_blocks(x.h_out[i]);
-    bool off = false;
-    for (uint64_t k = 1 + lane; k < K; k += 64)
-        off = off || a.cuts[2 * k + 1] != k * kBiBlock;
-    const bool unaligned = __ballot(off) != 0;
-    if (!unaligned) {
-        uint64_t *e = x.index + x.first[i];
-        for (uint64_t k = 1 + lane; k < K; k += 64)
-            e[k] = a.cuts[2 * k];
-        if (lane == 0) {
-            e[0] = a.meta[0];
-            e[K] = x.h_in[i];
-        }
-    }
-    if (lane == 0)
-        build_verdict(x, i, unaligned ? kBiUnaligned : kBiBuilt);
-}
-
-// ---------------------------------------------------------------------
-// k_index_walk: bi_walk by one wavefront per listed stream, every lane the
-// same walk on wave-uniform values (scalar work; lane 0 stores).  The chain
-// is sequential - a hop needs the tag the hop before it led to - so the
-// wavefront is as fast as one dependent chain.
-// Measured on 256 streams of 1 MiB of text, walker alone (~221 000 hops a
-// stream, profiles/raw_index_build_walker.txt): 67.41 ms hopping through
-// memory, 67.55 ms with the input staged through 1 KiB windows in LDS (64
-// lanes x 16 bytes per refill, ds_read_u8 per hop) - 305 ns a hop either
-// way.  What a hop waits for is not its load (neighbouring tags share a cache
-// line) but the ~70 dependent scalar instructions and ten branches around it,
-// issued by a lone wavefront.  The windows bought nothing and are gone; what
-// would is fewer instructions per hop (k_bstream_scan's table of tags) or
-// its parallel entries, i.e. the scan route, which takes these streams first.
-// ---------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_index_walk(BuildArgs x)
-{
-    const uint32_t lane = threadIdx.x;
-    const uint64_t count = x.stat[4];
-    for (uint64_t w = blockIdx.x; w < count; w += gridDim.x) {
-        const uint32_t i = x.walk[w];
-        const gcptr in = (gcptr)x.in_ptrs[i];
-        const uint64_t in_len = x.h_in[i], dlen = x.h_out[i];
-        uint64_t *e = x.index + x.first[i];
-        const uint64_t cnt = bi_entries(dlen);
-        uint64_t announced = 0;
-        const uint32_t hdr = uni(
-            bi_header((const uint8_t *)x.in_ptrs[i], in_len, &announced));
-        int st = kBiCorrupt;
-        if (hdr != 0 && announced != dlen)
-            st = kBiMissized; // (k_index_build_plan has seen to it)
-        else if (hdr != 0)
-            st = bi_walk([in](uint64_t pos) { return uni(in[pos]); }, in_len,
-                         hdr, dlen, [e, lane](uint64_t k, uint64_t p) {
-                             if (lane == 0)
-                                 e[k] = p;
-                         });
-        if (st == kBiBuilt) {
-            if (lane == 0) {
-                e[0] = hdr;
-                e[cnt - 1] = in_len;
-            }
-        } else {
-            // (what the walk put before it knew)
-            __syncthreads();
-            for (uint64_t k = lane; k < cnt; k += 64)
-                e[k] = 0;
-        }
-        if (lane == 0)
-            build_verdict(x, i, st);
     }
 }
 

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "snapmi.h"
+#include "snapmi_piecelist.hpp"
 
 namespace snapmi {
 
@@ -155,6 +156,51 @@ __device__ __forceinline__ void set_error(snapmi_error *errs, uint64_t i,
         errs[i].b = b;
         errs[i].c = c;
     }
+}
+
+// Slot k of a piece-descriptor list (snapmi_piecelist.hpp) as whoever cuts
+// the pieces hands it to the batch decoder: these in_len bytes into this room
+// of cap bytes, mode m, nothing produced yet and no error.  piece_put stores
+// the error's kind alone (a decoder that reports another kind writes the other
+// fields beside it); piece_put_err a whole error of the caller's.
+__device__ __forceinline__ void piece_put_fields(const PieceList &l,
+                                                 uint64_t k, const void *in,
+                                                 uint64_t in_len, void *out,
+                                                 uint64_t cap, uint8_t mode)
+{
+    l.c_in[k] = in;
+    l.c_inlen[k] = in_len;
+    l.c_out[k] = out;
+    l.c_cap[k] = cap;
+    l.c_outlen[k] = 0;
+    l.c_mode[k] = mode;
+}
+
+__device__ __forceinline__ void piece_put(const PieceList &l, uint64_t k,
+                                          const void *in, uint64_t in_len,
+                                          void *out, uint64_t cap,
+                                          uint8_t mode)
+{
+    piece_put_fields(l, k, in, in_len, out, cap, mode);
+    l.c_err[k].kind = SNAPMI_OK;
+}
+
+__device__ __forceinline__ void piece_put_err(const PieceList &l, uint64_t k,
+                                              const void *in, uint64_t in_len,
+                                              void *out, uint64_t cap,
+                                              uint8_t mode,
+                                              const snapmi_error &err)
+{
+    piece_put_fields(l, k, in, in_len, out, cap, mode);
+    l.c_err[k] = err;
+}
+
+// The piece of slot k came out whole: it was the decoder's (mode 2), reports
+// OK and filled its room.
+__device__ __forceinline__ bool piece_whole(const PieceList &l, uint64_t k)
+{
+    return l.c_mode[k] == 2 && l.c_err[k].kind == SNAPMI_OK &&
+           l.c_outlen[k] == l.c_cap[k];
 }
 
 // reference bytes::read_varu64, src/bytes.rs:73-90 (returns header length,

@@ -1,5 +1,7 @@
 // snapmi_kernels.hpp -- kernel argument blocks and kernel declarations shared
-// between the .hip translation units and the host API.
+// between the .hip translation units and the host API.  (The kernels over the
+// block index and their argument blocks are local to the files that launch
+// them: snapmi_index.hip, snapmi_update.hip.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -278,18 +280,14 @@ struct StreamArgs {
     // handed, ~630 cycles a hop whoever else is on the chip
     // (stream_scan_segs in snapmi_streamplan.hpp)
     uint32_t scan_segs;
-    // piece descriptors for k_decompress_streams
-    const void **c_in;
-    unsigned long long *c_inlen;
-    void **c_out;
-    unsigned long long *c_cap;
-    unsigned long long *c_outlen;
-    snapmi_error *c_err;
-    uint8_t *c_mode;
+    // its piece descriptors, [kmax], for the batch decoder
+    PieceList c;
     // a long stream of a batch: where k_bstream_finish says whether the
     // launch behind it must decode the stream (0) or not (3); else nullptr
     uint8_t *fb_mode;
 };
+// (plan_streams sizes the descriptor block of a launch with it)
+static_assert(sizeof(StreamArgs) == 200, "StreamArgs sizes the descriptor block");
 // the long streams of a batch (a lone stream is a batch of one): their
 // descriptors and, per kernel, the first workgroup of every stream (nullptr:
 // one workgroup each)
@@ -334,126 +332,6 @@ __global__ void k_long_plan(const void *const *in_ptrs, const uint64_t *in_lens,
                             void *const *out_ptrs, const uint64_t *out_caps,
                             uint32_t n, uint64_t min_len, uint8_t *modes,
                             LongItem *list, uint32_t cap, uint32_t *count);
-
-// snapmi_decompress_batch_indexed (snapmi_blockindex.hpp): the batch, the
-// caller's index and the one descriptor list the batch decoder runs over -
-// slot i < n: stream i, slot n + e: index entry e as a piece.
-struct IndexArgs {
-    const void *const *in_ptrs;
-    const uint64_t *in_lens;
-    void *const *out_ptrs;
-    const uint64_t *out_caps;
-    uint64_t *out_lens;
-    snapmi_error *errs;    // [n] or nullptr
-    const uint64_t *first; // [n + 1]
-    const uint64_t *index; // [entries]
-    uint64_t entries;
-    uint32_t n;
-    // [n], of the launch behind the list over the caller's own arrays: 0 =
-    // an indexed stream whose pieces did not come out whole, 3 = any other
-    uint8_t *modes;
-    // [n + entries]
-    const void **c_in;
-    uint64_t *c_inlen;
-    void **c_out;
-    uint64_t *c_cap;
-    uint64_t *c_outlen;
-    snapmi_error *c_err;
-    uint8_t *c_mode;
-    uint32_t *c_owner; // [entries] the stream entry e is a piece of
-    // [0] = seq once a stream of this call is indexed, [1] streams delivered
-    // by pieces, [2] handed back, [3] = seq once one was handed back (what
-    // the launch behind waits for)
-    unsigned long long *gate;
-    unsigned long long seq;
-};
-__global__ void k_index_plan(IndexArgs x);
-__global__ void k_index_pieces(IndexArgs x);
-__global__ void k_index_finish(IndexArgs x);
-// snapmi_decompress_ranges_indexed (snapmi_blockindex.hpp): the streams, their
-// index, the ranges, and ONE GROUP of consecutive ranges [r0, r0 + mg) whose
-// pieces (host: `pieces`) and edge rooms (host: `rooms`) this round of
-// launches runs.  Slot j < pieces of the descriptor list is the j-th touched
-// block of the group in range order.
-struct RangeArgs {
-    const void *const *in_ptrs;
-    const uint64_t *in_lens;
-    const uint64_t *first; // [n + 1]
-    const uint64_t *index; // [entries]
-    uint64_t entries;
-    uint32_t n;
-    const uint32_t *r_stream; // [m], as are the next five
-    const uint64_t *r_off;
-    const uint64_t *r_len;
-    void *const *r_out;
-    uint64_t *r_got;
-    snapmi_error *r_errs; // or nullptr
-    uint32_t r0, mg;
-    uint64_t pieces, rooms; // what the host sized for this group
-    // [m]: first piece slot and first edge room of the range inside its group
-    // (exclusive scans of what the DEVICE arrays ask for), and its verdict:
-    // 0 failed or empty (got and err are written), 1 its pieces decide
-    uint64_t *slot, *eslot;
-    uint8_t *state;
-    uint64_t *part; // [2 * parts]: the scans' workgroup totals
-    uint8_t *room;  // [rooms * 64 KiB]
-    // [pieces]
-    const void **c_in;
-    uint64_t *c_inlen;
-    void **c_out;
-    uint64_t *c_cap;
-    uint64_t *c_outlen;
-    snapmi_error *c_err;
-    uint8_t *c_mode;
-    unsigned long long *stat; // [0] ranges that succeeded, [1] that failed
-};
-// pieces a range may ask for in the scan: more than any call holds
-constexpr uint64_t kRangeCountClamp = 1ull << 32;
-__global__ void k_range_scan_a(RangeArgs x);
-__global__ void k_range_scan_b(RangeArgs x, uint32_t nparts);
-__global__ void k_range_scan_c(RangeArgs x);
-__global__ void k_range_plan(RangeArgs x);
-__global__ void k_range_pieces(RangeArgs x);
-__global__ void k_range_finish(RangeArgs x);
-// snapmi_build_block_index (bi_build of snapmi_blockindex.hpp on the device):
-// the batch, the device's copies of the host's arrays - which size the index
-// and every launch and are trusted for nothing else -, and what the kernels
-// hand each other.
-struct BuildArgs {
-    const void *const *in_ptrs;
-    const uint64_t *in_lens; // the caller's
-    const uint64_t *h_in;    // [n] copies of h_in_lens, h_out_lens
-    const uint64_t *h_out;
-    const uint64_t *first;   // [n + 1] the prefix sum the host made
-    uint64_t *index;         // [first[n]], all 0 when k_index_build_plan runs
-    uint8_t *status;         // [n] or nullptr
-    uint32_t n;
-    // [n]: 0 = a stream of two blocks and more that awaits its walk (scan or
-    // k_index_walk), else its verdict
-    uint8_t *state;
-    // the streams k_index_walk walks, and the counters: [0..3] streams built,
-    // unaligned, corrupt, missized; [4] streams in `walk`
-    uint32_t *walk;
-    unsigned long long *stat;
-    // 0: pending streams are the scan's, those it gives up on the walker's;
-    // 1: all pending streams are the walker's; 2: the scan alone, what it
-    // gives up on is corrupt (test option "index_build_route")
-    uint32_t route;
-    // a pending stream longer than this is the walker's under every route
-    // (the scan's plan does not hold it)
-    uint64_t scan_max_len;
-};
-// one group of pending streams on the scan route: descriptors [mg] (as
-// launch_stream_chain takes them) and the batch's stream of each
-struct BuildGroup {
-    StreamArgs *descs;
-    const uint32_t *idx;
-    uint32_t mg;
-};
-__global__ void k_index_build_plan(BuildArgs x);
-__global__ void k_index_build_adopt(BuildArgs x, BuildGroup g);
-__global__ void k_index_build_entries(BuildArgs x, BuildGroup g);
-__global__ void k_index_walk(BuildArgs x);
 
 // snapmi_compress_batch_indexed: first[], then the entries
 __global__ void k_index_first(const uint64_t *in_lens, uint32_t n,

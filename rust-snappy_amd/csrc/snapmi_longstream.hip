@@ -79,14 +79,7 @@ void stream_pointers(snapmi_ctx *ctx, const StreamPlan &p, const StreamSlot &g,
     a.cuts = (unsigned long long *)(t + g.cuts);
     if (!ctx->sd_desc.p)
         return;
-    const PieceList l = piece_list(ctx->sd_desc.p, p.pieces);
-    a.c_in = l.c_in + g.entry;
-    a.c_inlen = (unsigned long long *)l.c_inlen + g.entry;
-    a.c_out = l.c_out + g.entry;
-    a.c_cap = (unsigned long long *)l.c_cap + g.entry;
-    a.c_outlen = (unsigned long long *)l.c_outlen + g.entry;
-    a.c_err = l.c_err + g.entry;
-    a.c_mode = l.c_mode + g.entry;
+    a.c = piece_list_from(piece_list(ctx->sd_desc.p, p.pieces), g.entry);
 }
 
 // The streams of plan `p`, whose descriptor block (descriptors, then the

@@ -5,9 +5,11 @@
 //   c_err [P]                                                snapmi_error
 //   c_mode [P]                                               a byte
 // The one host-side description of it: snapmi_streamplan.hpp sizes sd_desc
-// with it, the three callers turn a base address into pointers with it.
+// with it, the callers turn a base address into pointers with it, and every
+// argument block that carries a list holds one PieceList.
 // Plain functions, no HIP (tests/test_piecelist_cpu.py); the kernels never
-// compute these addresses, they are handed the pointers.
+// compute these addresses, they are handed the pointers and store and check a
+// slot through piece_put / piece_whole of snapmi_device.hpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -63,6 +65,22 @@ inline PieceList piece_list(void *base, size_t P)
     l.c_err = (snapmi_error *)(d + o.c_err);
     l.c_mode = d + o.c_mode;
     return l;
+}
+
+// the list of the slots of `l` from `first` on: a stream's own pieces inside
+// the slab of its plan
+inline PieceList piece_list_from(const PieceList &l, size_t first)
+{
+    PieceList s;
+    s.c_in = l.c_in + first;
+    s.c_inlen = l.c_inlen + first;
+    s.c_out = l.c_out + first;
+    s.c_cap = l.c_cap + first;
+    s.c_outlen = l.c_outlen + first;
+    // (snapmi_error is only named here)
+    s.c_err = (snapmi_error *)((uint8_t *)l.c_err + first * kPieceErrBytes);
+    s.c_mode = l.c_mode + first;
+    return s;
 }
 
 } // namespace snapmi

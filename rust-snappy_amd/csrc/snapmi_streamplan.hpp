@@ -103,7 +103,9 @@ struct StreamSlot {
     size_t entry; // its first piece in the descriptor arrays of sd_desc
 };
 
-struct StreamPlan {
+// Its PieceOffsets base lays out sd_desc: the piece descriptors of all
+// streams, an array per field (snapmi_piecelist.hpp).
+struct StreamPlan : PieceOffsets {
     uint32_t n;
     uint32_t seg_log2, scan_segs;
     bool fits; // every nseg and kmax under 2^30 (else nothing below is set)
@@ -111,10 +113,9 @@ struct StreamPlan {
     // sd_tables: the meta of all streams, the e-tables of all streams (one
     // 0xFF fill of e_bytes from e_off), then per stream s1, s2, s3, cuts
     size_t e_off, e_bytes, t_bytes;
-    // sd_desc: the piece descriptors of all streams, an array per field
-    // (snapmi_piecelist.hpp)
-    size_t pieces;
-    size_t c_in, c_inlen, c_out, c_cap, c_outlen, c_err, c_mode, d_bytes;
+    // sd_desc: `pieces` slots at the offsets of the base; d_bytes is its
+    // `total`, named like the other sizes to reserve
+    size_t pieces, d_bytes;
     // descriptor block: n descriptors of desc_size bytes, then the prefixes
     // [kPre][n + 1] (uint32_t)
     size_t pre_off, desc_bytes;
@@ -192,15 +193,8 @@ inline StreamPlan plan_streams(StreamSlot *slot, uint32_t n, bool lone,
         pre[k * st + n] = p.grid[k];
     p.t_bytes = t + 64;
 
-    const PieceOffsets o = piece_offsets(p.pieces);
-    p.c_in = o.c_in;
-    p.c_inlen = o.c_inlen;
-    p.c_out = o.c_out;
-    p.c_cap = o.c_cap;
-    p.c_outlen = o.c_outlen;
-    p.c_err = o.c_err;
-    p.c_mode = o.c_mode;
-    p.d_bytes = o.total;
+    static_cast<PieceOffsets &>(p) = piece_offsets(p.pieces);
+    p.d_bytes = p.total;
 
     p.pre_off = (size_t)n * desc_size;
     p.desc_bytes = p.pre_off + (size_t)kPre * st * sizeof(uint32_t);

@@ -3,7 +3,7 @@
 // (snapmi_append_indexed), kernels and host side.  Only the blocks an update
 // changes go through the codec; every other block keeps its compressed bytes
 // (snapmi_blockindex.hpp has the rules: bi_write_*, bi_append_*,
-// bi_update_groups).
+// bi_update_groups; what only reads an index is snapmi_index.hip).
 //
 // Both calls are one pipeline.  The host checks its own arrays, lists the
 // NAMED streams - those a write touches, those bytes are appended to - and
@@ -235,26 +235,13 @@ __device__ __forceinline__ void update_store_block(const UpdateArgs &x,
     x.z_inlen[j] = b.z_len;
     x.z_out[j] = slot;
     x.z_outlen[j] = 0;
-    if (r != 0xFFFFFFFFu) {
-        x.c.c_in[r] = b.p_in;
-        x.c.c_inlen[r] = b.p_inlen;
-        x.c.c_out[r] = b.p_out;
-        x.c.c_cap[r] = b.p_cap;
-        x.c.c_outlen[r] = 0;
-        set_error(x.c.c_err, r, SNAPMI_OK, 0, 0, 0);
-        x.c.c_mode[r] = b.mode;
-    }
+    if (r != 0xFFFFFFFFu)
+        piece_put_err(x.c, r, b.p_in, b.p_inlen, b.p_out, b.p_cap, b.mode,
+                      snapmi_error{SNAPMI_OK, 0, 0, 0, 0});
 }
 
-// the piece of room r came out: OK and full
-__device__ __forceinline__ bool update_piece_ok(const UpdateArgs &x,
-                                                uint32_t r)
-{
-    return x.c.c_mode[r] == 2 && x.c.c_err[r].kind == SNAPMI_OK &&
-           x.c.c_outlen[r] == x.c.c_cap[r];
-}
-
-// ... it did not: the stream fails with the piece's error (k: its block)
+// The piece of room r did not come out whole (piece_whole): the stream fails
+// with the piece's error (k: its block)
 __device__ __forceinline__ void update_piece_fail(const UpdateArgs &x,
                                                   uint32_t t, uint32_t s,
                                                   uint32_t r, uint64_t k)
@@ -262,7 +249,8 @@ __device__ __forceinline__ void update_piece_fail(const UpdateArgs &x,
     const snapmi_error e = x.c.c_err[r];
     if (e.kind != SNAPMI_OK)
         update_fail(x, t, s, e.kind, e.a, e.b, e.c);
-    // not reached, kept as the guard of an invariant (see k_range_finish): a
+    // not reached, kept as the guard of an invariant (see k_range_finish of
+    // snapmi_index.hip): a
     // mode-2 piece that reports OK is full
     else
         update_fail(x, t, s, SNAPMI_E_ARGUMENT, s, k, 0);
@@ -486,7 +474,7 @@ __global__ __launch_bounds__(256) void k_write_sizes(WriteArgs x)
     uint64_t bad = ~0ull;
     for (uint32_t i = threadIdx.x; i < nt && bad == ~0ull; i += blockDim.x) {
         const uint32_t r = x.tb_room[ba + i];
-        if (r != 0xFFFFFFFFu && !update_piece_ok(x, r))
+        if (r != 0xFFFFFFFFu && !piece_whole(x.c, r))
             bad = i;
     }
     bad = wave_min64(bad);
@@ -679,7 +667,7 @@ __global__ __launch_bounds__(256) void k_append_sizes(AppendArgs x)
     const uint32_t r = x.ns_room[t];
     const uint64_t dlen = x.ns_dlen[t];
     // the tail's piece
-    if (r != 0xFFFFFFFFu && !update_piece_ok(x, r)) {
+    if (r != 0xFFFFFFFFu && !piece_whole(x.c, r)) {
         if (threadIdx.x == 0)
             update_piece_fail(x, t, s, r, bi_append_full(dlen));
         return;

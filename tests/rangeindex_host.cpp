@@ -7,6 +7,8 @@
 //   U in_len hdr dlen first next total e...  -> 0 / 1    (e: the whole index)
 //   K in_len off len e...  -> first bad block, or 18446744073709551615
 //   P m off len ...        -> the pieces of m ranges, saturating
+//   G scratch m off len ...  -> groups max_pieces max_rooms, then r0 mg
+//                               pieces rooms of every group (bi_range_groups)
 // (it has a main of its own so that it can also be built with
 // -fsanitize=address,undefined and run as it is)
 #include <inttypes.h>
@@ -71,14 +73,32 @@ int main()
             printf("%" PRIu64 "\n",
                    bi_range_first_bad_block(a.data() + 3, a[0], a[1], a[2]));
         } else if (op == 'P' && a.size() >= 1 && a.size() == 1 + 2 * a[0]) {
-            uint64_t sum = 0;
+            std::vector<uint64_t> off(a[0]), len(a[0]);
             for (uint64_t r = 0; r < a[0]; r++) {
-                uint64_t k0;
-                const uint64_t c =
-                    bi_range_blocks(a[1 + 2 * r], a[2 + 2 * r], &k0);
-                sum = sum + c < sum ? ~0ull : sum + c;
+                off[r] = a[1 + 2 * r];
+                len[r] = a[2 + 2 * r];
             }
-            printf("%" PRIu64 "\n", sum);
+            printf("%" PRIu64 "\n",
+                   bi_range_pieces(off.data(), len.data(), off.size()));
+        } else if (op == 'G' && a.size() >= 2 && a.size() == 2 + 2 * a[1]) {
+            // (the arrays have exactly m places, the groups' as well)
+            const size_t m = (size_t)a[1];
+            std::vector<uint64_t> off(m), len(m);
+            for (size_t r = 0; r < m; r++) {
+                off[r] = a[2 + 2 * r];
+                len[r] = a[3 + 2 * r];
+            }
+            std::vector<BiRangeGroup> g(m);
+            BiRangeMax max;
+            const size_t count = bi_range_groups(off.data(), len.data(), m,
+                                                 a[0], g.data(), &max);
+            if (count > m)
+                return 3;
+            printf("%zu %" PRIu64 " %" PRIu64, count, max.pieces, max.rooms);
+            for (size_t i = 0; i < count; i++)
+                printf(" %u %u %" PRIu64 " %" PRIu64, g[i].r0, g[i].mg,
+                       g[i].pieces, g[i].rooms);
+            printf("\n");
         } else {
             return 2;
         }

@@ -22,10 +22,10 @@ SHAPES += [(0, d) for d in DLENS] + [(d - 1, 1) for d in DLENS if d]
 SHAPES += [(d, 0) for d in DLENS] + [(d, 1) for d in DLENS]
 
 
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("rangeindex") / "rangeindex_host"
+def build(tmp_path_factory, name, extra):
+    exe = tmp_path_factory.mktemp(name) / "rangeindex_host"
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror",
+                           *extra,
                            str(ROOT / "tests" / "rangeindex_host.cpp"),
                            "-o", str(exe)])
 
@@ -39,6 +39,11 @@ def prog(tmp_path_factory):
         assert len(rows) == len(lines)
         return rows
     return run
+
+
+@pytest.fixture(scope="module")
+def prog(tmp_path_factory):
+    return build(tmp_path_factory, "rangeindex", [])
 
 
 def draws(seed, count):
@@ -108,6 +113,63 @@ def test_pieces_sum_saturates(prog):
     for s, row in zip(sets, rows):
         assert row == [R.pieces([o for o, _ in s], [n for _, n in s])]
     assert rows[-1] == [U64 - 1]
+
+
+def test_groups(prog, tmp_path_factory):
+    """bi_range_groups, which snapmi_decompress_ranges_indexed cuts a call
+    with, against room_groups - the model the GPU tests count groups with -
+    and the pieces and rooms of every group summed from the per-range rules;
+    the same lines through a build with -fsanitize=address,undefined."""
+    floor, big = 128 << 10, 1 << 30
+    none, one, two, wide = (0, 65536), (1, 10), (65535, 2), (1, 131072)
+    empty, wraps = (70000, 0), (U64 - 1, 2)
+    assert [R.edges(*r) for r in (none, one, two, wide, empty, wraps)] == \
+        [0, 1, 2, 2, 0, 0]
+    lists = [
+        [],
+        [none, one, two, wide, empty, wraps],
+        [wraps, empty, wide, none, two, one, one, none, empty, two],
+        [one, one, one],              # a group closes exactly when full
+        [one, none, one, empty, one, one, two],
+        [two, one, one, one],         # the first range alone fills the floor
+        [wide, wide, none, wide],
+        [none] * 5, [empty] * 3, [wraps],
+        [(1000, 189000)] * 3 + [(0, 1 << 20), (5, (1 << 20) + 7)],
+    ]
+    lists += [[r] for r in (none, one, two, wide, empty, wraps)]   # m = 1
+    rng = random.Random(20261020)
+    for _ in range(300):
+        lists.append(rng.choices([none, one, two, wide, empty, wraps]
+                                 + draws(rng.randrange(1 << 30), 12),
+                                 k=rng.randrange(1, 41)))
+    cases = [(sc, rs) for rs in lists for sc in (floor, big)]
+    # (a few at scratch sizes in between, a partial room included)
+    cases += [(sc, rs) for rs in lists[:40] for sc in (3 * 65536, 327679)]
+    lines, want = [], []
+    for sc, rs in cases:
+        offs, lens = [o for o, _ in rs], [n for _, n in rs]
+        lines.append(f"G {sc} {len(rs)} " + " ".join(f"{o} {n}"
+                                                     for o, n in rs))
+        groups = R.room_groups(offs, lens, sc)
+        rows = [(g[0], len(g), sum(R.blocks(*rs[r])[0] for r in g),
+                 sum(R.edges(*rs[r]) for r in g)) for g in groups]
+        assert [r for g in groups for r in g] == list(range(len(rs)))
+        want.append([len(rows), max([q[2] for q in rows], default=0),
+                     max([q[3] for q in rows], default=0),
+                     *[v for q in rows for v in q]])
+    got = prog(lines)
+    assert got == want
+    sanitized = build(tmp_path_factory, "rangeindex_sanitized",
+                      ["-g", "-fsanitize=address,undefined",
+                       "-fno-sanitize-recover=all"])
+    assert sanitized(lines) == want
+    # what the lists were chosen for, at the floor
+    by = {(sc, tuple(rs)): w for (sc, rs), w in zip(cases, want)}
+    assert by[floor, (one, one, one)] == [2, 2, 2, 0, 2, 2, 2, 2, 1, 1, 1]
+    assert by[floor, (two, one, one, one)][:3] == [3, 2, 2]
+    assert by[floor, (two, one, one, one)][3:7] == [0, 1, 2, 2]
+    assert by[big, (two, one, one, one)] == [1, 5, 5, 0, 4, 5, 5]
+    assert by[floor, (wraps,)] == [1, 0, 0, 0, 1, 0, 0]
 
 
 def test_local_index_rule(prog):

@@ -3446,93 +3446,4 @@ __global__ __launch_bounds__(256) void k_compact(CompressArgs a)
         to[head + body + threadIdx.x] = from[head + body + threadIdx.x];
 }
 
-// ---------------------------------------------------------------------
-// The block index of snapmi_compress_batch_indexed (snapmi_blockindex.hpp):
-// first[] is the exclusive scan of the streams' entry counts - on one
-// workgroup, or as wg_scan_a, _b, _c like the scans above -, and behind
-// everything else of the batch one thread per entry reads what the compressor
-// already knows: the varint's length, blk_off, the stream's length.
-// ---------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_index_first(const uint64_t *in_lens,
-                                                      uint32_t n,
-                                                      uint64_t *first)
-{
-    uint64_t carry[1] = {0};
-    wg_scan_strided(
-        n, carry,
-        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = bi_entries(in_lens[i]); },
-        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
-            first[i] = ex[0];
-        });
-    if (threadIdx.x == 0)
-        first[n] = carry[0];
-}
-
-__global__ __launch_bounds__(1024) void k_index_first_a(
-    const uint64_t *in_lens, uint32_t n, uint64_t *first, uint64_t *part)
-{
-    wg_scan_a<uint64_t, 1>(
-        n, part,
-        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = bi_entries(in_lens[i]); },
-        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
-            first[i] = ex[0];
-        });
-}
-
-__global__ __launch_bounds__(1024) void k_index_first_b(uint32_t n,
-                                                        uint64_t *first,
-                                                        uint64_t *part,
-                                                        uint32_t nparts)
-{
-    uint64_t carry[1] = {0};
-    wg_scan_b(part, nparts, carry);
-    if (threadIdx.x == 0)
-        first[n] = carry[0];
-}
-
-__global__ __launch_bounds__(1024) void k_index_first_c(uint32_t n,
-                                                        uint64_t *first,
-                                                        const uint64_t *part)
-{
-    wg_scan_c<uint64_t, 1>(
-        n, part,
-        [&](uint32_t i, const uint64_t (&off)[1]) { first[i] += off[0]; });
-}
-
-// Entry j of stream st: the varint's length plus the compressed bytes of the
-// stream's blocks in front of block j.  A stream without blocks of its own
-// (empty: the one entry {1}; under small_limit: the lane-per-stream kernels')
-// has the varint's length and its compressed length; a stream that failed
-// (out_lens 0) has zeros.
-__global__ __launch_bounds__(256) void k_block_index(CompressArgs a,
-                                                     const uint64_t *first,
-                                                     uint64_t *index,
-                                                     uint64_t entries)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= entries || e >= first[a.n_streams])
-        return;
-    const uint32_t st = bi_find_stream(first, a.n_streams, e);
-    const uint64_t j = e - first[st];
-    const uint64_t len = a.in_lens[st], out_len = a.out_lens[st];
-    const uint64_t last = bi_entries(len) - 1;
-    const uint32_t fb = a.blk_first[st];
-    const uint32_t nb = a.blk_first[st + 1] - fb;
-    uint64_t v = 0;
-    if (out_len != 0 && j <= last) {
-        const uint32_t vl = varint_len(len);
-        if (j == 0)
-            v = vl;
-        else if (j == last)
-            v = out_len;
-        // (a middle entry: the stream has last >= 2 blocks, and one that
-        // succeeded - out_len != 0 - was given exactly `last` blocks inside
-        // the launch by k_plan_compress, which rejects any other; the test
-        // is the bound of the read, never the reason for a 0)
-        else if (j < nb && (uint64_t)fb + nb <= a.host_blocks)
-            v = vl + (a.blk_off[fb + j] - a.blk_off[fb]);
-    }
-    index[e] = v;
-}
-
 } // namespace snapmi

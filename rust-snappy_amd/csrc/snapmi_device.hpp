@@ -30,6 +30,9 @@ constexpr uint32_t kSlotBytes = 76496;
 typedef __attribute__((address_space(1))) uint8_t g_u8;
 typedef g_u8 *gptr;        // global (HBM) bytes
 typedef const g_u8 *gcptr; // global (HBM) bytes, read only
+typedef __attribute__((address_space(3))) uint8_t l_u8; // LDS
+typedef __attribute__((address_space(3))) uint16_t l_u16x;
+typedef __attribute__((address_space(3))) uint32_t l_u32;
 typedef __attribute__((address_space(3))) uint16_t l_u16;
 typedef l_u16 *lptr16; // LDS u16
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

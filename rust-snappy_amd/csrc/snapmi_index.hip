@@ -2,11 +2,13 @@
 // host side: indexed decode (snapmi_decompress_batch_indexed), range reads
 // (snapmi_decompress_ranges_indexed) and the index of streams that came
 // without one (snapmi_build_block_index); each family of kernels and its
-// argument block stand in front of the entry point that launches them.  What
-// CHANGES an index - range writes and appends - is snapmi_update.hip; the
-// rules of both are snapmi_blockindex.hpp.  The kernels decode nothing: they
-// cut pieces into a descriptor list (snapmi_piecelist.hpp; piece_put and
-// piece_whole of snapmi_device.hpp) which the batch decoder runs over.
+// argument block stand in front of the entry point that launches them.  Last
+// in the file, what WRITES the index of a batch as it is compressed
+// (snapmi_compress_batch_indexed: launch_block_index, which launch_compress
+// calls).  What CHANGES an index - range writes and appends - is
+// snapmi_update.hip; the rules of all are snapmi_blockindex.hpp.  The readers
+// decode nothing: they cut pieces into a descriptor list (snapmi_piecelist.hpp;
+// piece_put, piece_whole of snapmi_device.hpp) which the batch decoder runs over.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -1083,16 +1085,8 @@ int snapmi_build_block_index(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         }
         StreamArgs *const descs = (StreamArgs *)ctx->pin_ibg[q].p;
         for (uint32_t j = 0; j < mg; j++) {
-            StreamArgs &a = descs[j];
-            const StreamSlot &t = slots[g.j0 + j];
-            memset(&a, 0, sizeof a);
-            a.in = nullptr; // (k_index_build_adopt)
-            a.in_len = t.in_len;
-            // no output exists: stream_head only asks that dlen fits
-            a.out = nullptr;
-            a.out_cap = t.bound;
-            stream_pointers(ctx, p, t, a);
-            a.c = PieceList{}; // no piece descriptors: nothing is decoded
+            // (cuts only: the scan's streams have no ends and no pieces)
+            descs[j] = stream_desc(ctx, p, slots[g.j0 + j], nullptr);
         }
         uint8_t *const blk = (uint8_t *)descs;
         memcpy(blk + p.pre_off, pres[gi].data(),
@@ -1132,3 +1126,126 @@ int snapmi_build_block_index(snapmi_ctx *ctx, const void *const *d_in_ptrs,
 }
 
 } // extern "C"
+
+namespace snapmi {
+
+// ---------------------------------------------------------------------
+// The block index of snapmi_compress_batch_indexed (snapmi_blockindex.hpp):
+// first[] is the exclusive scan of the streams' entry counts - on one
+// workgroup, or as wg_scan_a, _b, _c like the scans above -, and behind
+// everything else of the batch one thread per entry reads what the compressor
+// already knows: the varint's length, blk_off, the stream's length.
+// ---------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_index_first(const uint64_t *in_lens,
+                                                      uint32_t n,
+                                                      uint64_t *first)
+{
+    uint64_t carry[1] = {0};
+    wg_scan_strided(
+        n, carry,
+        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = bi_entries(in_lens[i]); },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            first[i] = ex[0];
+        });
+    if (threadIdx.x == 0)
+        first[n] = carry[0];
+}
+
+__global__ __launch_bounds__(1024) void k_index_first_a(
+    const uint64_t *in_lens, uint32_t n, uint64_t *first, uint64_t *part)
+{
+    wg_scan_a<uint64_t, 1>(
+        n, part,
+        [&](uint32_t i, uint64_t (&x)[1]) { x[0] = bi_entries(in_lens[i]); },
+        [&](uint32_t i, const uint64_t (&)[1], const uint64_t (&ex)[1]) {
+            first[i] = ex[0];
+        });
+}
+
+__global__ __launch_bounds__(1024) void k_index_first_b(uint32_t n,
+                                                        uint64_t *first,
+                                                        uint64_t *part,
+                                                        uint32_t nparts)
+{
+    uint64_t carry[1] = {0};
+    wg_scan_b(part, nparts, carry);
+    if (threadIdx.x == 0)
+        first[n] = carry[0];
+}
+
+__global__ __launch_bounds__(1024) void k_index_first_c(uint32_t n,
+                                                        uint64_t *first,
+                                                        const uint64_t *part)
+{
+    wg_scan_c<uint64_t, 1>(
+        n, part,
+        [&](uint32_t i, const uint64_t (&off)[1]) { first[i] += off[0]; });
+}
+
+// Entry j of stream st: the varint's length plus the compressed bytes of the
+// stream's blocks in front of block j.  A stream without blocks of its own
+// (empty: the one entry {1}; under small_limit: the lane-per-stream kernels')
+// has the varint's length and its compressed length; a stream that failed
+// (out_lens 0) has zeros.
+__global__ __launch_bounds__(256) void k_block_index(CompressArgs a,
+                                                     const uint64_t *first,
+                                                     uint64_t *index,
+                                                     uint64_t entries)
+{
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= entries || e >= first[a.n_streams])
+        return;
+    const uint32_t st = bi_find_stream(first, a.n_streams, e);
+    const uint64_t j = e - first[st];
+    const uint64_t len = a.in_lens[st], out_len = a.out_lens[st];
+    const uint64_t last = bi_entries(len) - 1;
+    const uint32_t fb = a.blk_first[st];
+    const uint32_t nb = a.blk_first[st + 1] - fb;
+    uint64_t v = 0;
+    if (out_len != 0 && j <= last) {
+        const uint32_t vl = varint_len(len);
+        if (j == 0)
+            v = vl;
+        else if (j == last)
+            v = out_len;
+        // (a middle entry: the stream has last >= 2 blocks, and one that
+        // succeeded - out_len != 0 - was given exactly `last` blocks inside
+        // the launch by k_plan_compress, which rejects any other; the test
+        // is the bound of the read, never the reason for a 0)
+        else if (j < nb && (uint64_t)fb + nb <= a.host_blocks)
+            v = vl + (a.blk_off[fb + j] - a.blk_off[fb]);
+    }
+    index[e] = v;
+}
+
+// first[], then a thread per entry, behind every scan of the batch: plan_part
+// is free again
+void launch_block_index(snapmi_ctx *ctx, const CompressArgs &a,
+                        uint64_t *d_index_first, uint64_t *d_index,
+                        uint64_t index_entries)
+{
+    hipStream_t s = ctx->stream;
+    const uint32_t n = a.n_streams;
+    uint64_t *part = (uint64_t *)ctx->plan_part.p;
+    launch_scan(
+        n,
+        [&] {
+            hipLaunchKernelGGL(k_index_first, dim3(1), dim3(1024), 0, s,
+                               a.in_lens, n, d_index_first);
+        },
+        [&](uint32_t parts) {
+            hipLaunchKernelGGL(k_index_first_a, dim3(parts), dim3(1024), 0, s,
+                               a.in_lens, n, d_index_first, part);
+            hipLaunchKernelGGL(k_index_first_b, dim3(1), dim3(1024), 0, s, n,
+                               d_index_first, part, parts);
+            hipLaunchKernelGGL(k_index_first_c, dim3(parts), dim3(1024), 0, s,
+                               n, d_index_first, part);
+        });
+    if (index_entries)
+        hipLaunchKernelGGL(k_block_index,
+                           dim3((uint32_t)((index_entries + 255) / 256)),
+                           dim3(256), 0, s, a, d_index_first, d_index,
+                           index_entries);
+}
+
+} // namespace snapmi

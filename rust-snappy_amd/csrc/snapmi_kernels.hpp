@@ -1,7 +1,8 @@
-// snapmi_kernels.hpp -- kernel argument blocks and kernel declarations shared
-// between the .hip translation units and the host API.  (The kernels over the
-// block index and their argument blocks are local to the files that launch
-// them: snapmi_index.hip, snapmi_update.hip.)
+// snapmi_kernels.hpp -- the codec's own kernels, as their launchers see them:
+// CompressArgs, the token constants, DecompressArgs and the declarations of
+// the kernels of snapmi_compress.hip and snapmi_decompress.hip.  (Every other
+// kernel is local to the file that launches it: snapmi_longstream.hip,
+// snapmi_index.hip, snapmi_update.hip.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,7 +11,6 @@
 #include "snapmi.h"
 #include "snapmi_tiny.hpp"
 #include "snapmi_profile.hpp"
-#include "snapmi_streamplan.hpp"
 #include "snapmi_blockindex.hpp"
 
 namespace snapmi {
@@ -96,7 +96,7 @@ struct CompressArgs {
     // _c in k_plan_compress_*, k_scan_sizes_*): a workgroup's totals, then
     // its offsets, one per 1024 streams / blocks; scan_part[parts] parks the
     // carry from the segment in front.  The same memory: the scans of a
-    // batch run one behind the other (k_index_first_* takes it last)
+    // batch run one behind the other (launch_block_index takes it last)
     uint2 *plan_part;
     unsigned long long *scan_part;
     // streams of 1 .. small_limit - 1 bytes get no blocks: k_compress_tiny
@@ -186,7 +186,7 @@ struct DecompressArgs {
     uint64_t *out_lens;
     snapmi_error *errs; // [n] or nullptr
     // optional [n]: 1 = stored chunk (frame type 0x01): plain copy of the
-    // input; 2 = headerless piece of a long stream (k_bstream_pieces):
+    // input; 2 = headerless piece of a long stream (snapmi_longstream.hip):
     // elements only, out_caps[i] is the exact output length; 3 = not this
     // launch's (a long stream of a batch, decoded through its pieces):
     // nothing is read, nothing written
@@ -247,103 +247,6 @@ __global__ void k_encode_tokens(CompressArgs a);
 __global__ void k_scan_sizes(CompressArgs a);
 __global__ void k_compact(CompressArgs a);
 __global__ void k_stream_lens(CompressArgs a);
-
-// One long raw stream decoded by many wavefronts (snapmi_decompress_stream,
-// and the long streams of a small batch): the constants and the plan of the
-// launches are snapmi_streamplan.hpp's.
-struct StreamArgs {
-    const uint8_t *in;
-    unsigned long long in_len;
-    uint8_t *out;
-    unsigned long long out_cap;
-    unsigned long long *out_len; // [1]
-    snapmi_error *err;           // [1]
-    // meta[0] header bytes, [1] decoded length, [2] 0 = pieces decode it,
-    // 1 = the sequential decoder must (error, or a stream whose pieces are
-    // not independent), [3] pieces
-    unsigned long long *meta;
-    // per level (4 KiB, 256 KiB, 16 MiB blocks): tables of (exit, produced)
-    // per entry offset < kEntry - level 1 [segments * kEntry], levels 2 and 3
-    // [blocks * 64 children * 64] - and entries [blocks] of (position,
-    // produced) where the chain enters each block (~0 = it does not)
-    unsigned long long *s1, *s2, *s3;
-    unsigned long long *e1, *e2, *e3;
-    unsigned long long *cuts;     // [(kmax + 1) * 2] (src, dst) of piece k
-    uint32_t nseg, nsuper, nsuper3, kmax;
-    // log2 of the segment size of this call (12 = kSeg; 10 for streams that
-    // are short enough for the scan to be a wait for its longest walk: a
-    // quarter of the hops per lane, four times the lanes - round 5)
-    uint32_t seg_log2;
-    // segments a wavefront of k_bstream_scan owns: kScanSegs when that still
-    // makes kScanFill wavefronts, fewer (a power of two from 8) when it does
-    // not - a scan wavefront is as slow as the chain of walks its lanes are
-    // handed, ~630 cycles a hop whoever else is on the chip
-    // (stream_scan_segs in snapmi_streamplan.hpp)
-    uint32_t scan_segs;
-    // its piece descriptors, [kmax], for the batch decoder
-    PieceList c;
-    // a long stream of a batch: where k_bstream_finish says whether the
-    // launch behind it must decode the stream (0) or not (3); else nullptr
-    uint8_t *fb_mode;
-};
-// (plan_streams sizes the descriptor block of a launch with it)
-static_assert(sizeof(StreamArgs) == 200, "StreamArgs sizes the descriptor block");
-// the long streams of a batch (a lone stream is a batch of one): their
-// descriptors and, per kernel, the first workgroup of every stream (nullptr:
-// one workgroup each)
-struct BatchStreams {
-    const StreamArgs *descs;
-    const uint32_t *pre; // [n + 1]
-    uint32_t n;
-};
-// Is a raw stream of `len` compressed bytes that announces `dl` bytes of
-// output worth cutting into pieces (ten small launches, ~0.5 ms, instead of
-// one wavefront at 0.14 GiB/s of elements or 0.85 GB/s of literal bytes)?
-// From min_len (32 KiB) on when it expands by half and fills a piece and a
-// half; from 256 KiB on whatever it holds (profiles/r4_scalar_latency.txt).
-__host__ __device__ inline bool long_stream_rule(unsigned long long len,
-                                                 unsigned long long dl,
-                                                 unsigned long long min_len)
-{
-    const bool sane = dl / 22 <= len && 2 * dl >= 3ull * kStreamChunk;
-    return sane && len >= min_len &&
-           (2 * dl >= 3 * len || len >= (256ull << 10));
-}
-struct LongItem { // what k_long_plan hands to the host
-    uint32_t idx, pad;
-    unsigned long long in_len, dlen;
-    const void *in;
-    void *out;
-    unsigned long long out_cap;
-};
-#define SNAPMI_STREAM_KERNEL_DECL(name)                                       \
-    __global__ void k_bstream_##name(BatchStreams b);
-SNAPMI_STREAM_KERNEL_DECL(head)
-SNAPMI_STREAM_KERNEL_DECL(scan)
-SNAPMI_STREAM_KERNEL_DECL(super)
-SNAPMI_STREAM_KERNEL_DECL(super3)
-SNAPMI_STREAM_KERNEL_DECL(chain)
-SNAPMI_STREAM_KERNEL_DECL(spread3)
-SNAPMI_STREAM_KERNEL_DECL(spread2)
-SNAPMI_STREAM_KERNEL_DECL(cuts)
-SNAPMI_STREAM_KERNEL_DECL(pieces)
-SNAPMI_STREAM_KERNEL_DECL(finish)
-__global__ void k_long_plan(const void *const *in_ptrs, const uint64_t *in_lens,
-                            void *const *out_ptrs, const uint64_t *out_caps,
-                            uint32_t n, uint64_t min_len, uint8_t *modes,
-                            LongItem *list, uint32_t cap, uint32_t *count);
-
-// snapmi_compress_batch_indexed: first[], then the entries
-__global__ void k_index_first(const uint64_t *in_lens, uint32_t n,
-                              uint64_t *first);
-__global__ void k_index_first_a(const uint64_t *in_lens, uint32_t n,
-                                uint64_t *first, uint64_t *part);
-__global__ void k_index_first_b(uint32_t n, uint64_t *first, uint64_t *part,
-                                uint32_t nparts);
-__global__ void k_index_first_c(uint32_t n, uint64_t *first,
-                                const uint64_t *part);
-__global__ void k_block_index(CompressArgs a, const uint64_t *first,
-                              uint64_t *index, uint64_t entries);
 
 __global__ void k_plan_decompress(DecompressArgs a);
 __global__ void k_plan_decompress_a(DecompressArgs a);

@@ -173,18 +173,6 @@ int snapmi_compress_batch_indexed(snapmi_ctx *ctx,
 
 namespace snapmi {
 
-// A scan of n items (snapmi_scan.hpp): one() launches the one-workgroup
-// kernel, three(parts) the (a) (b) (c) kernels over `parts` workgroups of 1024
-// items, for more than kPlanOneWg of them.
-template <class One, class Three>
-static void launch_scan(size_t n, One one, Three three)
-{
-    if (n > kPlanOneWg)
-        three((uint32_t)((n + 1023) / 1024));
-    else
-        one();
-}
-
 // k_scan_sizes over the blocks [a.blk_lo, min(a.blk_hi, host_blocks))
 static void launch_scan_sizes(const CompressArgs &a, hipStream_t s)
 {
@@ -615,31 +603,9 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         hipLaunchKernelGGL(k_compact, dim3((uint32_t)blocks), dim3(256), 0,
                            s, a);
     }
-    // the block index: first[], then a thread per entry (plan_part is free
-    // again: every scan of the batch is done)
-    if (d_index_first) {
-        uint64_t *part = (uint64_t *)ctx->plan_part.p;
-        launch_scan(
-            n,
-            [&] {
-                hipLaunchKernelGGL(k_index_first, dim3(1), dim3(1024), 0, s,
-                                   d_in_lens, (uint32_t)n, d_index_first);
-            },
-            [&](uint32_t parts) {
-                hipLaunchKernelGGL(k_index_first_a, dim3(parts), dim3(1024), 0,
-                                   s, d_in_lens, (uint32_t)n, d_index_first,
-                                   part);
-                hipLaunchKernelGGL(k_index_first_b, dim3(1), dim3(1024), 0, s,
-                                   (uint32_t)n, d_index_first, part, parts);
-                hipLaunchKernelGGL(k_index_first_c, dim3(parts), dim3(1024), 0,
-                                   s, (uint32_t)n, d_index_first, part);
-            });
-        if (index_entries)
-            hipLaunchKernelGGL(k_block_index,
-                               dim3((uint32_t)((index_entries + 255) / 256)),
-                               dim3(256), 0, s, a, d_index_first, d_index,
-                               index_entries);
-    }
+    // the block index, behind every scan of the batch
+    if (d_index_first)
+        launch_block_index(ctx, a, d_index_first, d_index, index_entries);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[3], s));
     HIP_TRY(ctx, hipGetLastError());
     ctx->timing_valid = true;

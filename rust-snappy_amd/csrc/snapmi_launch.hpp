@@ -6,13 +6,12 @@
 
 #include "snapmi_ctx.hpp"
 #include "snapmi_piecelist.hpp"
+#include "snapmi_streamplan.hpp"
 
 namespace snapmi {
 
 struct RouteOptions;            // snapmi_route.hpp
-struct StreamPlan;              // snapmi_streamplan.hpp
-struct StreamSlot;
-struct StreamArgs;              // snapmi_kernels.hpp
+struct CompressArgs;            // snapmi_kernels.hpp
 
 static_assert(sizeof(snapmi_error) == kPieceErrBytes,
               "snapmi_piecelist.hpp sizes the piece descriptors with it");
@@ -28,6 +27,17 @@ static_assert(sizeof(snapmi_error) == kPieceErrBytes,
 // batches of up to this many streams / blocks are planned and scanned by one
 // workgroup (one launch instead of three)
 constexpr size_t kPlanOneWg = 16384;
+// A scan of n items (snapmi_scan.hpp): one() launches the one-workgroup
+// kernel, three(parts) the (a) (b) (c) kernels over `parts` workgroups of 1024
+// items, for more than kPlanOneWg of them.
+template <class One, class Three>
+inline void launch_scan(size_t n, One one, Three three)
+{
+    if (n > kPlanOneWg)
+        three((uint32_t)((n + 1023) / 1024));
+    else
+        one();
+}
 
 // pinned host staging of a context (grow-only): pageable copies go through
 // the runtime's own staging buffer one at a time, process-wide - eight
@@ -71,6 +81,11 @@ void free_lane_tables(snapmi_ctx *ctx);
 int place_lane_tables(snapmi_ctx *ctx, uint32_t lanes, bool top_of_memory);
 int prepare_lane_tables(snapmi_ctx *ctx, uint64_t blocks, bool top);
 
+// snapmi_index.hip: the block index of the batch launch_compress compressed
+void launch_block_index(snapmi_ctx *ctx, const CompressArgs &a,
+                        uint64_t *d_index_first, uint64_t *d_index,
+                        uint64_t index_entries);
+
 // snapmi_launch.hip
 RouteOptions route_options(const snapmi_ctx *ctx);
 // raw compress of n streams; blocks/slots = launch geometry computed from
@@ -110,8 +125,16 @@ inline int launch_pieces(snapmi_ctx *ctx, const PieceList &l, size_t count,
 
 // snapmi_longstream.hip
 size_t long_stream_min();
-void stream_pointers(snapmi_ctx *ctx, const StreamPlan &p, const StreamSlot &g,
-                     StreamArgs &a);
+// a stream's own ends, as its descriptor holds them (StreamArgs)
+struct StreamEnds {
+    const void *in;
+    void *out;
+    uint64_t out_cap, *out_len;
+    snapmi_error *err;
+    uint8_t *fb_mode; // a long stream of a batch, else nullptr
+};
+StreamArgs stream_desc(snapmi_ctx *ctx, const StreamPlan &p,
+                       const StreamSlot &g, const StreamEnds *io);
 int launch_stream_cuts(snapmi_ctx *ctx, const StreamPlan &p, const void *dev);
 
 } // namespace snapmi

@@ -2,15 +2,23 @@
 // pieces: the k_bstream_* kernels) for one raw stream or the long streams of
 // a small batch: geometry, workgroups, and where every table and descriptor
 // lies in the scratch.  Plain functions, no HIP, so that
-// tests/test_streamplan_cpu.py can pin them on the CPU.  Its users in the
-// library: snapmi_longstream.hip (snapmi_decompress_stream,
-// decompress_batch_long) and snapmi_index.hip (snapmi_build_block_index); the
-// kernels see the constants through snapmi_kernels.hpp.
+// tests/test_streamplan_cpu.py can pin them on the CPU; with them what the
+// launches are handed (StreamArgs, BatchStreams) and the rule that sends a
+// stream this way (long_stream_rule; LongItem).  Its users in the library:
+// snapmi_longstream.hip (the kernels, snapmi_decompress_stream,
+// decompress_batch_long), snapmi_index.hip (snapmi_build_block_index) and
+// snapmi_api.hip (the rule, for the scalar calls).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #include "snapmi_piecelist.hpp"
+
+#if defined(__HIPCC__)
+#define SNAPMI_SP_HD __host__ __device__
+#else
+#define SNAPMI_SP_HD
+#endif
 
 namespace snapmi {
 
@@ -87,10 +95,80 @@ inline uint64_t lone_stream_bound(uint64_t in_len, uint64_t out_cap)
     return out_cap;
 }
 
+// Is a raw stream of `len` compressed bytes that announces `dl` bytes of
+// output worth cutting into pieces (ten small launches, ~0.5 ms, instead of
+// one wavefront at 0.14 GiB/s of elements or 0.85 GB/s of literal bytes)?
+// From min_len (32 KiB) on when it expands by half and fills a piece and a
+// half; from 256 KiB on whatever it holds (profiles/r4_scalar_latency.txt).
+SNAPMI_SP_HD inline bool long_stream_rule(unsigned long long len,
+                                          unsigned long long dl,
+                                          unsigned long long min_len)
+{
+    const bool sane = dl / 22 <= len && 2 * dl >= 3ull * kStreamChunk;
+    return sane && len >= min_len &&
+           (2 * dl >= 3 * len || len >= (256ull << 10));
+}
+struct LongItem { // what k_long_plan hands to the host
+    uint32_t idx, pad;
+    unsigned long long in_len, dlen;
+    const void *in;
+    void *out;
+    unsigned long long out_cap;
+};
+
 // the kernels with more than one workgroup per stream; the launch of each has
 // an exclusive prefix of its workgroups over the streams (BatchStreams::pre)
 enum StreamKernel { kPScan, kPSuper, kPSuper3, kPSpread3, kPSpread2, kPCuts,
                     kPPieces, kPre };
+
+// One long raw stream decoded by many wavefronts (snapmi_decompress_stream,
+// and the long streams of a small batch): what every k_bstream_* kernel is
+// handed of it.
+struct StreamArgs {
+    const uint8_t *in;
+    unsigned long long in_len;
+    uint8_t *out;
+    unsigned long long out_cap;
+    unsigned long long *out_len; // [1]
+    snapmi_error *err;           // [1]
+    // meta[0] header bytes, [1] decoded length, [2] 0 = pieces decode it,
+    // 1 = the sequential decoder must (error, or a stream whose pieces are
+    // not independent), [3] pieces
+    unsigned long long *meta;
+    // per level (4 KiB, 256 KiB, 16 MiB blocks): tables of (exit, produced)
+    // per entry offset < kEntry - level 1 [segments * kEntry], levels 2 and 3
+    // [blocks * 64 children * 64] - and entries [blocks] of (position,
+    // produced) where the chain enters each block (~0 = it does not)
+    unsigned long long *s1, *s2, *s3;
+    unsigned long long *e1, *e2, *e3;
+    unsigned long long *cuts;     // [(kmax + 1) * 2] (src, dst) of piece k
+    uint32_t nseg, nsuper, nsuper3, kmax;
+    // log2 of the segment size of this call (12 = kSeg; 10 for streams that
+    // are short enough for the scan to be a wait for its longest walk: a
+    // quarter of the hops per lane, four times the lanes - round 5)
+    uint32_t seg_log2;
+    // segments a wavefront of k_bstream_scan owns: kScanSegs when that still
+    // makes kScanFill wavefronts, fewer (a power of two from 8) when it does
+    // not - a scan wavefront is as slow as the chain of walks its lanes are
+    // handed, ~630 cycles a hop whoever else is on the chip
+    // (stream_scan_segs)
+    uint32_t scan_segs;
+    // its piece descriptors, [kmax], for the batch decoder
+    PieceList c;
+    // a long stream of a batch: where k_bstream_finish says whether the
+    // launch behind it must decode the stream (0) or not (3); else nullptr
+    uint8_t *fb_mode;
+};
+// (plan_streams sizes the descriptor block of a launch with it)
+static_assert(sizeof(StreamArgs) == 200, "StreamArgs sizes the descriptor block");
+// the long streams of a batch (a lone stream is a batch of one): their
+// descriptors and, per kernel, the first workgroup of every stream (nullptr:
+// one workgroup each)
+struct BatchStreams {
+    const StreamArgs *descs;
+    const uint32_t *pre; // [n + 1]
+    uint32_t n;
+};
 
 // One stream of a plan.  in_len and bound are the caller's; plan_streams
 // fills in the rest.

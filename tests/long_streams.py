@@ -241,7 +241,8 @@ def mixed(seed, nblocks, weights=MIX, tail_len=None, tail_kind="text"):
 
 
 def long_stream_rule(in_len, dlen, min_len=32 << 10):
-    """long_stream_rule of csrc/snapmi_kernels.hpp."""
+    """long_stream_rule of csrc/snapmi_streamplan.hpp
+    (test_streamplan_cpu.py holds the two against each other)."""
     sane = dlen // 22 <= in_len and 2 * dlen >= 3 * BLOCK
     return sane and in_len >= min_len and (2 * dlen >= 3 * in_len or
                                            in_len >= (256 << 10))

@@ -24,6 +24,14 @@ uint64_t t_lone_bound(uint64_t in_len, uint64_t out_cap)
 {
     return lone_stream_bound(in_len, out_cap);
 }
+// is the stream worth its pieces (the route of every scalar decode and of
+// every small batch)
+int t_long_stream_rule(uint64_t len, uint64_t dl, uint64_t min_len)
+{
+    return long_stream_rule(len, dl, min_len);
+}
+// what the library passes plan_streams as desc_size
+uint64_t t_desc_size(void) { return sizeof(StreamArgs); }
 // the constants: kSeg, kEntry, kSegPerSuper, kCutSegs, kScanSegs, kScanFill,
 // kStreamChunk, kPre
 void t_constants(uint64_t *out)

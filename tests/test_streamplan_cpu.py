@@ -2,8 +2,10 @@
 segment size, scan groups, the pieces of a lone stream, the workgroups of
 each launch and where every table and descriptor lies in the scratch, for a
 lone stream (snapmi_decompress_stream) and for the long streams of a batch
-(snapmi_decompress_batch).  The GPU suite checks the bytes these launches
-produce; here the arithmetic that sizes and places them."""
+(snapmi_decompress_batch); and the rule that sends a stream this way at all
+(long_stream_rule), held against its restatement in long_streams.py.  The
+GPU suite checks the bytes these launches produce; here the arithmetic that
+routes, sizes and places them."""
 import ctypes as C
 import random
 import subprocess
@@ -11,9 +13,11 @@ from pathlib import Path
 
 import pytest
 
+import long_streams as LS
+
 ROOT = Path(__file__).resolve().parent.parent
 KIB, MIB = 1 << 10, 1 << 20
-DESC = 176       # a descriptor's bytes: any multiple of 8 does for the plan
+DESC = 200       # a descriptor's bytes: sizeof(StreamArgs), see test_long_stream_rule
 NTOT, NSLOT = 25, 13
 PRE = ["scan", "super", "super3", "spread3", "spread2", "cuts", "pieces"]
 
@@ -35,6 +39,10 @@ def P(tmp_path_factory):
     L.t_plan.restype = C.c_int
     L.t_plan.argtypes = [u32, C.POINTER(u64), C.POINTER(u64), C.c_int, u32,
                          u32, u64]
+    L.t_long_stream_rule.restype = C.c_int
+    L.t_long_stream_rule.argtypes = [u64, u64, u64]
+    L.t_desc_size.restype = u64
+    L.t_desc_size.argtypes = []
     return L
 
 
@@ -310,3 +318,34 @@ def test_fixed_totals(P):
     assert p["t_bytes"] == 64 + 64 + (1025 + 18 * 64) * 128 + 1043 * 16 + \
         51 * 16
     assert p["d_bytes"] == 50 * 73 + 64
+
+
+def test_long_stream_rule(P):
+    """The C++ rule and long_streams.long_stream_rule agree around every edge
+    of the rule - min_len and 256 KiB of input; an expansion of 1.5, of 22,
+    and a piece and a half of output - and on seeded random pairs."""
+    assert DESC == P.t_desc_size()
+    min_len = 32 * KIB
+    # (the 1.5 edge decides only from 64 KiB of input on, below 256 KiB, and
+    # is hit exactly by an even length: 100 KiB)
+    lens = [min_len - 1, min_len, min_len + 1, 100 * KIB, 100 * KIB + 1,
+            256 * KIB - 1, 256 * KIB, 256 * KIB + 1, 3 * MIB]
+    pairs = []
+    for n in lens:
+        dls = {3 * 65536 // 2 + d for d in (-1, 0, 1)}
+        dls |= {(3 * n + 1) // 2 + d for d in (-2, -1, 0, 1)}
+        dls |= set(range(22 * n - 22, 22 * n + 23))
+        pairs += [(n, dl) for dl in sorted(dls)]
+    rng = random.Random(20261020)
+    for _ in range(2000):
+        pairs.append((rng.randrange(1 << 33), rng.randrange(1 << 33)))
+        pairs.append((int(2 ** rng.uniform(0, 33)), int(2 ** rng.uniform(0, 33))))
+    seen = set()
+    for n, dl in pairs:
+        want = LS.long_stream_rule(n, dl, min_len)
+        assert bool(P.t_long_stream_rule(n, dl, min_len)) == want, (n, dl)
+        seen.add(want)
+    assert seen == {True, False}
+    # the default of the restatement is the library's (long_stream_min)
+    assert LS.long_stream_rule(min_len, 3 * min_len) and \
+        not LS.long_stream_rule(min_len - 1, 3 * min_len)

@@ -77,6 +77,22 @@ extern "C" {
  *                          a test which streams fell through)
  *   "index_build_group_streams"  most streams in one group of its scan route
  *                          (1 .. 4096, default 4096)
+ *   "scratch_fill"         -1 (default): off.  0..255: waits for the context's
+ *                          streams (its own two and the host pipe's), then
+ *                          sets the whole capacity of every SCRATCH buffer of
+ *                          the context - device, pinned, the host pipe's
+ *                          slots (the classes: DESIGN 4.2b) - to that byte;
+ *                          kept buffers are not touched.  While it is not -1
+ *                          every new allocation of either class is filled
+ *                          with the byte before its owner sees it.  No result
+ *                          depends on it: tests/test_gpu_scratch.py.  The
+ *                          counters a call left for snapmi_ctx_get_info in
+ *                          such a buffer read as "no call yet" afterwards.
+ *                          snapmi_ctx_get_info (test build): what the last
+ *                          setting of 0..255 filled, "scratch_fill_buffers"
+ *                          and "scratch_fill_bytes", and how many of those
+ *                          buffers hold the byte in their first, middle and
+ *                          last position, "scratch_fill_seen"
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
  */
 SNAPMI_API int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,

@@ -24,6 +24,9 @@
 #include "snapmi_test.h"
 #include "snapmi_ctx.hpp"
 #include "snapmi_launch.hpp"
+#ifdef SNAPMI_TESTING
+#include "snapmi_hostpipe.hpp" // "scratch_fill" reaches the pipe's slots
+#endif
 #include "snapmi_device.hpp"
 #include "snapmi_kernels.hpp"
 
@@ -75,7 +78,7 @@ int release_batch_scratch(snapmi_ctx *ctx)
     if (!ctx->release_scratch)
         return SNAPMI_OK;
     for (DevBuf *b : {&ctx->tokens, &ctx->tok_pages, &ctx->tok_stage,
-                      &ctx->slots}) {
+                      &ctx->ntok, &ctx->sched, &ctx->slots}) {
         if (b->p) {
             HIP_TRY(ctx, hipFree(b->p));
             b->p = nullptr;
@@ -385,6 +388,73 @@ int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
 }
 
 #ifdef SNAPMI_TESTING
+// Test option "scratch_fill" 0..255: with every stream of the context idle,
+// the whole capacity of every scratch buffer (ScratchDev / ScratchPin of the
+// context, of its UpdateScratch and of the host pipe's slots) is set to the
+// byte; kept buffers are left alone.  Counters a call left in such a buffer
+// for snapmi_ctx_get_info are gone with it: they read as "no call yet".
+static int scratch_fill_now(snapmi_ctx *ctx, int byte)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
+    if (ctx->pipe) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe->s_in));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe->s_out));
+    }
+    std::vector<DevBuf *> dev;
+    std::vector<PinBuf *> pin;
+    for (DevBuf *b : ctx->dev_bufs)
+        dev.push_back(b);
+    for (PinBuf *b : ctx->pin_bufs)
+        pin.push_back(b);
+    if (ctx->pipe)
+        for (PipeSlot &sl : ctx->pipe->slot) {
+            for (DevBuf *b : {&sl.in, &sl.out, &sl.desc, &sl.home})
+                dev.push_back(b);
+            for (PinBuf *b : {&sl.hb_in, &sl.hb_home})
+                pin.push_back(b);
+        }
+    ctx->fill_buffers = ctx->fill_bytes = ctx->fill_seen = 0;
+    for (DevBuf *b : dev)
+        if (!b->kept && b->p)
+            HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (PinBuf *b : pin)
+        if (!b->kept && b->p)
+            memset(b->p, byte, b->cap);
+    ctx->rg_stats_live = ctx->ib_stats_live = false;
+    ctx->wr.stats_live = ctx->ap.stats_live = false;
+    ctx->fr_nowait_live = false;
+    // what was filled, and what of it reads back as filled: first, middle
+    // and last byte of every buffer
+    const uint8_t want = (uint8_t)byte;
+    for (DevBuf *b : dev) {
+        if (b->kept || !b->p)
+            continue;
+        ctx->fill_buffers++;
+        ctx->fill_bytes += b->cap;
+        bool ok = true;
+        for (size_t off : {(size_t)0, b->cap / 2, b->cap - 1}) {
+            uint8_t got = (uint8_t)~want;
+            HIP_TRY(ctx, hipMemcpy(&got, (const uint8_t *)b->p + off, 1,
+                                   hipMemcpyDeviceToHost));
+            ok = ok && got == want;
+        }
+        ctx->fill_seen += ok;
+    }
+    for (PinBuf *b : pin) {
+        if (b->kept || !b->p)
+            continue;
+        ctx->fill_buffers++;
+        ctx->fill_bytes += b->cap;
+        const volatile uint8_t *p = (const volatile uint8_t *)b->p;
+        ctx->fill_seen +=
+            p[0] == want && p[b->cap / 2] == want && p[b->cap - 1] == want;
+    }
+    return SNAPMI_OK;
+}
+
 // include/snapmi_test.h: knobs of the test suite and the experiment drivers
 // (libsnapmi_test.so only: the product library does not export it)
 int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
@@ -450,7 +520,12 @@ int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
     else if (strcmp(name, "host_batch_listed") == 0 && value >= 0 &&
              value <= 1)
         ctx->host_batch_listed = (int)value;
-    else
+    else if (strcmp(name, "scratch_fill") == 0 && value >= -1 &&
+             value <= 255) {
+        ctx->scratch_fill = (int)value;
+        if (value >= 0)
+            return scratch_fill_now(ctx, (int)value);
+    } else
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "unknown test option %s",
                         name);
     return SNAPMI_OK;
@@ -690,6 +765,12 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                                    sizeof w, hipMemcpyDeviceToHost));
         }
         *value = w;
+    } else if (strcmp(name, "scratch_fill_buffers") == 0) {
+        *value = (int64_t)ctx->fill_buffers;
+    } else if (strcmp(name, "scratch_fill_bytes") == 0) {
+        *value = (int64_t)ctx->fill_bytes;
+    } else if (strcmp(name, "scratch_fill_seen") == 0) {
+        *value = (int64_t)ctx->fill_seen;
 #endif
     } else if (strcmp(name, "token_pool_pct_now") == 0) {
         *value = ctx->token_pool_now;

@@ -6,6 +6,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -13,16 +14,38 @@
 
 namespace snapmi {
 
-struct DevBuf { // device scratch (grow-only)
+struct DevBuf { // device memory of a context (grow-only)
     void *p = nullptr;
     size_t cap = 0;
     bool listed = false; // in snapmi_ctx::dev_bufs (reserve)
+    bool kept = false;   // the class: KeptDev / ScratchDev below
 };
 
 struct PinBuf { // pinned, device-mapped host memory (grow-only)
     void *p = nullptr;
     size_t cap = 0;
     bool listed = false; // in snapmi_ctx::pin_bufs (pin_reserve)
+    bool kept = false;   // the class: KeptPin / ScratchPin below
+};
+
+// Every buffer is declared as one of two classes (the table: DESIGN 4.2b;
+// tests/test_scratch_classes_cpu.py holds the two together):
+//   Scratch*  every word a call reads was written earlier in the same call -
+//             by a memset or a copy on the call's stream, by the host, or by
+//             a kernel of the call.  What the buffer held before does not
+//             matter: the test build fills these with any byte between calls
+//             (test option "scratch_fill") and every result stays the same.
+//   Kept*     meaning survives a call.  The declaration says who initialises
+//             the buffer and when; a buffer that grows is initialised again.
+// reserve, pin_reserve and slot_reserve take the base type and see the class
+// in `kept`.
+struct ScratchDev : DevBuf {};
+struct KeptDev : DevBuf {
+    KeptDev() { kept = true; }
+};
+struct ScratchPin : PinBuf {};
+struct KeptPin : PinBuf {
+    KeptPin() { kept = true; }
 };
 
 // What a range write, or an append, of indexed streams keeps between calls
@@ -34,8 +57,8 @@ struct PinBuf { // pinned, device-mapped host memory (grow-only)
 // and those that were decoded first in the last call; whether it ran its
 // kernels.
 struct UpdateScratch {
-    DevBuf meta, state, stat;
-    PinBuf pin;
+    ScratchDev meta, state, stat;
+    ScratchPin pin;
     hipEvent_t ev = nullptr;
     bool ev_live = false;
     uint64_t blocks = 0, decoded = 0;
@@ -57,7 +80,7 @@ struct snapmi_ctx {
     std::vector<snapmi::DevBuf *> dev_bufs;
     std::vector<snapmi::PinBuf *> pin_bufs;
     // pinned host staging of the scalar (host-pointer) entry points
-    snapmi::PinBuf pin_in, pin_out, pin_desc;
+    snapmi::ScratchPin pin_in, pin_out, pin_desc;
     // slices of the host-buffer frame calls: input bytes per encode slice,
     // data chunks per decode slice
     // (measured, profiles/r3_host_pipeline.txt: the match finder's latency
@@ -91,10 +114,15 @@ struct snapmi_ctx {
     bool owns_stream = false;
     std::string last_error;
     // grow-only device scratch of the raw codec
-    snapmi::DevBuf blk_first, slot_first, blk_size, blk_off, slots, plan_part;
-    // lane-per-block match finder: tokens, token counts, HBM hash tables
-    snapmi::DevBuf tokens, tok_pages, tok_stage, ntok, lane_tables,
-        lane_epochs;
+    snapmi::ScratchDev blk_first, slot_first, blk_size, blk_off, slots,
+        plan_part;
+    // lane-per-block match finder: tokens, token counts
+    snapmi::ScratchDev tokens, tok_pages, tok_stage, ntok;
+    // ... and its HBM hash tables with every lane's epoch: kept - an entry of
+    // an older epoch counts as empty, so a table is never cleared between
+    // blocks.  place_lane_tables (snapmi_lanetables.hip) zeroes both whenever
+    // it gives them memory.
+    snapmi::KeptDev lane_tables, lane_epochs;
     // lane_tables made of physical chunks (hipMemCreate) mapped into one
     // address range (place_lane_tables, snapmi_lanetables.hip): the chunks and
     // the bytes of the range; empty / 0 when lane_tables.p came from hipMalloc
@@ -115,7 +143,7 @@ struct snapmi_ctx {
     // order of the blocks is chosen as the launch goes (SpanSched,
     // snapmi_compress.hip), 0 ticket order, 2 scheduled whatever the count
     int span_schedule = 1;
-    snapmi::DevBuf sched;
+    snapmi::ScratchDev sched;
     // 1: lane-kernel launches of at least lane_coresident_min_blocks blocks
     // run k_match_both - three lane wavefronts and two window wavefronts on
     // every CU, one two-ended ticket
@@ -232,32 +260,37 @@ struct snapmi_ctx {
     hipEvent_t ev_crc[2] = {nullptr, nullptr}; // frame encode: CRC on stream2
     bool frame_crc_side_stream = true;
     // staging for the host-pointer (scalar) entry points
-    snapmi::DevBuf st_in, st_out, st_desc, st_prof, ticket, order;
+    snapmi::ScratchDev st_in, st_out, st_desc, st_prof, ticket, order;
     // long-stream decode scratch of snapmi_decompress_stream and of the long
     // streams of a batch (snapmi_streamplan.hpp lays them out): tables,
     // piece descriptors
-    snapmi::DevBuf sd_tables, sd_desc;
+    snapmi::ScratchDev sd_tables, sd_desc;
     // the long streams of a small batch get their pieces
     // (snapmi_decompress_batch, option batch_long_streams): modes of the
     // batch's own launch and of the one behind, what k_long_plan found; the
     // streams' descriptors and workgroup prefixes (a lone stream's too); pinned
     // staging of the list and of the batch's descriptors
     int batch_long_streams = 1;
-    snapmi::DevBuf bl_modes, bl_list, bl_descs, bl_order;
-    snapmi::PinBuf pin_bl;
-    snapmi::PinBuf pin_bl2; // descriptors of the long streams of a batch
+    snapmi::ScratchDev bl_modes, bl_list, bl_descs, bl_order;
+    snapmi::ScratchPin pin_bl;
+    snapmi::ScratchPin pin_bl2; // descriptors of the long streams of a batch
     // snapmi_decompress_batch_indexed: the modes of the launch behind, the
     // descriptor list (a slot per stream and per index entry), and the gate /
     // counter words of its kernels
     // (IndexArgs::gate); calls so far; whether the last call ran them
-    snapmi::DevBuf ix_modes, ix_desc, ix_gate;
+    snapmi::ScratchDev ix_modes, ix_desc;
+    // kept: gate[3] carries the ix_seq of the last call that handed a stream
+    // back, and the launch behind compares it with its own.
+    // snapmi_decompress_batch_indexed zeroes the 64 bytes when it first gives
+    // them memory (fresh_gate); every call's k_index_plan resets the counters
+    snapmi::KeptDev ix_gate;
     uint64_t ix_seq = 0;
     bool ix_stats_live = false;
     // snapmi_decompress_ranges_indexed: the piece descriptors of one group,
     // per-range slots and verdicts, the scans' partial sums, the edge rooms
     // (at most range_scratch_bytes of them) and the two counters of its
     // kernels; pieces the last call's ranges took; whether it ran them
-    snapmi::DevBuf rg_desc, rg_meta, rg_part, rg_room, rg_stat;
+    snapmi::ScratchDev rg_desc, rg_meta, rg_part, rg_room, rg_stat;
     uint64_t range_scratch_bytes = 1ull << 30;
     uint64_t rg_pieces = 0;
     bool rg_stats_live = false;
@@ -267,8 +300,8 @@ struct snapmi_ctx {
     // turn), each with the event of the copy that last read it - the call
     // waits for that event, never for the stream, before it writes there
     // again; groups so far; whether the last call ran its kernels
-    snapmi::DevBuf ib_meta, ib_stat;
-    snapmi::PinBuf pin_ib, pin_ibg[2];
+    snapmi::ScratchDev ib_meta, ib_stat;
+    snapmi::ScratchPin pin_ib, pin_ibg[2];
     hipEvent_t ev_ib = nullptr, ev_ibg[2] = {nullptr, nullptr};
     bool ev_ib_live = false, ev_ibg_live[2] = {false, false};
     uint64_t ib_groups = 0;
@@ -281,7 +314,7 @@ struct snapmi_ctx {
     // write_scratch_bytes a group, unless one stream takes more) and its piece
     // descriptors - is one set: the calls follow each other on the stream.
     snapmi::UpdateScratch wr, ap;
-    snapmi::DevBuf up_z, up_slot, up_room, up_desc;
+    snapmi::ScratchDev up_z, up_slot, up_room, up_desc;
     uint64_t write_scratch_bytes = 1ull << 30;
     // test options: "index_build_route" (BuildArgs::route) and the most
     // streams a group of the scan route holds
@@ -292,15 +325,18 @@ struct snapmi_ctx {
     uint32_t stream_seg_log2 = 0;
     uint32_t stream_scan_segs = 0; // test option: 0 = by size
     // frame layer scratch (snapmi_frame.hip)
-    snapmi::DevBuf fr_tables, fr_desc, fr_scan, fr_slots, fr_chunk_off;
+    snapmi::ScratchDev fr_desc, fr_slots, fr_chunk_off;
+    // kept: the CRC32C tables, filled once by ensure_tables
+    // (snapmi_frame.hip) when it gives them memory; fr_tables_ready says so
+    snapmi::KeptDev fr_tables;
     // snapmi_crc32c_masked_batch: the long buffers' segment scan and
     // accumulators (sized from n alone)
-    snapmi::DevBuf fr_crc;
+    snapmi::ScratchDev fr_crc;
     // frame decode: per-stream and per-chunk scratch
-    snapmi::DevBuf fb_streams, fb_chunks;
+    snapmi::ScratchDev fb_streams, fb_chunks;
     // the front that decided the last no-wait decode (info
     // "frame_nowait_front"); whether there has been one
-    snapmi::DevBuf fr_nowait;
+    snapmi::ScratchDev fr_nowait;
     bool fr_nowait_live = false;
     bool fr_tables_ready = false;
     // framed streams of at least this many bytes without a side index get
@@ -346,6 +382,13 @@ struct snapmi_ctx {
     uint64_t codec_launches = 0;
     uint32_t seam_seq = 0; // the seam's single-launch path: its last ticket
     uint32_t prof_tail_lanes = 0; // SNAPMI_PROFILE=3: lanes of the last launch
+#ifdef SNAPMI_TESTING
+    // test option "scratch_fill" (include/snapmi_test.h): the byte every new
+    // allocation is born holding, -1 = off; what the last setting filled
+    // (buffers, bytes) and how many of those buffers read back as filled
+    int scratch_fill = -1;
+    uint64_t fill_buffers = 0, fill_bytes = 0, fill_seen = 0;
+#endif
 };
 
 namespace snapmi {
@@ -369,6 +412,25 @@ inline int fail_ctx(snapmi_ctx *ctx, int kind, const char *fmt, ...)
             return snapmi::fail_ctx((ctx), SNAPMI_E_DEVICE, "%s failed: %s",  \
                                     #expr, hipGetErrorString(_e));            \
     } while (0)
+
+#ifdef SNAPMI_TESTING
+// Test option "scratch_fill": a new allocation of either class holds the
+// byte before its owner sees it (a kept buffer's own initialisation comes
+// after, as after a real hipMalloc).  Blocking.
+inline int fill_new_dev(snapmi_ctx *ctx, DevBuf &b)
+{
+    if (ctx->scratch_fill < 0)
+        return SNAPMI_OK;
+    HIP_TRY(ctx, hipMemsetAsync(b.p, ctx->scratch_fill, b.cap, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SNAPMI_OK;
+}
+inline void fill_new_pin(snapmi_ctx *ctx, PinBuf &b)
+{
+    if (ctx->scratch_fill >= 0)
+        memset(b.p, ctx->scratch_fill, b.cap);
+}
+#endif
 
 // (slack: an eighth more than asked for, so that batches that grow a little
 // do not reallocate every time - or none, for the token pool, whose size is a
@@ -394,7 +456,11 @@ inline int reserve(snapmi_ctx *ctx, DevBuf &b, size_t bytes,
     size_t want = bytes + (slack ? bytes / 8 : 0) + 256;
     HIP_TRY(ctx, hipMalloc(&b.p, want));
     b.cap = want;
+#ifdef SNAPMI_TESTING
+    return fill_new_dev(ctx, b);
+#else
     return SNAPMI_OK;
+#endif
 }
 
 } // namespace snapmi

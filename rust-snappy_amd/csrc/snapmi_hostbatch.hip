@@ -117,6 +117,9 @@ int pin_buf(snapmi_ctx *ctx, PinBuf &b, size_t bytes)
     const size_t want = bytes + bytes / 8 + 4096;
     HIP_TRY(ctx, hipHostMalloc(&b.p, want, hipHostMallocDefault));
     b.cap = want;
+#ifdef SNAPMI_TESTING
+    fill_new_pin(ctx, b);
+#endif
     return SNAPMI_OK;
 }
 

@@ -21,7 +21,7 @@ namespace snapmi {
 constexpr int kSlots = 3;
 
 struct PipeSlot {
-    DevBuf in, out, desc; // desc: u64 len | snapmi_error | index...
+    ScratchDev in, out, desc; // desc: u64 len | snapmi_error | index...
     hipEvent_t ev_h2d = nullptr, ev_k = nullptr, ev_d2h = nullptr;
     struct Result {
         uint64_t len;
@@ -32,8 +32,8 @@ struct PipeSlot {
     // the host-memory batch calls (snapmi_hostbatch.hip): the slice's results
     // and packed output on the device; pinned staging of what goes in
     // (descriptors + packed inputs) and of what comes home
-    DevBuf home;
-    PinBuf hb_in, hb_home;
+    ScratchDev home;
+    ScratchPin hb_in, hb_home;
 };
 
 } // namespace snapmi

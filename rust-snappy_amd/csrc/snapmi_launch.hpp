@@ -59,6 +59,9 @@ inline int pin_reserve(snapmi_ctx *ctx, PinBuf &b, size_t bytes)
     const size_t want = bytes + bytes / 4 + 4096;
     HIP_TRY(ctx, hipHostMalloc(&b.p, want, hipHostMallocDefault));
     b.cap = want;
+#ifdef SNAPMI_TESTING
+    fill_new_pin(ctx, b);
+#endif
     return SNAPMI_OK;
 }
 

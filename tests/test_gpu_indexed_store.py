@@ -303,7 +303,7 @@ class Chain:
                 ints(self.first), ints(self.index)[:self.entries])
 
 
-def run_chain(ctx, run, kernel, check=True, spills=False):
+def run_chain(ctx, run, kernel, check=True, spills=False, before_call=None):
     """The steps of a played scenario, one synchronize per step; step k + 1
     reads its streams where step k left them - a stream that succeeded in the
     out slab, a kept one in the slab it was already in - and nothing is
@@ -320,9 +320,15 @@ def run_chain(ctx, run, kernel, check=True, spills=False):
         b = Buffers(p, k)
         torch.cuda.synchronize()  # the buffers are filled
         info = []
-        b.enqueue(ctx, c.ptrs, c.lens, c.first, c.index, c.entries,
-                  lambda: info.extend(ctx.info("index_streams_" + x)
-                                      for x in ("pieced", "fallback")))
+
+        def between():
+            info.extend(ctx.info("index_streams_" + x)
+                        for x in ("pieced", "fallback"))
+            if before_call:
+                before_call()
+        if before_call:
+            before_call()
+        b.enqueue(ctx, c.ptrs, c.lens, c.first, c.index, c.entries, between)
         ctx.synchronize()
         if p.kind in ("write", "append"):
             assert ctx.last_kernel() == kernel, (what, ctx.last_kernel())

@@ -154,6 +154,13 @@ SNAPMI_API const char *snapmi_version(void);
  *                          lane-per-block kernel on large batches (default)
  *                          [2, both at once, is a cross-check of the test
  *                          build: snapmi_test.h]
+ *   "span_kernel"          1 (default, and the only value here): the window
+ *                          kernels take a window of 63 positions per step
+ *                          [0, one copy per step, is a cross-check of the
+ *                          test build: snapmi_test.h]
+ *   "both_wave_cus"        compress_mode 2 only: CUs the window kernel's
+ *                          persistent workgroups take beside the lane kernel
+ *                          (0 .. 4096; default 0 = half of the CUs)
  *   "small_table_kernel"   1 (default): blocks of at most 8 KiB - pages,
  *                          short frame chunks, tails - are matched by a
  *                          window kernel with the 16 KiB table the reference
@@ -186,6 +193,23 @@ SNAPMI_API const char *snapmi_version(void);
  *                          for fewer blocks
  *   "lane_min_blocks"      batches with at least this many 64 KiB blocks use
  *                          the lane-per-block kernel (default 20480 = 1.25 GiB)
+ *   "lane_coresident"      1 (default): large lane-kernel launches run
+ *                          k_match_both - lane wavefronts and two window
+ *                          wavefronts on every CU, one two-ended ticket (cfg2:
+ *                          115.6 -> 108.4 ms for the match finder; at 4 GiB a
+ *                          draw); 0: the lane kernel alone
+ *   "lane_coresident_min_blocks"  launches of at least this many blocks are
+ *                          "large" for lane_coresident (default 98304 = 6 GiB)
+ *   "match_kernel"         the match finder of a large batch: 0 k_match_blocks
+ *                          (a lane per block, hash tables in HBM), 1
+ *                          k_match_spans (a wavefront per block, table in LDS,
+ *                          no tables in HBM), 2 (default) k_match_spans when
+ *                          the context's last batch did not compress, else
+ *                          k_match_blocks
+ *   "match_spans_ratio_pct"  for match_kernel 2, "did not compress": the
+ *                          output was at least this per cent of the input
+ *                          (1 .. 200; default 90) - such data costs a lane
+ *                          three HBM transactions per probe for nothing
  *   "lane_speculate"       1 (default): a lane-kernel launch of at most 24 576
  *                          blocks (1.5 GiB) also fetches, in a probe's round,
  *                          the table entry of the probe that follows a miss -

@@ -41,6 +41,9 @@ extern "C" {
  *                          stream meanwhile (measured slower); 2: whenever it
  *                          has two blocks
  *   "lane_table_probe"     1: time the placement even with one try
+ *   "lane_table_stride_kib"  bytes between two lanes' tables, in KiB: 0
+ *                          (default) by the budget, or 256 .. 4096 in steps
+ *                          of 4 (an experiment knob: no probing, no chunks)
  *   "lane_tables_renew"    1: free the lane tables now; the next large batch
  *                          allocates (and places) new ones
  *   "lane_epoch_preset"    0..65535: every lane's hash-table epoch is set to
@@ -56,6 +59,11 @@ extern "C" {
  *                          k_decompress_streams3_many, 16 streams of the
  *                          sorted order per workgroup (default 1 048 576; the
  *                          suite lowers it to reach the kernel with 40 000)
+ *   "stream_seg_log2"      segment size of the long-stream scan: 0 (default)
+ *                          by size - 1 KiB under 256 MiB of long streams,
+ *                          4 KiB from there -, 10 or 12: forced
+ *   "stream_scan_segs"     segments a scan workgroup of it takes: 0 (default)
+ *                          by size, or 8, 16, 32, 64
  *   "frame_walk_segment"   segment of the parallel chunk-header walk (>= 128
  *                          KiB; default 32 MiB)
  *   "host_batch_direct_min"  the host batch calls copy a stream of at least
@@ -94,6 +102,13 @@ extern "C" {
  *                          buffers hold the byte in their first, middle and
  *                          last position, "scratch_fill_seen"
  * Returns SNAPMI_E_ARGUMENT for an unknown name.
+ *
+ * snapmi_ctx_get_info answers one more name in the test build (beside the
+ * three of "scratch_fill"):
+ *   "lane_multi_rounds"    rounds of the last token-path segment's lane
+ *                          wavefronts that resolved more probes than the
+ *                          launch's own depth (the test build's kernels
+ *                          count them; waits for the launch)
  */
 SNAPMI_API int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
                                int64_t value);

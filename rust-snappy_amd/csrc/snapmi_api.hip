@@ -18,6 +18,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "snapmi.h"
@@ -281,109 +282,27 @@ void snapmi_ctx_destroy(snapmi_ctx *ctx)
     delete ctx;
 }
 
+#ifdef SNAPMI_TESTING // (the test build, libsnapmi_test.so: Makefile)
+constexpr bool kTestBuild = true;
+#else
+constexpr bool kTestBuild = false;
+#endif
+static_assert(kOptWriteScratchMin == (int64_t)(kSlotBytes + kMaxBlock),
+              "snapmi_options.hpp and snapmi_kernels.hpp disagree");
+
+// The names, the values each takes in this build and the fields they are
+// stored in: snapmi_options.hpp.  Here only what does more than store.
 int snapmi_ctx_set_option(snapmi_ctx *ctx, const char *name, int64_t value)
 {
     if (!ctx || !name)
         return SNAPMI_E_ARGUMENT;
-#ifdef SNAPMI_TESTING
-    // cross-checks of the test build: both compressors at once on one
-    // ticket (compress_mode 2), the one-copy-per-step wavefront kernels of
-    // rounds 1-3 (span_kernel 0), the second-generation decoder alone
-    // (decode_kernel 2)
-    constexpr int64_t kModeMax = 2, kSpanMin = 0;
-    constexpr bool kDec2 = true;
-#else
-    constexpr int64_t kModeMax = 1, kSpanMin = 1;
-    constexpr bool kDec2 = false;
-#endif
-    if (strcmp(name, "compress_mode") == 0 && value >= 0 && value <= kModeMax)
-        ctx->compress_mode = (int)value;
-    else if (strcmp(name, "lane_min_blocks") == 0 && value >= 1)
-        ctx->lane_min_blocks = (uint32_t)value;
-    else if (strcmp(name, "lane_segment_blocks") == 0 && value >= 64 &&
-             value <= 0x7FFFFFFF)
-        ctx->lane_segment_blocks = (uint32_t)value;
-    else if (strcmp(name, "lane_table_spread") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->lane_table_spread = value != 0;
-    else if (strcmp(name, "lane_table_tries") == 0 && value >= 1 &&
-             value <= 16)
-        ctx->lane_table_tries = (uint32_t)value;
-    else if (strcmp(name, "lane_table_budget_pct") == 0 && value >= 1 &&
-             value <= 90)
-        ctx->lane_table_budget_pct = (uint32_t)value;
-    else if (strcmp(name, "token_pool_pct") == 0 && value >= 1 &&
-             value <= 100) {
-        ctx->token_pool_pct = (uint32_t)value;
-        ctx->token_pool_now = 0; // (what it had grown to is forgotten)
-    } else if (strcmp(name, "token_pool_min_pages") == 0 && value >= 0 &&
-               value <= 0x7FFFFFFF)
-        ctx->token_pool_min_pages = (uint32_t)value;
-    else if (strcmp(name, "span_schedule") == 0 && value >= 0 && value <= 2)
-        ctx->span_schedule = (int)value;
-    else if (strcmp(name, "lane_coresident") == 0 && value >= 0 && value <= 1)
-        ctx->lane_coresident = (int)value;
-    else if (strcmp(name, "lane_coresident_min_blocks") == 0 && value >= 1)
-        ctx->lane_coresident_min_blocks = (uint64_t)value;
-    else if (strcmp(name, "small_table_kernel") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->small_table_kernel = (int)value;
-    else if (strcmp(name, "small_table_min_blocks") == 0 && value >= 1)
-        ctx->small_table_min_blocks = (uint64_t)value;
-    else if (strcmp(name, "small_batch_kernel") == 0 && value >= 0 &&
-             value <= 2)
-        ctx->small_batch_kernel = (int)value;
-    else if (strcmp(name, "lane_speculate") == 0 && value >= 0 && value <= 1)
-        ctx->lane_speculate = (int)value;
-    else if (strcmp(name, "lane_tail_probes") == 0 && value >= 0 &&
-             value <= 4)
-        ctx->lane_tail_probes = (uint32_t)value;
-    else if (strcmp(name, "lane_tail_idle_pct") == 0 && value >= 0 &&
-             value <= 100)
-        ctx->lane_tail_idle_pct = (uint32_t)value;
-    else if (strcmp(name, "span_kernel") == 0 && value >= kSpanMin &&
-             value <= 1)
-        ctx->span_kernel = (int)value;
-    else if (strcmp(name, "match_kernel") == 0 && value >= 0 && value <= 2)
-        ctx->match_kernel = (int)value;
-    else if (strcmp(name, "match_spans_ratio_pct") == 0 && value >= 1 &&
-             value <= 200)
-        ctx->match_spans_ratio_pct = (uint32_t)value;
-    else if (strcmp(name, "release_scratch") == 0 && value >= 0 && value <= 1)
-        ctx->release_scratch = (int)value;
-    else if (strcmp(name, "batch_long_streams") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->batch_long_streams = (int)value;
-    else if (strcmp(name, "both_wave_cus") == 0 && value >= 0 &&
-             value <= 4096)
-        ctx->both_wave_cus = (uint32_t)value;
-    else if (strcmp(name, "tiny_stream_kernel") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->tiny_stream_kernel = (int)value;
-    else if (strcmp(name, "small_stream_kernel") == 0 && value >= 0 &&
-             value <= 2)
-        ctx->small_stream_kernel = (int)value;
-    else if (strcmp(name, "frame_parallel_walk_min") == 0 && value >= 0)
-        ctx->frame_parallel_walk_min = (uint64_t)value;
-    else if (strcmp(name, "host_copy_kernel") == 0 && value >= 0 && value <= 3)
-        ctx->host_copy_kernel = (int)value;
-    else if (strcmp(name, "host_encode_slice") == 0 && value >= (1 << 16))
-        ctx->host_encode_slice = (uint64_t)value;
-    else if (strcmp(name, "host_decode_slice_chunks") == 0 && value >= 1)
-        ctx->host_decode_slice_chunks = (uint64_t)value;
-    else if (strcmp(name, "host_batch_slice") == 0 && value >= (1 << 16))
-        ctx->host_batch_slice = (uint64_t)value;
-    else if (strcmp(name, "range_scratch_bytes") == 0 && value >= (128 << 10))
-        ctx->range_scratch_bytes = (uint64_t)value;
-    // (the floor: one block's compress slot and its room)
-    else if (strcmp(name, "write_scratch_bytes") == 0 &&
-             value >= (int64_t)(kSlotBytes + kMaxBlock))
-        ctx->write_scratch_bytes = (uint64_t)value;
-    else if (strcmp(name, "decode_kernel") == 0 &&
-             (value == 0 || (value == 2 && kDec2) || value == 3))
-        ctx->decode_kernel = ctx->lds_store_order_ok ? (int)value : 0;
-    else
+    if (option_set(*ctx, name, value, false, kTestBuild) !=
+        OptionSet::accepted)
         return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "unknown option %s", name);
+    if (strcmp(name, "token_pool_pct") == 0)
+        ctx->token_pool_now = 0; // (what it had grown to is forgotten)
+    else if (strcmp(name, "decode_kernel") == 0 && !ctx->lds_store_order_ok)
+        ctx->decode_kernel = 0;
     return SNAPMI_OK;
 }
 
@@ -462,72 +381,19 @@ int snapmi_ctx_set_test_option(snapmi_ctx *ctx, const char *name,
 {
     if (!ctx || !name)
         return SNAPMI_E_ARGUMENT;
-    if (strcmp(name, "lane_waves_per_cu") == 0 && value >= 1 && value <= 32)
-        ctx->lane_waves_per_cu = (uint32_t)value;
-    else if (strcmp(name, "decode_many_min") == 0 && value >= 0)
-        ctx->decode_many_min = (uint64_t)value;
-    else if (strcmp(name, "lane_speculate_max_blocks") == 0 && value >= 0)
-        ctx->lane_speculate_max_blocks = (uint64_t)value;
-    else if (strcmp(name, "lane_max_waves") == 0 && value >= 0 &&
-             value <= 0x7FFFFFFF)
-        ctx->lane_max_waves = (uint32_t)value;
-    else if (strcmp(name, "frame_crc_side_stream") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->frame_crc_side_stream = value != 0;
-    else if (strcmp(name, "lane_tables_uncached") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->lane_tables_uncached = (int)value;
-    else if (strcmp(name, "lane_overlap_encode") == 0 && value >= 0 &&
-             value <= 2)
-        ctx->lane_overlap_encode = (int)value;
-    else if (strcmp(name, "frame_walk_segment") == 0 && value >= (128 << 10))
-        ctx->frame_walk_segment = (uint64_t)value;
-    else if (strcmp(name, "lane_table_stride_kib") == 0 &&
-             (value == 0 || (value >= 256 && value <= 4096 && value % 4 == 0)))
-        ctx->lane_table_stride_kib = (uint32_t)value; // 0: by the budget
-    else if (strcmp(name, "lane_table_probe") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->lane_table_probe = value != 0; // time the placement even if 1 try
-    else if (strcmp(name, "lane_tables_renew") == 0 && value == 1) {
+    if (option_set(*ctx, name, value, true, kTestBuild) != OptionSet::accepted)
+        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "unknown test option %s",
+                        name);
+    if (strcmp(name, "lds_order_ok") == 0)
+        ctx->lds_order_ok = ctx->lds_order_hw && value != 0; // can only lower
+    else if (strcmp(name, "lane_tables_renew") == 0) {
         // drop the tables so the next launch places new ones
         if (ctx->lane_tables.p) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             snapmi::free_lane_tables(ctx);
         }
-    } else if (strcmp(name, "lane_epoch_preset") == 0 && value >= -1 &&
-             value <= 0xFFFF)
-        ctx->lane_epoch_preset = value;
-    else if (strcmp(name, "index_build_route") == 0 && value >= 0 &&
-             value <= 2)
-        ctx->index_build_route = (uint32_t)value;
-    else if (strcmp(name, "index_build_group_streams") == 0 && value >= 1 &&
-             value <= 4096)
-        ctx->index_build_group_streams = (uint32_t)value;
-    else if (strcmp(name, "stream_seg_log2") == 0 &&
-             (value == 0 || value == 10 || value == 12))
-        ctx->stream_seg_log2 = (uint32_t)value; // 0: by size
-    else if (strcmp(name, "stream_scan_segs") == 0 &&
-             (value == 0 || value == 8 || value == 16 || value == 32 ||
-              value == 64))
-        ctx->stream_scan_segs = (uint32_t)value; // 0: by size
-    else if (strcmp(name, "lds_order_ok") == 0 && value >= 0 && value <= 1)
-        ctx->lds_order_ok = ctx->lds_order_hw && value != 0; // can only lower
-    else if (strcmp(name, "host_batch_direct_min") == 0 && value >= 0)
-        ctx->host_batch_direct_min = (uint64_t)value;
-    else if (strcmp(name, "host_batch_pack_to_host") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->host_batch_pack_to_host = (int)value;
-    else if (strcmp(name, "host_batch_listed") == 0 && value >= 0 &&
-             value <= 1)
-        ctx->host_batch_listed = (int)value;
-    else if (strcmp(name, "scratch_fill") == 0 && value >= -1 &&
-             value <= 255) {
-        ctx->scratch_fill = (int)value;
-        if (value >= 0)
-            return scratch_fill_now(ctx, (int)value);
-    } else
-        return fail_ctx(ctx, SNAPMI_E_ARGUMENT, "unknown test option %s",
-                        name);
+    } else if (strcmp(name, "scratch_fill") == 0 && value >= 0)
+        return scratch_fill_now(ctx, (int)value);
     return SNAPMI_OK;
 }
 #endif // SNAPMI_TESTING
@@ -736,12 +602,92 @@ static int fetch_counters(snapmi_ctx *ctx, bool live, const DevBuf &stat,
     return SNAPMI_OK;
 }
 
+// What snapmi_ctx_get_info answers: a name reads a field of the context, or
+// word `word` of the counters the kernels of a call keep on the device
+// (fetch_counters: waits for the call), or is written out below.  The names,
+// and which of them only the test build answers: snapmi_options.hpp.
+namespace {
+
+struct InfoDesc {
+    const char *name;
+    int64_t (*field)(const snapmi_ctx *);
+    int (*counters)(snapmi_ctx *, unsigned long long *w);
+    size_t word; // (neither: written out in snapmi_ctx_get_info)
+};
+
+#define FIELD(name, expr)                                                     \
+    {name, [](const snapmi_ctx *c) { return (int64_t)(c->expr); }, nullptr, 0}
+#define COUNTER(name, live, stat, k, word)                                    \
+    {name, nullptr, [](snapmi_ctx *c, unsigned long long *w) {                \
+         return fetch_counters(c, c->live, c->stat, w, k);                    \
+     }, word}
+constexpr InfoDesc kInfo[] = {
+    {"scratch_bytes"},
+    {"token_scratch_bytes"},
+    FIELD("token_pool_pages", tok_pool_pages_last),
+    FIELD("token_pool_pct_now", token_pool_now),
+    {"token_pages_asked"},
+    {"token_blocks_spilled"},
+    FIELD("host_batch_slices", hb_slices),
+    FIELD("host_batch_h2d_bytes", hb_h2d_bytes),
+    FIELD("host_batch_d2h_bytes", hb_d2h_bytes),
+    FIELD("host_batch_listed_slices", hb_listed_slices),
+    // (snapmi_decompress_batch_indexed: words 1 and 2 of its gate)
+    COUNTER("index_streams_pieced", ix_stats_live, ix_gate, 3, 1),
+    COUNTER("index_streams_fallback", ix_stats_live, ix_gate, 3, 2),
+    FIELD("range_pieces", rg_pieces),
+    COUNTER("range_ranges_ok", rg_stats_live, rg_stat, 2, 0),
+    COUNTER("range_ranges_failed", rg_stats_live, rg_stat, 2, 1),
+    FIELD("write_blocks", wr.blocks),
+    FIELD("write_blocks_decoded", wr.decoded),
+    COUNTER("write_streams_ok", wr.stats_live, wr.stat, 2, 0),
+    COUNTER("write_streams_failed", wr.stats_live, wr.stat, 2, 1),
+    FIELD("append_blocks", ap.blocks),
+    FIELD("append_blocks_decoded", ap.decoded),
+    COUNTER("append_streams_ok", ap.stats_live, ap.stat, 2, 0),
+    COUNTER("append_streams_failed", ap.stats_live, ap.stat, 2, 1),
+    COUNTER("index_build_built", ib_stats_live, ib_stat, 5, 0),
+    COUNTER("index_build_unaligned", ib_stats_live, ib_stat, 5, 1),
+    COUNTER("index_build_corrupt", ib_stats_live, ib_stat, 5, 2),
+    COUNTER("index_build_missized", ib_stats_live, ib_stat, 5, 3),
+    COUNTER("index_build_walked", ib_stats_live, ib_stat, 5, 4),
+    {"frame_nowait_front"},
+    {"lane_multi_rounds"},
+    FIELD("scratch_fill_buffers", fill_buffers),
+    FIELD("scratch_fill_bytes", fill_bytes),
+    FIELD("scratch_fill_seen", fill_seen),
+};
+#undef FIELD
+#undef COUNTER
+constexpr bool info_names_agree() // kInfo has kInfoNames' names, in order
+{
+    for (size_t i = 0; i < std::size(kInfo); i++)
+        if (std::string_view(kInfoNames[i].name) != kInfo[i].name)
+            return false;
+    return true;
+}
+static_assert(std::size(kInfo) == std::size(kInfoNames) && info_names_agree(),
+              "kInfo and snapmi_options.hpp's kInfoNames disagree");
+
+} // namespace
+
 int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value)
         return SNAPMI_E_ARGUMENT;
-    int rc;
-    if (strcmp(name, "scratch_bytes") == 0) {
+    const InfoDesc *d = find_named(kInfo, name);
+    if (!d || (kInfoNames[d - kInfo].test_only && !kTestBuild)) {
+        ctx->last_error = std::string("unknown info: ") + name;
+        return SNAPMI_E_ARGUMENT;
+    }
+    if (d->field) {
+        *value = d->field(ctx);
+    } else if (d->counters) {
+        unsigned long long w[5];
+        if (int rc = d->counters(ctx, w))
+            return rc;
+        *value = (int64_t)w[d->word];
+    } else if (strcmp(name, "scratch_bytes") == 0) {
         uint64_t sum = ctx->lane_tables.cap;
         for (const DevBuf *b : ctx->dev_bufs)
             sum += b->cap;
@@ -749,8 +695,24 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
     } else if (strcmp(name, "token_scratch_bytes") == 0) {
         *value = (int64_t)(ctx->tokens.cap + ctx->tok_pages.cap +
                            ctx->tok_stage.cap + ctx->ntok.cap);
-    } else if (strcmp(name, "token_pool_pages") == 0) {
-        *value = ctx->tok_pool_pages_last;
+    } else if (strcmp(name, "token_pages_asked") == 0 ||
+               strcmp(name, "token_blocks_spilled") == 0) {
+        // of the last token-path launch: wait for it
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const volatile uint32_t *t = ctx->h_tokstat;
+        const bool asked = strcmp(name, "token_pages_asked") == 0;
+        *value = !t ? 0 : asked ? t[0] : t[1];
+    } else if (strcmp(name, "frame_nowait_front") == 0) {
+        // of the last SNAPMI_FRAME_NO_WAIT decode: wait for it
+        uint32_t w = 0;
+        if (ctx->fr_nowait_live) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(&w, ctx->fr_nowait.p, sizeof w,
+                                   hipMemcpyDeviceToHost));
+        }
+        *value = ctx->fr_nowait_live ? (int64_t)w : -1;
 #ifdef SNAPMI_TESTING
     } else if (strcmp(name, "lane_multi_rounds") == 0) {
         // of the last token-path segment's lane wavefronts (test build: the
@@ -765,98 +727,7 @@ int snapmi_ctx_get_info(snapmi_ctx *ctx, const char *name, int64_t *value)
                                    sizeof w, hipMemcpyDeviceToHost));
         }
         *value = w;
-    } else if (strcmp(name, "scratch_fill_buffers") == 0) {
-        *value = (int64_t)ctx->fill_buffers;
-    } else if (strcmp(name, "scratch_fill_bytes") == 0) {
-        *value = (int64_t)ctx->fill_bytes;
-    } else if (strcmp(name, "scratch_fill_seen") == 0) {
-        *value = (int64_t)ctx->fill_seen;
 #endif
-    } else if (strcmp(name, "token_pool_pct_now") == 0) {
-        *value = ctx->token_pool_now;
-    } else if (strcmp(name, "token_pages_asked") == 0 ||
-               strcmp(name, "token_blocks_spilled") == 0) {
-        // of the last token-path launch: wait for it
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const volatile uint32_t *t = ctx->h_tokstat;
-        *value = !t ? 0 : name[6] == 'p' ? t[0] : t[1];
-    } else if (strcmp(name, "index_streams_pieced") == 0 ||
-               strcmp(name, "index_streams_fallback") == 0) {
-        // of the last snapmi_decompress_batch_indexed: wait for it
-        unsigned long long w[3] = {0, 0, 0};
-        if (ctx->ix_stats_live && ctx->ix_gate.p) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(w, ctx->ix_gate.p, sizeof w,
-                                   hipMemcpyDeviceToHost));
-        }
-        *value = (int64_t)(name[14] == 'p' ? w[1] : w[2]);
-    } else if (strcmp(name, "range_pieces") == 0) {
-        *value = (int64_t)ctx->rg_pieces;
-    } else if (strcmp(name, "range_ranges_ok") == 0 ||
-               strcmp(name, "range_ranges_failed") == 0) {
-        // of the last snapmi_decompress_ranges_indexed: wait for it
-        unsigned long long w[2];
-        if ((rc = fetch_counters(ctx, ctx->rg_stats_live, ctx->rg_stat, w, 2)))
-            return rc;
-        *value = (int64_t)(name[13] == 'o' ? w[0] : w[1]);
-    } else if (strcmp(name, "write_blocks") == 0) {
-        *value = (int64_t)ctx->wr.blocks;
-    } else if (strcmp(name, "write_blocks_decoded") == 0) {
-        *value = (int64_t)ctx->wr.decoded;
-    } else if (strcmp(name, "write_streams_ok") == 0 ||
-               strcmp(name, "write_streams_failed") == 0) {
-        // of the last snapmi_write_ranges_indexed: wait for it
-        unsigned long long w[2];
-        if ((rc = fetch_counters(ctx, ctx->wr.stats_live, ctx->wr.stat, w, 2)))
-            return rc;
-        *value = (int64_t)(name[14] == 'o' ? w[0] : w[1]);
-    } else if (strcmp(name, "append_blocks") == 0) {
-        *value = (int64_t)ctx->ap.blocks;
-    } else if (strcmp(name, "append_blocks_decoded") == 0) {
-        *value = (int64_t)ctx->ap.decoded;
-    } else if (strcmp(name, "append_streams_ok") == 0 ||
-               strcmp(name, "append_streams_failed") == 0) {
-        // of the last snapmi_append_indexed: wait for it
-        unsigned long long w[2];
-        if ((rc = fetch_counters(ctx, ctx->ap.stats_live, ctx->ap.stat, w, 2)))
-            return rc;
-        *value = (int64_t)(name[15] == 'o' ? w[0] : w[1]);
-    } else if (strncmp(name, "index_build_", 12) == 0 &&
-               (strcmp(name + 12, "built") == 0 ||
-                strcmp(name + 12, "unaligned") == 0 ||
-                strcmp(name + 12, "corrupt") == 0 ||
-                strcmp(name + 12, "missized") == 0 ||
-                strcmp(name + 12, "walked") == 0)) {
-        // of the last snapmi_build_block_index: wait for it
-        unsigned long long w[5];
-        if ((rc = fetch_counters(ctx, ctx->ib_stats_live, ctx->ib_stat, w, 5)))
-            return rc;
-        const char c = name[12];
-        *value = (int64_t)w[c == 'b' ? 0 : c == 'u' ? 1 : c == 'c' ? 2
-                            : c == 'm' ? 3 : 4];
-    } else if (strcmp(name, "frame_nowait_front") == 0) {
-        // of the last SNAPMI_FRAME_NO_WAIT decode: wait for it
-        uint32_t w = 0;
-        if (ctx->fr_nowait_live) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(&w, ctx->fr_nowait.p, sizeof w,
-                                   hipMemcpyDeviceToHost));
-        }
-        *value = ctx->fr_nowait_live ? (int64_t)w : -1;
-    } else if (strcmp(name, "host_batch_slices") == 0) {
-        *value = (int64_t)ctx->hb_slices;
-    } else if (strcmp(name, "host_batch_h2d_bytes") == 0) {
-        *value = (int64_t)ctx->hb_h2d_bytes;
-    } else if (strcmp(name, "host_batch_d2h_bytes") == 0) {
-        *value = (int64_t)ctx->hb_d2h_bytes;
-    } else if (strcmp(name, "host_batch_listed_slices") == 0) {
-        *value = (int64_t)ctx->hb_listed_slices;
-    } else {
-        ctx->last_error = std::string("unknown info: ") + name;
-        return SNAPMI_E_ARGUMENT;
     }
     return SNAPMI_OK;
 }

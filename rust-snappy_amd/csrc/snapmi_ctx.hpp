@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "snapmi.h"
+#include "snapmi_options.hpp"
 
 namespace snapmi {
 
@@ -69,7 +70,8 @@ struct UpdateScratch {
 
 struct snapmi_host_pipe; // snapmi_frame.hip: staging of the host-buffer calls
 
-struct snapmi_ctx {
+// (the base: every knob, its default and what it means)
+struct snapmi_ctx : snapmi::Options {
     int device = 0;
     snapmi_host_pipe *pipe = nullptr;
     // 256 bytes of pinned, device-mapped host memory: kernels post small
@@ -81,31 +83,6 @@ struct snapmi_ctx {
     std::vector<snapmi::PinBuf *> pin_bufs;
     // pinned host staging of the scalar (host-pointer) entry points
     snapmi::ScratchPin pin_in, pin_out, pin_desc;
-    // slices of the host-buffer frame calls: input bytes per encode slice,
-    // data chunks per decode slice
-    // (measured, profiles/r3_host_pipeline.txt: the match finder's latency
-    // floor wants two slices for 4 GiB, the decoder is happy from 0.5 GiB)
-    uint64_t host_encode_slice = 2048ull << 20;
-    uint64_t host_decode_slice_chunks = 8192;
-    // results go home by a copy kernel (bit 0: decode, bit 1: encode) or by
-    // hipMemcpyAsync: see k_to_host.  The kernel is used only when the
-    // caller's buffer is pinned, device-mapped host memory
-    // (snapmi_host_alloc).  Encode: off - the copy kernel would wait for the
-    // match finder's persistent workgroups.
-    int host_copy_kernel = 1;
-    // the host-memory batch calls (snapmi_hostbatch.hip): input bytes per
-    // slice; streams of at least host_batch_direct_min bytes are copied to
-    // the device from where they lie instead of through the pinned staging;
-    // 1: k_hb_pack stores a compress slice's packed output straight into
-    // pinned host memory, 0: into device memory, followed by one D2H
-    // (measured, profiles/host_batch.json; the last two are test options)
-    uint64_t host_batch_slice = 16ull << 20;
-    uint64_t host_batch_direct_min = 1ull << 20;
-    int host_batch_pack_to_host = 1;
-    // 1: a slice of snapmi_frame_decompress_batch_host whose streams the host
-    // found well-formed sends its chunk list along and the device does not
-    // walk (k_fbd_from_list); 0: the device always walks (test option)
-    int host_batch_listed = 1;
     // what the last host batch call did: slices, bytes copied each way,
     // slices decoded from the host's chunk list
     uint64_t hb_slices = 0, hb_h2d_bytes = 0, hb_d2h_bytes = 0;
@@ -131,134 +108,25 @@ struct snapmi_ctx {
     uint32_t lane_chunk_count = 0, lane_per_chunk = 0; // lane -> table map
     uint32_t n_lanes = 0;
     uint64_t lane_stride = 0;      // 16-byte entries between two lanes' tables
-    bool lane_table_spread = true; // spread the tables over free memory
     bool lane_tables_top = false;  // placed by snapmi_ctx_prepare(TOP_OF_MEMORY)
-    // SNAPMI_COMPRESS=waves|lanes|both: 0 = wavefront kernel only, 1 = lane
-    // kernel on large batches and the wavefront kernel on small ones
-    // (default), 2 = on large batches both kernels at once, sharing one
-    // two-ended ticket (no faster: the wavefront kernel takes whole CUs' LDS
-    // away from the lanes' input windows; kept as a cross-check)
-    int compress_mode = 1;
-    // k_compress_spans on more blocks than it has wavefronts: 1 (default) the
-    // order of the blocks is chosen as the launch goes (SpanSched,
-    // snapmi_compress.hip), 0 ticket order, 2 scheduled whatever the count
-    int span_schedule = 1;
     snapmi::ScratchDev sched;
-    // 1: lane-kernel launches of at least lane_coresident_min_blocks blocks
-    // run k_match_both - three lane wavefronts and two window wavefronts on
-    // every CU, one two-ended ticket
-    // (cfg2, 146 700 blocks: 115.6 -> 108.4 ms for the match finder; at 4 GiB
-    // a draw, below that the lanes have taken every block before a window
-    // wavefront has finished one: profiles/r5_coresident.txt)
-    int lane_coresident = 1;
-    uint64_t lane_coresident_min_blocks = 98304;
     const char *last_kernel = "";
-    // 1: blocks of at most 8 KiB go to the window kernel with 16 KiB tables
-    // (k_match_spans_8k: 10 wavefronts per CU) when the batch has at least
-    // small_table_min_blocks of them
-    int small_table_kernel = 1;
-    uint64_t small_table_min_blocks = 256;
-    // k_compress_block_lds (one block per CU, input block in LDS as well):
-    // 1 = for batches of at most two blocks per CU (default), 0 = never,
-    // 2 = whenever the wavefront kernel would run (tests)
-    int small_batch_kernel = 1;
-    // the wavefront-per-block kernels' step: 1 (default) = a window of 63
-    // consecutive positions per step, every parse event inside it resolved
-    // by a walk over registers (k_compress_spans / k_compress_span_lds);
-    // 0 = one copy per step (k_compress_blocks / k_compress_block_lds, the
-    // kernels of rounds 1-3: kept as the cross-check)
-    int span_kernel = 1;
-    // compress_mode 2 ("both"): CUs the wavefront kernel's persistent
-    // workgroups take (each owns a CU's whole LDS, so the lane kernel's
-    // wavefronts run on the others); 0 = half of the CUs
-    uint32_t both_wave_cus = 0;
-    // 1: the per-batch scratch of the compressor (token arrays: 128 KiB per
-    // block of a lane-kernel segment, up to 34 GB; block slots of the
-    // wavefront kernels) is given back when the batch's results are waited
-    // for (snapmi_ctx_synchronize; the scalar and libsnappy entry points,
-    // which wait for their own result) instead of being kept for the next
-    // batch.  snapmi_last_timing waits for events only and the host frame
-    // calls keep their pipeline's scratch: neither frees.  For a host
-    // that compresses now and then and shares the GPU; costs a hipFree /
-    // hipMalloc pair per batch.  The lane tables are not scratch: they are
-    // bounded by lane_table_budget_pct.
-    int release_scratch = 0;
-    // the match finder of the token path (large batches, compress_mode 1):
-    // 0 = k_match_blocks (a lane per block, hash tables in HBM), 1 =
-    // k_match_spans (a wavefront per block, table in LDS, no tables in HBM
-    // at all), 2 (default) = by what this context's last batch compressed
-    // to: data that does not compress (ratio >= match_spans_ratio_pct) costs
-    // a lane three HBM transactions per probe for nothing
-    int match_kernel = 2;
-    uint32_t match_spans_ratio_pct = 90;
     // the hint: pinned words the last token-path batch posted (compressed
     // bytes, input bytes, its number)
     volatile uint32_t *h_ratio = nullptr;
     uint32_t ratio_seq = 0; // batches posted so far
-    // the token pool (CompressArgs::tok_pool): per cent of the worst case it
-    // is sized to (option token_pool_pct), what that has grown to behind
-    // batches that spilled, the floor in pages (64 MiB: small batches never
-    // spill; test option token_pool_min_pages), and what k_redo_spilled
-    // posted of the last launch it has finished: pages asked for | blocks
-    // spilled | blocks | seq
-    uint32_t token_pool_pct = 39, token_pool_now = 0;
-    uint32_t token_pool_min_pages = 32768;
+    // the token pool (CompressArgs::tok_pool): what option token_pool_pct has
+    // grown to behind batches that spilled, and what k_redo_spilled posted of
+    // the last launch it has finished: pages asked for | blocks spilled |
+    // blocks | seq
+    uint32_t token_pool_now = 0;
     volatile uint32_t *h_tokstat = nullptr;
     uint32_t tokstat_seq = 0, tokstat_seen = 0;
     uint32_t tok_pages_asked = 0, tok_blocks_spilled = 0;
     uint32_t tok_pool_pages_last = 0; // pages of the last launch's pool
-    // 1 (default): a lane-kernel launch of at most lane_speculate_max_blocks
-    // blocks (and no more blocks than lanes) runs k_match_blocks_spec (a
-    // probe's round also fetches the entry of the probe that follows a
-    // miss); 0: always the plain kernel.  Measured: -10..15 % at 2 048 ..
-    // 16 384 blocks of text, nothing at 32 768 (test option to move the
-    // limit: lane_speculate_max_blocks).
-    int lane_speculate = 1;
-    uint64_t lane_speculate_max_blocks = 24576;
-    // The tail of a lane-kernel launch (k_match_blocks, k_match_blocks_spec,
-    // the lane wavefronts of k_match_both): once the ticket has run out lanes
-    // only finish, memory falls below its random-access rate and a round
-    // costs its latency.  lane_tail_probes 2..4: a wavefront that has seen
-    // the ticket run out resolves up to that many probes a round from the
-    // moment lane_tail_idle_pct per cent of the launch's lanes are out of
-    // work (0: from the first round); 0 or 1: never (the rounds of the launch
-    // stay what lane_speculate makes them).  Same bytes at every setting.
-    // Measured at cfg2, each time in one process on one table placement
-    // (profiles/lane_tail.json, the timeline in
-    // profiles/lane_tail_timeline.txt): 2 probes from 40 % idle take 2.6 ms
-    // off k_match_both's 107.7 and 1.4 off 110.6 on a second box; 3 and 4
-    // probes cost more than they save.
-    uint32_t lane_tail_probes = 2;
-    uint32_t lane_tail_idle_pct = 40;
-    // k_compress_tiny (streams of fewer than 256 bytes, one per LANE, all of
-    // their state in LDS): 1 = on (default), 0 = such streams are one-block
-    // streams of the block kernels (cross-check, and what round 2 measured)
-    int tiny_stream_kernel = 1;
-    // k_compress_small (streams of 256 bytes and more, a few per wavefront,
-    // state in LDS; needs tiny_stream_kernel): 1 = up to 1 023 bytes
-    // (default), 2 = up to 2 047 (measured slower than the lane kernel from
-    // 1 KiB on), 0 = off
-    int small_stream_kernel = 1;
-    // batches of more streams than this are decoded by
-    // k_decompress_streams3_many (kManyStreams streams per workgroup)
-    uint64_t decode_many_min = 1u << 20;
-    // the lane kernel's segment is matched in two halves and the first
-    // half's tokens are encoded on the side stream meanwhile: 1 = when the
-    // segment has at least 1.4 blocks per lane, 0 = never (default: measured
-    // SLOWER, 121.6 -> 135 ms at cfg2 - the encoder's streaming traffic under
-    // the match finder costs its random accesses far more than the 3.3 ms
-    // it hides), 2 = whenever the segment has two blocks (tests)
-    int lane_overlap_encode = 0;
-    // 1: the lane tables come from hipExtMallocWithFlags(hipDeviceMallocUncached)
-    int lane_tables_uncached = 0;
-    // 3: k_decompress_streams3 (element per lane, 128-byte windows; default);
-    // 2: k_decompress_streams2 (64-byte windows), kept as a cross-check;
-    // 0: the sequential decoder alone
-    int decode_kernel = 3;
     hipStream_t stream2 = nullptr; // the wavefront kernel's side stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_crc[2] = {nullptr, nullptr}; // frame encode: CRC on stream2
-    bool frame_crc_side_stream = true;
     // staging for the host-pointer (scalar) entry points
     snapmi::ScratchDev st_in, st_out, st_desc, st_prof, ticket, order;
     // long-stream decode scratch of snapmi_decompress_stream and of the long
@@ -270,7 +138,6 @@ struct snapmi_ctx {
     // batch's own launch and of the one behind, what k_long_plan found; the
     // streams' descriptors and workgroup prefixes (a lone stream's too); pinned
     // staging of the list and of the batch's descriptors
-    int batch_long_streams = 1;
     snapmi::ScratchDev bl_modes, bl_list, bl_descs, bl_order;
     snapmi::ScratchPin pin_bl;
     snapmi::ScratchPin pin_bl2; // descriptors of the long streams of a batch
@@ -291,7 +158,6 @@ struct snapmi_ctx {
     // (at most range_scratch_bytes of them) and the two counters of its
     // kernels; pieces the last call's ranges took; whether it ran them
     snapmi::ScratchDev rg_desc, rg_meta, rg_part, rg_room, rg_stat;
-    uint64_t range_scratch_bytes = 1ull << 30;
     uint64_t rg_pieces = 0;
     bool rg_stats_live = false;
     // snapmi_build_block_index: the device's copies of the host's arrays, the
@@ -315,15 +181,6 @@ struct snapmi_ctx {
     // descriptors - is one set: the calls follow each other on the stream.
     snapmi::UpdateScratch wr, ap;
     snapmi::ScratchDev up_z, up_slot, up_room, up_desc;
-    uint64_t write_scratch_bytes = 1ull << 30;
-    // test options: "index_build_route" (BuildArgs::route) and the most
-    // streams a group of the scan route holds
-    uint32_t index_build_route = 0;
-    uint32_t index_build_group_streams = 4096;
-    // segment size of the long-stream scan: 0 = by size (1 KiB under 256 MiB
-    // of long streams, 4 KiB from there), 10 / 12 forced (test option)
-    uint32_t stream_seg_log2 = 0;
-    uint32_t stream_scan_segs = 0; // test option: 0 = by size
     // frame layer scratch (snapmi_frame.hip)
     snapmi::ScratchDev fr_desc, fr_slots, fr_chunk_off;
     // kept: the CRC32C tables, filled once by ensure_tables
@@ -339,35 +196,9 @@ struct snapmi_ctx {
     snapmi::ScratchDev fr_nowait;
     bool fr_nowait_live = false;
     bool fr_tables_ready = false;
-    // framed streams of at least this many bytes without a side index get
-    // their chunk headers found in parallel (k_fw_*); shorter ones are walked
-    uint64_t frame_parallel_walk_min = 4ull << 20;
-    uint64_t frame_walk_segment = 32ull << 20; // >= 128 KiB (test knob)
     int num_cus = 0;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // measured crossover (profiles/r5_crossover.txt): the corpus round 1.7
-    // GiB, alice29.txt 1.15, html 0.55 - 8 192 until the window kernel got
-    // its lane-parallel walk in round 5
-    uint32_t lane_min_blocks = 20480;
-    // blocks per lane-kernel launch: bounds the token scratch (34 GB here)
-    uint32_t lane_segment_blocks = 262144;
-    uint32_t lane_waves_per_cu = 6; // 24 KiB of LDS per wave
-    uint32_t lane_max_waves = 0;    // test knob: cap on lane-kernel waves (0 = none)
-    // placements of the lane tables that are timed before one is kept
-    // (place_lane_tables in snapmi_lanetables.hip: spread over the budget, then
-    // packed behind that, then spread again; a candidate costs one hipMalloc
-    // and a 3 ms probe, and the driver wipes what a loser gives back)
-    uint32_t lane_table_tries = 2;
-    // percent of the free device memory the lane tables (and, while a
-    // placement is chosen, their candidates) may hold: the GPU may be shared
-    uint32_t lane_table_budget_pct = 33;
-    bool lane_table_probe = false; // experiment knob: probe even with 1 try
-    uint32_t lane_table_stride_kib = 0; // experiment knob: bytes between tables
     std::string probe_log;          // k_probe_tables ms of every candidate
-    // test knob: every lane's table epoch is set to this value before the
-    // next lane-kernel launch (-1 = leave the epochs alone); lets a test
-    // reach the 16-bit epoch wrap without 65 535 blocks per lane
-    int64_t lane_epoch_preset = -1;
     // ds_mskor_rtn_b32 applies same-address lanes in ascending lane order on
     // this device (checked by k_probe_lds_order at context creation); the
     // wavefront-per-block kernel is only used when this holds
@@ -382,13 +213,10 @@ struct snapmi_ctx {
     uint64_t codec_launches = 0;
     uint32_t seam_seq = 0; // the seam's single-launch path: its last ticket
     uint32_t prof_tail_lanes = 0; // SNAPMI_PROFILE=3: lanes of the last launch
-#ifdef SNAPMI_TESTING
-    // test option "scratch_fill" (include/snapmi_test.h): the byte every new
-    // allocation is born holding, -1 = off; what the last setting filled
-    // (buffers, bytes) and how many of those buffers read back as filled
-    int scratch_fill = -1;
+    // test option "scratch_fill": what the last setting filled (buffers,
+    // bytes) and how many of those buffers read back as filled (in the
+    // product context too, always 0: kInfo is the same table in both builds)
     uint64_t fill_buffers = 0, fill_bytes = 0, fill_seen = 0;
-#endif
 };
 
 namespace snapmi {

@@ -390,7 +390,8 @@ int place_lane_tables(snapmi_ctx *ctx, uint32_t lanes, bool top_of_memory)
 // for and the tables are not there yet.
 int prepare_lane_tables(snapmi_ctx *ctx, uint64_t blocks, bool top)
 {
-    const uint32_t lanes = prepare_lanes(route_options(ctx), blocks);
+    const uint32_t lanes = prepare_lanes(
+        *ctx, {ctx->lds_order_ok, (uint32_t)ctx->num_cus}, blocks);
     if (!lanes)
         return SNAPMI_OK;
     if (lanes <= ctx->n_lanes && !(top && !ctx->lane_tables_top))

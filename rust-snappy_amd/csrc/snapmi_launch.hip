@@ -27,33 +27,6 @@ static_assert(kRouteCompressWaves == kCompressWaves &&
                   kRouteSmallCompress == kSmallCompress,
               "snapmi_route.hpp and snapmi_kernels.hpp disagree");
 
-// (snapmi_route.hpp: the options it reads)
-RouteOptions route_options(const snapmi_ctx *ctx)
-{
-    RouteOptions o;
-    o.compress_mode = ctx->compress_mode;
-    o.lds_order_ok = ctx->lds_order_ok;
-    o.num_cus = (uint32_t)ctx->num_cus;
-    o.lane_min_blocks = ctx->lane_min_blocks;
-    o.lane_segment_blocks = ctx->lane_segment_blocks;
-    o.lane_waves_per_cu = ctx->lane_waves_per_cu;
-    o.lane_max_waves = ctx->lane_max_waves;
-    o.lane_coresident = ctx->lane_coresident;
-    o.lane_coresident_min_blocks = ctx->lane_coresident_min_blocks;
-    o.small_table_kernel = ctx->small_table_kernel;
-    o.small_table_min_blocks = ctx->small_table_min_blocks;
-    o.small_batch_kernel = ctx->small_batch_kernel;
-    o.span_kernel = ctx->span_kernel;
-    o.span_schedule = ctx->span_schedule;
-    o.both_wave_cus = ctx->both_wave_cus;
-    o.match_kernel = ctx->match_kernel;
-    o.lane_speculate = ctx->lane_speculate;
-    o.lane_speculate_max_blocks = ctx->lane_speculate_max_blocks;
-    o.lane_overlap_encode = ctx->lane_overlap_encode;
-    o.tiny_stream_kernel = ctx->tiny_stream_kernel;
-    o.small_stream_kernel = ctx->small_stream_kernel;
-    return o;
-}
 static_assert(snapmi::kPoolTokPage == kTokPage &&
                   snapmi::kPoolExcPage == kExcPage &&
                   snapmi::kPoolPagesPerBlock ==
@@ -97,7 +70,7 @@ static int compress_batch(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     }
     uint64_t blocks = 0, slots = 0, cnt8 = 0, block_bytes = 0;
     // streams under this length are the lane-per-stream kernels': no block
-    const uint64_t small = small_stream_limit(route_options(ctx));
+    const uint64_t small = small_stream_limit(*ctx);
     uint32_t classes = 0; // which of those kernels have anything to do
     for (size_t i = 0; i < n; i++) {
         const uint64_t len = h_in_lens[i];
@@ -235,10 +208,10 @@ static void launch_window(const CompressRoute &route, const CompressArgs &a,
 }
 
 // the route's match finder over the blocks [a.blk_lo, a.blk_hi) of segment g
-static void launch_match(const RouteOptions &o, const CompressRoute &route,
+static void launch_match(const RouteDevice &d, const CompressRoute &route,
                          const Segment &g, CompressArgs a, hipStream_t s)
 {
-    const dim3 grid(match_grid(o, route, a.blk_hi - a.blk_lo));
+    const dim3 grid(match_grid(d, route, a.blk_hi - a.blk_lo));
     switch (route.match) {
     case MatchKernel::spans:
         hipLaunchKernelGGL(k_match_spans, grid, dim3(kCompressWaves * 64), 0,
@@ -289,8 +262,9 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
         return rc;
 
     // which kernels the batch runs (snapmi_route.hpp)
-    const RouteOptions o = route_options(ctx);
-    const CompressRoute route = compress_route(o, blocks, cnt8, spans_hint(ctx));
+    const RouteDevice d = {ctx->lds_order_ok, (uint32_t)ctx->num_cus};
+    const CompressRoute route =
+        compress_route(*ctx, d, blocks, cnt8, spans_hint(ctx));
 
     CompressArgs a;
     a.in_ptrs = d_in_ptrs;
@@ -329,7 +303,7 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     a.lane_tail_depth = 0;
     a.lane_tail_idle = 0;
     a.tok_base = 0;
-    a.small_limit = (uint32_t)small_stream_limit(o);
+    a.small_limit = (uint32_t)small_stream_limit(*ctx);
     a.cls_lo = 0;
     a.cls_hi = kMaxBlock;
     a.direct = route.direct ? 1 : 0;
@@ -511,7 +485,7 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
             const uint64_t hi = lo + route.seg_blocks < blocks
                                     ? lo + route.seg_blocks
                                     : blocks;
-            const Segment g = segment(o, route, lo, hi);
+            const Segment g = segment(*ctx, d, route, lo, hi);
             a.tok_base = (uint32_t)lo;
             a.blk_lo = (uint32_t)lo;
             a.blk_hi = (uint32_t)g.mid;
@@ -524,7 +498,7 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
             // (with the small-block kernels on, this launch's class is the
             // blocks of more than 8 KiB - if the batch has any)
             a.cls_lo = route.small_grid ? 8192 : 0;
-            launch_match(o, route, g, a, s);
+            launch_match(d, route, g, a, s);
             if (route.small_grid) {
                 HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
                 a.cls_lo = 0;
@@ -545,7 +519,7 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
                 a.blk_lo = (uint32_t)g.mid;
                 a.blk_hi = (uint32_t)hi;
                 HIP_TRY(ctx, hipMemsetAsync(ctx->ticket.p, 0, 64, s));
-                launch_match(o, route, g, a, s);
+                launch_match(d, route, g, a, s);
             }
             if (hi == blocks) // dominant_ms: first match start .. last end
                 HIP_TRY(ctx, hipEventRecord(ctx->ev[5], s));

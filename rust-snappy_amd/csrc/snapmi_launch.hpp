@@ -10,7 +10,6 @@
 
 namespace snapmi {
 
-struct RouteOptions;            // snapmi_route.hpp
 struct CompressArgs;            // snapmi_kernels.hpp
 
 static_assert(sizeof(snapmi_error) == kPieceErrBytes,
@@ -90,7 +89,6 @@ void launch_block_index(snapmi_ctx *ctx, const CompressArgs &a,
                         uint64_t index_entries);
 
 // snapmi_launch.hip
-RouteOptions route_options(const snapmi_ctx *ctx);
 // raw compress of n streams; blocks/slots = launch geometry computed from
 // the (host-known) stream lengths
 int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,

@@ -1,11 +1,12 @@
 // snapmi - which kernels a compress batch runs (DESIGN 4.1's routing table):
 // plain functions of the context's options and the batch (no HIP), so that
 // tests/test_route_cpu.py can pin every row of it on the CPU.
-// launch_compress (snapmi_api.hip) computes a CompressRoute, reserves what it
-// names and launches it; snapmi_api.hip is the only user in the library.
+// launch_compress (snapmi_launch.hip) computes a CompressRoute, reserves what
+// it names and launches it; the functions read the context's own Options.
 #pragma once
 #include <cstdint>
 
+#include "snapmi_options.hpp"
 #include "snapmi_pool.hpp"
 
 namespace snapmi {
@@ -13,32 +14,17 @@ namespace snapmi {
 // wavefronts per workgroup of the window kernel, of k_match_spans_8k and of
 // k_match_both (all of it, and its lane wavefronts); streams under these
 // lengths are k_compress_tiny's / k_compress_small's (snapmi_kernels.hpp and
-// snapmi_tiny.hpp have the same numbers; a static_assert in snapmi_api.hip
+// snapmi_tiny.hpp have the same numbers; a static_assert in snapmi_launch.hip
 // ties them)
 constexpr uint32_t kRouteCompressWaves = 5, kRouteSmallTableWaves = 10;
 constexpr uint32_t kRouteBothWaves = 6, kRouteBothLaneWaves = 4;
 constexpr uint32_t kRouteTinyCompress = 256, kRouteSmallCompress = 2048;
 
-// the context's options that steer the route (snapmi_ctx.hpp says what each
-// one means)
-struct RouteOptions {
-    int compress_mode;
-    bool lds_order_ok;
+// what the route reads beside the context's options (snapmi_options.hpp says
+// what each of those means): the two facts of the device
+struct RouteDevice {
+    bool lds_order_ok; // the LDS order self-check passed (snapmi_ctx.hpp)
     uint32_t num_cus;
-    uint32_t lane_min_blocks, lane_segment_blocks;
-    uint32_t lane_waves_per_cu, lane_max_waves;
-    int lane_coresident;
-    uint64_t lane_coresident_min_blocks;
-    int small_table_kernel;
-    uint64_t small_table_min_blocks;
-    int small_batch_kernel;
-    int span_kernel, span_schedule;
-    uint32_t both_wave_cus;
-    int match_kernel;
-    int lane_speculate;
-    uint64_t lane_speculate_max_blocks;
-    int lane_overlap_encode;
-    int tiny_stream_kernel, small_stream_kernel;
 };
 
 // the wavefront-per-block kernels that match and encode in one pass
@@ -91,7 +77,7 @@ struct CompressRoute {
 // (k_compress_tiny under 256 bytes, k_compress_small under 1 KiB - under
 // 2 KiB with small_stream_kernel = 2) and get no blocks; 0: every stream goes
 // through the block kernels
-inline uint64_t small_stream_limit(const RouteOptions &o)
+inline uint64_t small_stream_limit(const Options &o)
 {
     if (!o.tiny_stream_kernel)
         return 0;
@@ -110,12 +96,12 @@ inline uint32_t window_grid(uint64_t count, uint64_t cus)
         (count + kRouteCompressWaves - 1) / kRouteCompressWaves, cus);
 }
 
-inline uint32_t lane_count(const RouteOptions &o, uint64_t seg_blocks,
-                           bool both_cores)
+inline uint32_t lane_count(const Options &o, const RouteDevice &d,
+                           uint64_t seg_blocks, bool both_cores)
 {
     // waves of the lane-per-block match finder: a few per CU saturate the
     // random-access rate of HBM; never more lanes than blocks
-    uint64_t waves = (uint64_t)o.num_cus * o.lane_waves_per_cu;
+    uint64_t waves = (uint64_t)d.num_cus * o.lane_waves_per_cu;
     const uint64_t need = (seg_blocks + 63) / 64;
     if (waves > need)
         waves = need ? need : 1;
@@ -124,15 +110,16 @@ inline uint32_t lane_count(const RouteOptions &o, uint64_t seg_blocks,
     // k_match_both: its lane wavefronts on every CU, beside two of the
     // window kernel
     if (both_cores)
-        waves = (uint64_t)o.num_cus * kRouteBothLaneWaves;
+        waves = (uint64_t)d.num_cus * kRouteBothLaneWaves;
     return (uint32_t)waves * 64;
 }
 
 // spans_hint: the context's last batch compressed to no less than
 // match_spans_ratio_pct of its input (read by the caller; only
 // match_kernel 2 follows it)
-inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
-                                    uint64_t cnt8, bool spans_hint)
+inline CompressRoute compress_route(const Options &o, const RouteDevice &d,
+                                    uint64_t blocks, uint64_t cnt8,
+                                    bool spans_hint)
 {
     CompressRoute r;
     r.seg_blocks = segment_blocks(blocks, o.lane_segment_blocks);
@@ -150,7 +137,7 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
     // blocks of at most 4 KiB were built too and measured the same: at ten
     // wavefronts the CU's one scalar unit is 70 % busy.)
     const uint64_t nb_small = min_u64(cnt8, blocks);
-    const bool small = o.lds_order_ok && o.compress_mode == 1 &&
+    const bool small = d.lds_order_ok && o.compress_mode == 1 &&
                        o.small_table_kernel &&
                        nb_small >= o.small_table_min_blocks;
     r.nb_big = small ? blocks - nb_small : blocks;
@@ -158,11 +145,11 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
     // The token path: a device that failed the LDS order self-check only has
     // the lane kernel; the small-block kernel runs on it too, with the
     // window kernel as the match finder of a batch that is not big.
-    r.tokens = !o.lds_order_ok || (o.compress_mode != 0 && big) || small;
+    r.tokens = !d.lds_order_ok || (o.compress_mode != 0 && big) || small;
     // (segment_blocks: equal launches that bound the token scratch; "both at
     // once" needs the whole list in one segment)
     const bool window =
-        o.lds_order_ok &&
+        d.lds_order_ok &&
         (!r.tokens || o.compress_mode == 0 ||
          (o.compress_mode == 2 && r.seg_blocks == blocks));
     if (window) {
@@ -175,11 +162,11 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
         // flight; five tables per CU from there
         const bool lds_input =
             o.small_batch_kernel == 2 ||
-            (o.small_batch_kernel == 1 && blocks <= 2 * (uint64_t)o.num_cus);
+            (o.small_batch_kernel == 1 && blocks <= 2 * (uint64_t)d.num_cus);
         if (lds_input) {
             r.window = o.span_kernel ? WindowKernel::span_lds
                                      : WindowKernel::block_lds;
-            r.window_grid = (uint32_t)min_u64(blocks, o.num_cus);
+            r.window_grid = (uint32_t)min_u64(blocks, d.num_cus);
         } else {
             r.window = o.span_kernel ? WindowKernel::spans
                                      : WindowKernel::blocks;
@@ -187,8 +174,8 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
             // persistent workgroup owns its CU's whole LDS)
             r.window_grid = window_grid(
                 blocks, r.window_beside ? (o.both_wave_cus ? o.both_wave_cus
-                                                           : o.num_cus / 2)
-                                        : o.num_cus);
+                                                           : d.num_cus / 2)
+                                        : d.num_cus);
             // several blocks per wavefront, the window kernel alone: the
             // order of the blocks is chosen as the launch goes (SpanSched,
             // snapmi_compress.hip: heavy streams first, light ones last - a
@@ -216,12 +203,12 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
     // does not compress costs a lane three HBM transactions per probe for
     // nothing (cfg5: 12 ms of lane kernel for 32 GiB against ~4 of windows).
     const bool span_match =
-        !window && o.lds_order_ok &&
+        !window && d.lds_order_ok &&
         (o.match_kernel == 1 || (small && !big) ||
          (o.match_kernel == 2 && spans_hint));
     // both match finders on every CU (k_match_both): launches that fill the
     // chip with lanes anyway
-    const bool both_cores = !window && !span_match && o.lds_order_ok &&
+    const bool both_cores = !window && !span_match && d.lds_order_ok &&
                             o.lane_coresident &&
                             r.nb_big >= o.lane_coresident_min_blocks;
     if (span_match)
@@ -230,11 +217,11 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
     else
         r.match = both_cores ? MatchKernel::both : MatchKernel::blocks;
     if (!span_match)
-        r.lanes = lane_count(o, r.seg_blocks, both_cores);
+        r.lanes = lane_count(o, d, r.seg_blocks, both_cores);
     if (small) // one 640-thread workgroup per CU: ten 16 KiB tables
         r.small_grid = (uint32_t)min_u64(
             (nb_small + kRouteSmallTableWaves - 1) / kRouteSmallTableWaves,
-            o.num_cus);
+            d.num_cus);
     // the window wavefronts' staging arrays (TokenWriter): one per wavefront
     // of the largest workgroup this call launches
     r.stage_waves = small ? kRouteSmallTableWaves
@@ -251,15 +238,15 @@ inline CompressRoute compress_route(const RouteOptions &o, uint64_t blocks,
 // workgroups of a match launch over `count` blocks of a segment (with the
 // small-block kernel on, the window kernel's share is the blocks of more
 // than 8 KiB: the whole batch's, whatever the segment)
-inline uint32_t match_grid(const RouteOptions &o, const CompressRoute &r,
+inline uint32_t match_grid(const RouteDevice &d, const CompressRoute &r,
                            uint64_t count)
 {
     switch (r.match) {
     case MatchKernel::spans:
         return window_grid(r.small_grid ? min_u64(r.nb_big, count) : count,
-                           o.num_cus);
+                           d.num_cus);
     case MatchKernel::both:
-        return o.num_cus;
+        return d.num_cus;
     case MatchKernel::blocks:
         return r.lanes / 64;
     default:
@@ -288,8 +275,8 @@ struct Segment {
     uint32_t redo_grid; // k_redo_spilled's workgroups
 };
 
-inline Segment segment(const RouteOptions &o, const CompressRoute &r,
-                       uint64_t lo, uint64_t hi)
+inline Segment segment(const Options &o, const RouteDevice &d,
+                       const CompressRoute &r, uint64_t lo, uint64_t hi)
 {
     Segment g;
     const uint64_t n = hi - lo;
@@ -302,7 +289,7 @@ inline Segment segment(const RouteOptions &o, const CompressRoute &r,
     g.mid = split ? lo + n / 2 : hi;
     g.spec = o.lane_speculate && n <= r.lanes &&
              n <= o.lane_speculate_max_blocks;
-    g.redo_grid = window_grid(n, o.num_cus);
+    g.redo_grid = window_grid(n, d.num_cus);
     return g;
 }
 
@@ -312,14 +299,16 @@ inline Segment segment(const RouteOptions &o, const CompressRoute &r,
 // where the launch runs none (match_kernel 1; a hint that picks
 // k_match_spans) or the reverse (compress_mode 0 on a device that failed the
 // LDS order self-check).
-inline uint32_t prepare_lanes(const RouteOptions &o, uint64_t blocks)
+inline uint32_t prepare_lanes(const Options &o, const RouteDevice &d,
+                              uint64_t blocks)
 {
     if (o.compress_mode == 0 || blocks < o.lane_min_blocks)
         return 0;
-    const bool both = o.compress_mode == 1 && o.lds_order_ok &&
+    const bool both = o.compress_mode == 1 && d.lds_order_ok &&
                       o.lane_coresident &&
                       blocks >= o.lane_coresident_min_blocks;
-    return lane_count(o, segment_blocks(blocks, o.lane_segment_blocks), both);
+    return lane_count(o, d, segment_blocks(blocks, o.lane_segment_blocks),
+                      both);
 }
 
 } // namespace snapmi

@@ -114,8 +114,8 @@ class Context:
         "write_blocks_decoded", "write_streams_ok", "write_streams_failed",
         "append_blocks", "append_blocks_decoded", "append_streams_ok",
         "append_streams_failed", "frame_nowait_front" (include/snapmi.h);
-        the test build also "scratch_fill_buffers", "scratch_fill_bytes",
-        "scratch_fill_seen" (include/snapmi_test.h)."""
+        the test build also "lane_multi_rounds", "scratch_fill_buffers",
+        "scratch_fill_bytes", "scratch_fill_seen" (include/snapmi_test.h)."""
         v = C.c_int64(0)
         rc = self._L.snapmi_ctx_get_info(self._h, name.encode(), C.byref(v))
         if rc:

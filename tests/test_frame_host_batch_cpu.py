@@ -303,13 +303,14 @@ def test_library_carries_the_list_kernel(built):
 
 
 def test_option_and_info_names_in_the_sources():
+    from test_options_cpu import options_table
+    T = options_table()
     header = (ROOT / "include" / "snapmi.h").read_text()
     test_h = (ROOT / "include" / "snapmi_test.h").read_text()
-    api = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_api.hip").read_text()
     assert '"host_batch_listed_slices"' in header
     assert '"host_batch_listed"' in test_h
-    for name in ("host_batch_listed_slices", "host_batch_listed"):
-        assert f'strcmp(name, "{name}") == 0' in api, name
+    assert T.has_info("host_batch_listed_slices")
+    assert T.has_option("host_batch_listed", test_only=True)
     for text in (header, ):
         assert "4b. Many independent framed streams in HOST memory" in text
 

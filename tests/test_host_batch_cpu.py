@@ -234,14 +234,18 @@ def test_library_carries_the_pack_kernel(built):
 
 def test_option_and_info_names_in_the_sources():
     """A context cannot be made without a GPU (the GPU suite sets and reads
-    them); what is checked here: the names the header documents are the names
-    the library compares with."""
+    them); what is checked here: the names the header documents are names of
+    the library's tables (csrc/snapmi_options.hpp)."""
+    from test_options_cpu import options_table
+    T = options_table()
     header = (ROOT / "include" / "snapmi.h").read_text()
-    api = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_api.hip").read_text()
     for name in ("host_batch_slice", "host_batch_slices",
                  "host_batch_h2d_bytes", "host_batch_d2h_bytes"):
         assert f'"{name}"' in header, name
-        assert f'strcmp(name, "{name}") == 0' in api, name
+    assert T.has_option("host_batch_slice", test_only=False)
+    for name in ("host_batch_slices", "host_batch_h2d_bytes",
+                 "host_batch_d2h_bytes"):
+        assert T.has_info(name), name
 
 
 def test_null_context_names_are_refused(built):

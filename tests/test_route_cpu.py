@@ -3,7 +3,7 @@ a batch runs for the options a context holds - DESIGN 4.1's table.  The GPU
 suite forces each kernel with options and so tests the kernels; here the
 choice the defaults make, and the choice every `cctx` configuration of
 tests/conftest.py makes, row by row.  Options are MI355X's: 256 CUs, a device
-that passed the LDS order self-check, snapmi_ctx.hpp's defaults."""
+that passed the LDS order self-check, snapmi_options.hpp's defaults."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -12,7 +12,7 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 
-# snapmi_ctx.hpp's defaults on an MI355X
+# snapmi_options.hpp's defaults on an MI355X, pinned
 MI355X = dict(compress_mode=1, lds_order_ok=1, num_cus=256,
               lane_min_blocks=20480, lane_segment_blocks=262144,
               lane_waves_per_cu=6, lane_max_waves=0, lane_coresident=1,
@@ -38,6 +38,9 @@ def P(tmp_path_factory):
                            "-o", str(so)])
     L = C.CDLL(str(so))
     u64, u32 = C.c_uint64, C.c_uint32
+    L.t_reset.restype = None
+    L.t_default.restype = C.c_int64
+    L.t_default.argtypes = [C.c_char_p]
     L.t_set.restype = C.c_int
     L.t_set.argtypes = [C.c_char_p, C.c_int64]
     L.t_route.restype = None
@@ -55,9 +58,26 @@ def P(tmp_path_factory):
     return L
 
 
+# what the context finds out about an MI355X (not options)
+DEVICE = dict(lds_order_ok=1, num_cus=256)
+
+
 def _set(P, opts):
-    for k, v in dict(MI355X, **opts).items():
+    """A fresh set of options - the table's own defaults - on an MI355X, then
+    `opts`."""
+    P.t_reset()
+    for k, v in dict(DEVICE, **opts).items():
         assert P.t_set(k.encode(), v) == 0, k
+
+
+def test_defaults_are_the_pinned_ones(P):
+    """The routes below start from the option table's defaults: they are the
+    values pinned here."""
+    for k, v in MI355X.items():
+        if k in DEVICE:
+            assert DEVICE[k] == v, k
+        else:
+            assert P.t_default(k.encode()) == v, k
 
 
 def route(P, blocks, cnt8=0, hint=False, **opts):

@@ -26,7 +26,8 @@ def _strip_comments(text):
 
 
 def _struct_body(text, name):
-    m = re.search(r"\bstruct\s+%s\s*\{" % re.escape(name), text)
+    # (the definition: a base list may stand before the brace)
+    m = re.search(r"\bstruct\s+%s\s*(?::[^;{]*)?\{" % re.escape(name), text)
     assert m, f"struct {name} not found"
     depth, i = 1, m.end()
     while depth:

@@ -68,7 +68,7 @@ struct UpdateScratch {
 
 } // namespace snapmi
 
-struct snapmi_host_pipe; // snapmi_frame.hip: staging of the host-buffer calls
+struct snapmi_host_pipe; // snapmi_hostpipe.hip: staging of the host-buffer calls
 
 // (the base: every knob, its default and what it means)
 struct snapmi_ctx : snapmi::Options {
@@ -181,10 +181,10 @@ struct snapmi_ctx : snapmi::Options {
     // descriptors - is one set: the calls follow each other on the stream.
     snapmi::UpdateScratch wr, ap;
     snapmi::ScratchDev up_z, up_slot, up_room, up_desc;
-    // frame layer scratch (snapmi_frame.hip)
+    // frame layer scratch (snapmi_frame.hip, its layouts: snapmi_frame.hpp)
     snapmi::ScratchDev fr_desc, fr_slots, fr_chunk_off;
     // kept: the CRC32C tables, filled once by ensure_tables
-    // (snapmi_frame.hip) when it gives them memory; fr_tables_ready says so
+    // (snapmi_crc.hip) when it gives them memory; fr_tables_ready says so
     snapmi::KeptDev fr_tables;
     // snapmi_crc32c_masked_batch: the long buffers' segment scan and
     // accumulators (sized from n alone)

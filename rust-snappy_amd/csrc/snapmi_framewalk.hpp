@@ -1,6 +1,6 @@
 // snapmi_framewalk.hpp -- the walk over the chunk headers of a framed stream
 // (reference FrameDecoder::read, src/read.rs:111-236), in plain C++ that the
-// kernels of snapmi_frame.hip, the host code of the host-memory batch calls
+// kernels of snapmi_framedec.hip, the host code of the host-memory batch calls
 // (snapmi_hostbatch.hip) and a CPU test (tests/framewalk_host.cpp) compile
 // alike:
 //

@@ -44,6 +44,7 @@
 #include "snapmi.h"
 #include "snapmi_ctx.hpp"
 #include "snapmi_hostpipe.hpp"
+#include "snapmi_frame.hpp"
 #include "snapmi_hostbatch.hpp"
 #include "snapmi_framewalk.hpp"
 #include "snapmi_device.hpp"

@@ -1,5 +1,5 @@
 // snapmi_hostpipe.hpp -- private: the three-slot staging pipeline of the
-// host-buffer calls (snapmi_frame.hip owns it; snapmi_hostbatch.hip shares
+// host-buffer calls (snapmi_hostpipe.hip owns it; snapmi_hostbatch.hip shares
 // it).
 //
 // A batch is cut into slices; slice i+1 is on its way to the device (copy
@@ -14,7 +14,7 @@
 #pragma once
 
 #include "snapmi_ctx.hpp"
-#include "snapmi_launch.hpp" // the launchers the frame layer calls
+#include "snapmi_launch.hpp" // pin_reserve and the codec's launchers
 
 namespace snapmi {
 
@@ -64,7 +64,7 @@ struct PipeDrain {
     }
 };
 
-// snapmi_frame.hip
+// snapmi_hostpipe.hip
 // the context's pipe, made on first use
 int host_pipe(snapmi_ctx *ctx, snapmi_host_pipe **out);
 // a slot's device buffer grows only when nothing of the slot is in flight
@@ -73,22 +73,5 @@ int slot_reserve(snapmi_ctx *ctx, DevBuf &b, size_t bytes);
 // by k_to_host (16-byte stores over the link) or by hipMemcpyAsync
 int pipe_copy_home(snapmi_ctx *ctx, hipStream_t st, uint8_t *h_dst,
                    const void *d_src, uint64_t n, bool by_kernel);
-// k_scan_u64 (the strided one-workgroup scan of snapmi_scan.hpp):
-// out[0..n) = exclusive scan of in[0..n), out[n] = total
-int launch_scan_u64(snapmi_ctx *ctx, hipStream_t st, const uint64_t *in,
-                    uint64_t *out, uint32_t n);
-// snapmi_frame_decompress_batch of n streams the host has walked: d_first
-// [n + 1] and d_list [total] (FwEntry, snapmi_framewalk.hpp) replace the
-// device's walk and its wait; *d_bad (cleared by the caller) is raised when
-// the list disagrees with the bytes
-int frame_decompress_batch_listed(snapmi_ctx *ctx,
-                                  const void *const *d_in_ptrs,
-                                  const uint64_t *d_in_lens,
-                                  void *const *d_out_ptrs,
-                                  const uint64_t *d_out_caps,
-                                  uint64_t *d_out_lens, snapmi_error *d_errs,
-                                  size_t n, const uint64_t *d_first,
-                                  const void *d_list, uint64_t total,
-                                  uint32_t *d_bad);
 
 } // namespace snapmi

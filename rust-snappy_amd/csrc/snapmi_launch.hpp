@@ -64,7 +64,7 @@ inline int pin_reserve(snapmi_ctx *ctx, PinBuf &b, size_t bytes)
     return SNAPMI_OK;
 }
 
-void host_pipe_destroy(snapmi_ctx *ctx); // snapmi_frame.hip
+void host_pipe_destroy(snapmi_ctx *ctx); // snapmi_hostpipe.hip
 
 // snapmi_api.hip
 int release_batch_scratch(snapmi_ctx *ctx);

@@ -1,6 +1,6 @@
 // Host build of csrc/snapmi_framewalk.hpp for
 // tests/test_frame_host_batch_cpu.py: the chunk-header walk the kernels of
-// snapmi_frame.hip run, driven the way snapmi_hostbatch.hip drives it while it
+// snapmi_framedec.hip run, driven the way snapmi_hostbatch.hip drives it while it
 // stages a framed stream.
 #include <stdint.h>
 #include <stddef.h>

@@ -39,7 +39,7 @@ def test_names_in_the_sources():
     assert options_table().has_info("frame_nowait_front")
     shim = (ROOT / "shim" / "src" / "gpu.rs").read_text()
     assert re.search(r"pub const SNAPMI_FRAME_NO_WAIT: u32 = 4;", shim)
-    frame = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_frame.hip"
+    frame = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_framedec.hip"
              ).read_text()
     assert "k_frame_nowait_seal" in frame
     from rust_snappy_amd import frame as F
@@ -49,16 +49,23 @@ def test_names_in_the_sources():
 def test_flagged_path_has_no_wait_in_it():
     """The branch of snapmi_frame_decompress_ex the flag takes: no
     hipStreamSynchronize, no mailbox and no retry loop between its first line
-    and its return."""
-    frame = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_frame.hip"
+    and its return - nor in frame_front, the launcher of the fronts that the
+    branch shares with the retry loop."""
+    frame = (ROOT / "rust-snappy_amd" / "csrc" / "snapmi_framedec.hip"
              ).read_text()
     body = frame[frame.index("int snapmi_frame_decompress_ex("):]
     lo = body.index("    if (nowait) {")
     branch = body[lo:body.index("    for (int attempt", lo)]
     assert "return fbd_finish(ctx, b);" in branch
-    for word in ("hipStreamSynchronize", "h_mail", "k_post_words", "for (",
-                 "while (", "continue;"):
-        assert word not in branch, word
+    assert "frame_front(ctx, a, " in branch
+    at = frame.index("static int frame_front(")
+    front = frame[at:frame.index("\n}\n", at)]
+    for name in ("k_frame_index", "k_fw_candidates", "k_frame_walk"):
+        assert name in front, name
+    for text in (branch, front):
+        for word in ("hipStreamSynchronize", "h_mail", "k_post_words",
+                     "post_words", "for (", "while (", "continue;"):
+            assert word not in text, word
     assert "!nowait && (rc = mailbox(ctx))" in body[:lo]
 
 

@@ -142,7 +142,7 @@ def test_reserves_see_the_class():
                               "fill_new_dev(ctx, b)"),
                              ("snapmi_launch.hpp", "inline int pin_reserve(",
                               "fill_new_pin(ctx, b)"),
-                             ("snapmi_frame.hip", "int snapmi::slot_reserve(",
+                             ("snapmi_hostpipe.hip", "int snapmi::slot_reserve(",
                               "fill_new_dev(ctx, b)"),
                              ("snapmi_hostbatch.hip", "int pin_buf(",
                               "fill_new_pin(ctx, b)")):

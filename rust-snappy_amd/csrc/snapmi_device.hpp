@@ -10,19 +10,14 @@
 #include <stdint.h>
 
 #include "snapmi.h"
+#include "snapmi_block.hpp"
 #include "snapmi_piecelist.hpp"
 
 namespace snapmi {
 
 constexpr uint32_t kWave = 64;
-constexpr uint32_t kMaxBlock = 1u << 16;      // reference src/lib.rs:97
-constexpr uint32_t kMaxTable = 1u << 14;      // reference src/compress.rs:11
-constexpr uint32_t kInputMargin = 15;         // reference src/compress.rs:20
-constexpr uint32_t kMinNonLiteral = 17;       // reference src/compress.rs:24
-constexpr uint64_t kMaxInput = 0xFFFFFFFFull; // reference src/lib.rs:93
-// max_compress_len(65536) = 76490 (reference src/frame.rs:12), rounded up to
-// a multiple of 16 so scratch slots stay 16-byte aligned.
-constexpr uint32_t kSlotBytes = 76496;
+// (the codec's constants - kMaxBlock, kMaxTable, kSlotBytes ... - with
+// max_compress_len_u64 and varint_len: snapmi_block.hpp)
 
 // Explicit address spaces.  Pointers fetched from the descriptor arrays are
 // generic to the compiler; without these it emits flat_load/flat_store, which
@@ -127,25 +122,6 @@ __device__ __forceinline__ uint32_t ld32g(gcptr base, uint64_t pos,
         if (pos + k < avail)
             v |= (uint32_t)base[pos + k] << (8 * k);
     return v;
-}
-
-// max_compress_len, reference src/compress.rs:42-53.
-__host__ __device__ __forceinline__ uint64_t max_compress_len_u64(uint64_t n)
-{
-    if (n > kMaxInput)
-        return 0;
-    uint64_t m = 32 + n + n / 6;
-    return m > kMaxInput ? 0 : m;
-}
-
-__host__ __device__ __forceinline__ uint32_t varint_len(uint64_t n)
-{
-    uint32_t k = 1;
-    while (n >= 0x80) {
-        n >>= 7;
-        k++;
-    }
-    return k;
 }
 
 __device__ __forceinline__ void set_error(snapmi_error *errs, uint64_t i,

@@ -1,11 +1,15 @@
 // snapmi_kernels.hpp -- the codec's own kernels, as their launchers see them:
 // CompressArgs, the token constants, DecompressArgs and the declarations of
-// the kernels of snapmi_compress.hip and snapmi_decompress.hip.  (Every other
-// kernel is local to the file that launches it: snapmi_longstream.hip,
-// snapmi_index.hip, snapmi_update.hip.)
+// the kernels of the compressor's files (snapmi_compress.hip, _window.hip,
+// _lane.hip, _steps.hip) and of snapmi_decompress.hip.  (Every other kernel
+// is local to the file that launches it: snapmi_lanetables.hip,
+// snapmi_longstream.hip, snapmi_index.hip, snapmi_update.hip.)  The argument blocks and constants
+// are plain C++ (tests/test_block_cpu.py); the declarations are hipcc's alone.
 #pragma once
 
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include "snapmi.h"
@@ -34,7 +38,7 @@ struct CompressArgs {
     uint32_t *ticket; // device-wide block ticket counter, zeroed per launch
     // k_compress_spans alone on a batch of several blocks per wavefront:
     // the order of the blocks is chosen as the launch goes (SpanSched in
-    // snapmi_compress.hip); nullptr: blocks in ticket order
+    // snapmi_window.hip); nullptr: blocks in ticket order
     uint32_t *sched;
     // The token path (k_match_* -> k_encode_tokens): a block's tokens lie in
     // PAGES of kTokPage tokens that its match finder takes from one pool as
@@ -97,7 +101,7 @@ struct CompressArgs {
     // its offsets, one per 1024 streams / blocks; scan_part[parts] parks the
     // carry from the segment in front.  The same memory: the scans of a
     // batch run one behind the other (launch_block_index takes it last)
-    uint2 *plan_part;
+    uint32_t *plan_part;
     unsigned long long *scan_part;
     // streams of 1 .. small_limit - 1 bytes get no blocks: k_compress_tiny
     // (under 256 bytes, one per lane) and k_compress_small (under 2 KiB, a
@@ -202,17 +206,14 @@ struct DecompressArgs {
     unsigned long long *prof;
 };
 
+#if defined(__HIPCC__)
 __global__ void k_probe_lds_order(uint32_t *bad);
-__global__ void k_zero16(unsigned long long *p, unsigned long long n);
 __global__ void k_seam_compress_tiny(const uint8_t *in, uint32_t n,
                                      uint8_t *out,
                                      unsigned long long *out_len,
                                      uint32_t *done, uint32_t seq);
 __global__ void k_seam_decompress_tiny(DecompressArgs a, uint32_t *done,
                                        uint32_t seq);
-__global__ void k_probe_tables(unsigned long long *tables,
-                               unsigned long long stride, uint32_t steps,
-                               uint32_t chunks, uint32_t per_chunk);
 __global__ void k_plan_compress(CompressArgs a);
 __global__ void k_plan_compress_a(CompressArgs a);
 __global__ void k_plan_compress_b(CompressArgs a, uint32_t nparts);
@@ -262,5 +263,6 @@ __global__ void k_decompress_small(DecompressArgs a); // ... under 512 bytes, 32
 constexpr uint32_t kManyStreams = 16;
 __global__ void k_decompress_streams3_many(DecompressArgs a);
 __global__ void k_decompress_len(DecompressArgs a);
+#endif // __HIPCC__
 
 } // namespace snapmi

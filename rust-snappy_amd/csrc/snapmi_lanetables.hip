@@ -39,6 +39,50 @@ void free_lane_tables(snapmi_ctx *ctx)
 }
 
 // ---------------------------------------------------------------------
+// Placement probe for the lane tables (place_lane_tables, lane_table_tries):
+// the access pattern of k_match_blocks' probe rounds - every lane a chain of
+// dependent random 16-byte reads, each followed by a write to the same
+// entry, in its own 256 KiB table - without any of the parse.  Its duration
+// on a candidate region ranks that region for the real kernel.  The caller
+// zeroes the tables afterwards.
+// ---------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_probe_tables(unsigned long long *tables,
+                                                     unsigned long long stride,
+                                                     uint32_t steps,
+                                                     uint32_t chunks,
+                                                     uint32_t per_chunk)
+{
+    typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+    // (the lane kernel's own lane -> table map: CompressArgs::lane_chunks)
+    const uint32_t slot =
+        chunks ? (gid % chunks) * per_chunk + gid / chunks : gid;
+    g_u32x4 *t = (g_u32x4 *)tables + (uint64_t)slot * stride;
+    uint32_t state = gid * 2654435761u + 12345u;
+    for (uint32_t i = 0; i < steps; i++) {
+        const uint32_t h = (state * 0x1E35A7BDu) >> 18;
+        const u32x4 e = t[h];
+        t[h] = (u32x4){state, i, h, gid};
+        state = state * 1664525u + (e.x ^ e.y ^ e.z ^ e.w) + 1013904223u;
+    }
+    if (state == 0x12345678u) // keep the chain alive
+        t[0] = (u32x4){state, 0, 0, 0};
+}
+
+// n 16-byte entries to zero (the lane tables when they are mapped chunks:
+// nothing but a kernel is known to reach every such mapping)
+__global__ __launch_bounds__(256) void k_zero16(unsigned long long *p,
+                                                unsigned long long n)
+{
+    typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+    g_u32x4 *q = (g_u32x4 *)p;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 +
+                                threadIdx.x;
+         i < n; i += (unsigned long long)gridDim.x * 256)
+        q[i] = (u32x4){0, 0, 0, 0};
+}
+
+// ---------------------------------------------------------------------
 // The lane kernel's hash tables: one 256 KiB table of 16-byte entries per lane
 // in flight, allocated when a launch first needs more lanes than the context
 // has tables for.

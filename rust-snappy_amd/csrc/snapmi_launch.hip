@@ -278,7 +278,7 @@ int launch_compress(snapmi_ctx *ctx, const void *const *d_in_ptrs,
     a.blk_size = (uint32_t *)ctx->blk_size.p;
     a.blk_off = (uint64_t *)ctx->blk_off.p;
     // (the two scans never run at the same time: one buffer for both)
-    a.plan_part = (uint2 *)ctx->plan_part.p;
+    a.plan_part = (uint32_t *)ctx->plan_part.p;
     a.scan_part = (unsigned long long *)ctx->plan_part.p;
     a.n_streams = (uint32_t)n;
     a.host_blocks = (uint32_t)blocks;

@@ -44,7 +44,7 @@ struct Options {
     int compress_mode = 1;
     // k_compress_spans on more blocks than it has wavefronts: 1 (default) the
     // order of the blocks is chosen as the launch goes (SpanSched,
-    // snapmi_compress.hip), 0 ticket order, 2 scheduled whatever the count
+    // snapmi_window.hip), 0 ticket order, 2 scheduled whatever the count
     int span_schedule = 1;
     // 1: lane-kernel launches of at least lane_coresident_min_blocks blocks
     // run k_match_both - three lane wavefronts and two window wavefronts on

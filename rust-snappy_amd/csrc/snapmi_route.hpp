@@ -178,7 +178,7 @@ inline CompressRoute compress_route(const Options &o, const RouteDevice &d,
                                         : d.num_cus);
             // several blocks per wavefront, the window kernel alone: the
             // order of the blocks is chosen as the launch goes (SpanSched,
-            // snapmi_compress.hip: heavy streams first, light ones last - a
+            // snapmi_window.hip: heavy streams first, light ones last - a
             // launch ends with its small jobs)
             r.sched = !r.window_beside && o.span_kernel &&
                       (o.span_schedule == 2 ||

@@ -1,4 +1,4 @@
-// snapmi: the walk of k_compress_spans (snapmi_compress.hip) - the uniform
+// snapmi: the walk of k_compress_spans (snapmi_window.hpp) - the uniform
 // (scalar) half of a wavefront's step over a WINDOW of 63 consecutive
 // positions of its block.
 //
@@ -243,7 +243,7 @@ SNAPMI_LANE_FN bool span_fast_ok(const SpanState &st, const uint64_t hits,
 //   prev_bit(mask, t)    highest set bit < t (per lane, 0..63) or 64
 //   shr_lo(mask, i)      the low 32 bits of mask >> i (per lane, 0..63)
 //   count_cut()          a hook for the host test's statistics
-// snapmi_compress.hip instantiates it over the hardware, tests/
+// snapmi_window.hpp instantiates it over the hardware, tests/
 // span_wave_host.cpp over arrays of 64 - the same text - and
 // test_span_wave_cpu.py compares it with span_walk on random windows and the
 // streams it gives with the reference restatement's.

@@ -1,5 +1,5 @@
 """Round-level model of k_match_blocks / k_match_blocks_spec
-(rust-snappy_amd/csrc/snapmi_compress.hip): one lane, one block.
+(rust-snappy_amd/csrc/snapmi_lane.hip): one lane, one block.
 
 What is modelled is the order of table reads and writes inside a round - the
 entry of this round's probe and, with `spec`, the entry of the probe that

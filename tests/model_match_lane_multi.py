@@ -1,5 +1,5 @@
 """Round-level model of the lane match finder with up to four probes a round
-(match_blocks in rust-snappy_amd/csrc/snapmi_compress.hip): one lane, one
+(match_blocks in rust-snappy_amd/csrc/snapmi_lane.hip): one lane, one
 block.  tests/model_match_lane.py stays the model of the plain and the
 two-probe round; this one takes a depth of 1..4 and a round at which the depth
 changes from 1 to `depth`, in the middle of a block or not.

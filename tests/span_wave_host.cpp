@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: k_compress_spans (rust-snappy_amd/csrc/snapmi_compress.hip)
+// TEST INFRASTRUCTURE: k_compress_spans (rust-snappy_amd/csrc/snapmi_window.hpp)
 // on the host.  The uniform half of a step - span_walk() of
 // rust-snappy_amd/csrc/snapmi_span.hpp, the very text the kernel compiles - runs
 // as it is; the 64 lanes around it (hash, the lane-ordered table exchange,

@@ -117,6 +117,38 @@ def test_compress_block_edges(cctx):
         assert c == O.compress(d), len(d)
 
 
+_LOCATION_SHAPES = None
+
+
+def location_shapes():
+    """The batches of tests/test_block_cpu.py that every kernel has to locate
+    right - one-block streams only (the lookup's shortcut), one-block streams
+    around a multi-block one, streams without blocks in between - as
+    (inputs, the oracle's bytes), made once.  Contents as in
+    test_compress_block_edges: text (alice29.txt, twice over for the one
+    stream that is longer than the file) and zero bytes in turn."""
+    global _LOCATION_SHAPES
+    if _LOCATION_SHAPES is None:
+        B = 65536
+        text = (O.CORPUS / "alice29.txt").read_bytes() * 2
+        _LOCATION_SHAPES = []
+        for lens in ([1, B, 17, B - 1] * 8,
+                     [B] * 5 + [3 * B + 1] + [B] * 5,
+                     [0, B + 1, 0, 0, 2 * B, 5]):
+            # (zeros: every fourth stream, and the two-block one)
+            ins = [b"\x00" * n if i % 4 == 3 or n == 2 * B else text[:n]
+                   for i, n in enumerate(lens)]
+            _LOCATION_SHAPES.append((ins, [O.compress(d) for d in ins]))
+    return _LOCATION_SHAPES
+
+
+def test_compress_block_location_shapes(cctx):
+    for ins, want in location_shapes():
+        got = gpu_compress(cctx, ins)
+        for i, (w, c) in enumerate(zip(want, got)):
+            assert c == w, ([len(d) for d in ins], i)
+
+
 def test_decompress_corpus_and_kats(ctx):
     rnd = O.corpus_round()
     comps = [O.compress(d) for _, d in rnd]
@@ -668,7 +700,7 @@ def test_lane_table_epoch_wrap(built):
     """The lane kernel never zeroes its HBM hash tables: entries carry a
     16-bit epoch and a lane bumps its epoch per block.  After 65 535 blocks on
     one lane the epoch wraps: the table is really cleared and the epoch
-    restarts at 1 (snapmi_compress.hip, `if (epoch == 0)`).  Epochs persist in
+    restarts at 1 (snapmi_lane.hip, `if (epoch == 0)`).  Epochs persist in
     the context, so a long-lived context gets there.  The option
     lane_epoch_preset starts every lane shortly before the wrap; stale entries
     of epochs 1, 2, ... left by the earlier batch must not come back to life

@@ -2,7 +2,7 @@
 a decision, and the parser that proves they do - TEST INFRASTRUCTURE, pure
 Python, no GPU.
 
-The token path (rust-snappy_amd/csrc/snapmi_compress.hip) hands
+The token path (rust-snappy_amd/csrc/snapmi_lane.hip, snapmi_window.hpp) hands
 k_encode_tokens the reference's greedy parse as tokens (literal, copy,
 offset): four bytes each in pages of 512, the ones that do not fit (literal
 >= 1 024, copy > 64) in an exception list in pages of 256.  tokens() reads
@@ -148,7 +148,7 @@ def pages(toks):
 def token_parts(L, C, O):
     """The reference's emit rules for one token (emit_literal,
     src/compress.rs:433-474; emit_copy, :323-369) as the arithmetic
-    token_bytes() and TokenSink::flush() of snapmi_compress.hip carry:
+    token_bytes() and TokenSink::flush() of snapmi_compress_dev.hpp carry:
     (literal tag bytes, copies of 64, copies of 60, last piece's length, last
     piece's bytes)."""
     lt = 0 if L == 0 else (1 if L <= 60 else (2 if L <= 256 else 3))

@@ -23,6 +23,7 @@ import blockindex_ref as B
 import foreign
 import kats
 import oracle_lib as O
+import tiled_batch as TB
 from gpu_buffers import Slab, hostile, read_errs, u64
 
 pytestmark = pytest.mark.gpu
@@ -442,6 +443,12 @@ def test_index_of_more_streams_than_one_workgroup_scans(ctx):
     assert first.cpu().tolist() == want_first
     assert idx.cpu().tolist() == want
     assert enc.lens.tolist() == [len(cache[d][1]) for d in datas]
+    kinds = list(cache)
+    at = {d: k for k, d in enumerate(kinds)}
+    assert TB.assert_all(enc.data, enc.offsets, enc.lens,
+                         [at[d] for d in datas],
+                         [cache[d][1] for d in kinds],
+                         what="20 000 streams compressed") == n
     dec, out_lens, errs = batch.decompress(ctx, enc, caps=lens,
                                            index=(first, idx))
     assert ctx.info("index_streams_pieced") == 6
@@ -488,10 +495,11 @@ def test_planner_and_index_at_the_workgroup_seams(ctx, seam_payloads, n):
     assert first.cpu().tolist() == want_first
     assert idx.cpu().tolist() == want
     assert enc.lens.tolist() == [len(seam_payloads[size][2]) for size in lens]
-    sample = sorted({i for c in (0, 1023, 1024, 2048, 16383, 16384, 17407, n - 1)
-                     for i in range(c - 5, c + 6) if 0 <= i < n})
-    for i in sample:
-        assert enc.stream_bytes(i) == seam_payloads[lens[i]][2], i
+    sizes = list(seam_payloads)
+    assert TB.assert_all(enc.data, enc.offsets, enc.lens,
+                         [sizes.index(size) for size in lens],
+                         [seam_payloads[size][2] for size in sizes],
+                         what=f"{n} streams compressed") == n
     dec, out_lens, errs = batch.decompress(ctx, enc, caps=lens,
                                            index=(first, idx))
     assert out_lens.tolist() == lens and all(e[0] == 0 for e in errs)

@@ -13,6 +13,7 @@ import pytest
 import kats
 from conftest import ROOT, SCAN_GEOMETRIES, set_scan_geometry
 import oracle_lib as O
+import tiled_batch as TB
 
 pytestmark = pytest.mark.gpu
 
@@ -895,12 +896,35 @@ class _FreeMemoryPoll:
         self._t.join()
 
 
+_BUDGET_WANT = []
+
+
 def _budget_batch():
+    """(the batch on the device, each stream's payload number, the oracle's
+    bytes of the 40 payloads - made once per process)."""
     from rust_snappy_amd import batch
     blob = b"".join(d for _, d in O.corpus_round())
     blocks = [blob[o:o + 65536] for o in range(0, 40 * 65536, 65536)]
-    ins = [blocks[i % 40] for i in range(16500)]          # ~1 GiB, one block each
-    return ins, batch.StreamBatch.from_bytes(ins)
+    if not _BUDGET_WANT:
+        _BUDGET_WANT.extend(O.compress(b) for b in blocks)
+    kind = np.arange(16500) % 40
+    ins = [blocks[k] for k in kind]                       # ~1 GiB, one block each
+    return batch.StreamBatch.from_bytes(ins), kind, _BUDGET_WANT
+
+
+def _assert_every_stream(what, dst, lens, errs, kind, want):
+    """All lengths, error records and bytes of a batch.compress result, on
+    the device; says how many streams that were."""
+    t0 = time.perf_counter()
+    n = TB.assert_all(dst.data, dst.offsets, lens, kind, want, errs=errs,
+                      what=what)
+    assert n == len(kind)
+    print(f"\n{what}: {n} streams compared in "
+          f"{time.perf_counter() - t0:.2f} s")
+    # (the comparison's buffers go back to the driver: the tests of this file
+    # that watch the free memory see what they saw without it)
+    import torch
+    torch.cuda.empty_cache()
 
 
 def test_block_offsets_carry_into_a_second_large_segment(built):
@@ -929,13 +953,7 @@ def test_block_offsets_carry_into_a_second_large_segment(built):
         c.close()
     assert all(e[0] == 0 for e in errs)
     assert [int(x) for x in lens] == [len(want[k]) for k in kind]
-    sample = sorted({i for s in (0, 1024, 16384, 19999, 20000, 20001, 21024,
-                                 36384, 39999)
-                     for i in range(s - 2, s + 3) if 0 <= i < n}
-                    | set(range(0, n, 997)))
-    assert {19999, 20000, 20001, 39999} <= set(sample)
-    for i in sample:
-        assert dst.stream_bytes(i, lens[i]) == want[kind[i]], i
+    _assert_every_stream("two segments of 20 000", dst, lens, errs, kind, want)
 
 
 @pytest.mark.parametrize("lib", ["test", "product", "product-plain"])
@@ -965,7 +983,7 @@ def test_lane_table_placement_stays_within_its_budget(built, pct, lib):
     else:
         c = _lane_ctx()
     c.set_option("lane_table_budget_pct", pct)
-    ins, src = _budget_batch()
+    src, kind, want = _budget_batch()
     torch.cuda.synchronize()
     free1, _ = torch.cuda.mem_get_info()
     with _FreeMemoryPoll() as poll:
@@ -987,9 +1005,8 @@ def test_lane_table_placement_stays_within_its_budget(built, pct, lib):
     assert poll.samples > 20
     assert free1 - poll.low <= budget + (6 << 30), \
         (free1, poll.low, budget, log)
-    for i in (0, 39, 16499):
-        assert errs[i][0] == 0
-        assert dst.stream_bytes(i, lens[i]) == O.compress(ins[i])
+    _assert_every_stream(f"{lib} at {pct} %, {c.last_kernel()}, "
+                         f"{m.group(5)} lanes", dst, lens, errs, kind, want)
     free2, _ = torch.cuda.mem_get_info()
     assert free1 - free2 <= kept + (6 << 30), (free1, free2, kept)
     c.close()
@@ -1005,13 +1022,14 @@ def test_prepare_places_the_tables_ahead_of_the_first_batch(built):
     import torch
     from conftest import product_context
     from rust_snappy_amd import batch
-    ins, src = _budget_batch()
+    src, kind, want = _budget_batch()
+    n = len(kind)
     for top in (False, True):
         c = product_context()
         c.set_option("lane_min_blocks", 1)
         torch.cuda.synchronize()
         free1, _ = torch.cuda.mem_get_info()
-        c.prepare(len(ins), top_of_memory=top)
+        c.prepare(n, top_of_memory=top)
         log = c.table_probe_log()
         m = re.search(r"kept (\d+) KiB apart, (\d+) lanes, (\d+) bytes", log)
         assert m and int(m.group(2)) >= 16384, log
@@ -1024,9 +1042,9 @@ def test_prepare_places_the_tables_ahead_of_the_first_batch(built):
         dst, lens, errs = batch.compress(c, src)
         c.synchronize()
         assert c.table_probe_log() == log         # nothing placed again
-        for i in (0, 39, 16499):
-            assert errs[i][0] == 0
-            assert dst.stream_bytes(i, lens[i]) == O.compress(ins[i])
+        _assert_every_stream(f"prepared{' at the top' if top else ''}, "
+                             f"{c.last_kernel()}, {m.group(2)} lanes", dst,
+                             lens, errs, kind, want)
         c.close()
     # below lane_min_blocks there is nothing to prepare
     c = product_context()
@@ -1044,8 +1062,8 @@ def test_token_pool_spills_are_compressed_again_and_the_pool_grows(built):
     of one-block streams: the lane kernel beside the window kernel)."""
     from conftest import product_context
     from rust_snappy_amd import batch
-    ins, src = _budget_batch()
-    n = len(ins)
+    src, kind, want = _budget_batch()
+    n = len(kind)
     c = product_context()
     c.set_option("lane_min_blocks", 1)
     c.set_option("token_pool_min_pages", 0)
@@ -1056,9 +1074,8 @@ def test_token_pool_spills_are_compressed_again_and_the_pool_grows(built):
         spilled = c.info("token_blocks_spilled")
         seen.append((c.info("token_pool_pages"), spilled,
                      c.info("token_pages_asked")))
-        for i in list(range(0, n, 397)) + [n - 1]:
-            assert errs[i][0] == 0
-            assert dst.stream_bytes(i, lens[i]) == O.compress(ins[i]), i
+        _assert_every_stream(f"pool of {seen[-1][0]} pages, {spilled} "
+                             f"blocks spilled", dst, lens, errs, kind, want)
         if len(seen) > 1 and seen[-2][1] == 0:
             break                        # two calls without a spilled block
     pages = [p for p, _, _ in seen]
@@ -1077,31 +1094,52 @@ def test_token_pool_spills_are_compressed_again_and_the_pool_grows(built):
     c.set_option("token_pool_pct", 100)
     dst, lens, errs = batch.compress(c, src)
     assert c.info("token_blocks_spilled") == 0
-    assert dst.stream_bytes(n - 1, lens[n - 1]) == O.compress(ins[n - 1])
+    _assert_every_stream("pool of 100 %", dst, lens, errs, kind, want)
     c.close()
+
+
+_MANY_SMALL = []
+
+
+def _many_small_streams():
+    """40 000 streams of mixed sizes - some 32 000 distinct slices of the
+    corpus - and the oracle's bytes of every one: made once per process, for
+    every `cctx` (the oracle takes four to five seconds for all of them;
+    print below)."""
+    if not _MANY_SMALL:
+        rng = random.Random(2024)
+        blob = b"".join(d for _, d in O.corpus_round())
+        kinds = [0, 1, 7, 200, 200, 200, 1000, 4096, 70000, 140000]
+        ins = []
+        for i in range(40000):
+            n = kinds[i % len(kinds)] if i % 97 else rng.randrange(0, 3000)
+            o = rng.randrange(0, len(blob) - 150000)
+            ins.append(blob[o:o + n])
+        t0 = time.perf_counter()
+        want = TB.Expected([O.compress(x) for x in ins])
+        print(f"\nthe oracle's bytes of {len(ins)} streams: "
+              f"{time.perf_counter() - t0:.1f} s, once")
+        _MANY_SMALL.extend([ins, want])
+    return _MANY_SMALL
 
 
 def test_many_small_streams_plan_on_many_workgroups(cctx, ctx):
     """Batches of more than 16 384 streams are planned, scanned and sorted by
     many workgroups (k_plan_compress_a/b/c, k_scan_sizes_a/b/c,
     k_plan_decompress_a/b/c): 40 000 streams of mixed sizes - empty ones, tiny
-    ones, some of several blocks - against the oracle, both directions."""
+    ones, some of several blocks - against the oracle, both directions, every
+    stream of them."""
     from rust_snappy_amd import batch
-    rng = random.Random(2024)
-    blob = b"".join(d for _, d in O.corpus_round())
-    kinds = [0, 1, 7, 200, 200, 200, 1000, 4096, 70000, 140000]
-    ins = []
-    for i in range(40000):
-        n = kinds[i % len(kinds)] if i % 97 else rng.randrange(0, 3000)
-        o = rng.randrange(0, len(blob) - 150000)
-        ins.append(blob[o:o + n])
+    ins, want = _many_small_streams()
+    every = np.arange(len(ins))
     src = batch.StreamBatch.from_bytes(ins)
     dst, lens, errs = batch.compress(cctx, src)
     assert all(e[0] == 0 for e in errs)
-    check = list(range(0, 40000, 613)) + [0, 1, 39998, 39999]
-    want = {i: O.compress(ins[i]) for i in check}
-    for i in check:
-        assert dst.stream_bytes(i, lens[i]) == want[i], i
+    try:
+        _assert_every_stream("40 000 streams compressed", dst, lens, errs,
+                             every, want)
+    finally:
+        want.drop()
     # every stream's size: the oracle's size function is its compressor, so
     # compare sizes of equal inputs among themselves instead
     by_input = {}
@@ -1109,6 +1147,7 @@ def test_many_small_streams_plan_on_many_workgroups(cctx, ctx):
         by_input.setdefault(x, set()).add(int(lens[i]))
     assert all(len(v) == 1 for v in by_input.values())
     comp = batch.StreamBatch(dst.data, dst.offsets, lens)
+    inputs = TB.Expected.in_slab(src.data, src.offsets, src.lens)
     # (second pass: k_decompress_streams3_many, 16 streams of the sorted order
     # per workgroup - the kernel of batches of more than a million streams)
     for many_min in (1 << 20, 1000):
@@ -1116,8 +1155,8 @@ def test_many_small_streams_plan_on_many_workgroups(cctx, ctx):
         back, blens, derrs = batch.decompress(ctx, comp)
         assert all(e[0] == 0 for e in derrs)
         assert [int(x) for x in blens] == [len(x) for x in ins]
-        for i in check:
-            assert back.stream_bytes(i, blens[i]) == ins[i], i
+        _assert_every_stream(f"40 000 streams decoded, decode_many_min "
+                             f"{many_min}", back, blens, derrs, every, inputs)
     # errors come through it as well: damage three streams (1 000, 4 096 and
     # 70 000 bytes: their headers then promise more than the buffers hold)
     bad = [16, 20007, 39988]

@@ -13,6 +13,7 @@
 
 #include <stdint.h>
 
+#include "snapmi_element.hpp"
 #include "snapmi_kernels.hpp"
 #include "snapmi_tiny.hpp" // SNAPMI_LANE_FN
 
@@ -22,7 +23,7 @@ constexpr uint32_t kMaxBlock = 1u << 16;      // reference src/lib.rs:97
 constexpr uint32_t kMaxTable = 1u << 14;      // reference src/compress.rs:11
 constexpr uint32_t kInputMargin = 15;         // reference src/compress.rs:20
 constexpr uint32_t kMinNonLiteral = 17;       // reference src/compress.rs:24
-constexpr uint64_t kMaxInput = 0xFFFFFFFFull; // reference src/lib.rs:93
+// (kMaxInput, reference src/lib.rs:93: snapmi_element.hpp)
 // max_compress_len(65536) = 76490 (reference src/frame.rs:12), rounded up to
 // a multiple of 16 so scratch slots stay 16-byte aligned.
 constexpr uint32_t kSlotBytes = 76496;

@@ -27,6 +27,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "snapmi_element.hpp" // elem_step
+
 #if defined(__HIPCC__)
 #define SNAPMI_BI_HD __host__ __device__
 #else
@@ -677,8 +679,9 @@ SNAPMI_BI_HD inline size_t bi_update_groups(const uint32_t *b0,
 // Building the index of a stream that came without one
 // (snapmi_build_block_index): a walk from element to element that notes where
 // the chain stands when exactly k * 64 KiB have been produced.  bi_build is
-// the definition; the kernels (the scan's cuts in snapmi_decompress.hip and
-// k_index_walk in snapmi_index.hip) must reproduce it.
+// the definition; the kernels (the scan's cuts in snapmi_longstream.hip and
+// k_index_walk in snapmi_index.hip) must reproduce it.  The hop over one
+// element is elem_step of snapmi_element.hpp.
 //
 // The walk reads tag bytes and literal length bytes only.  Copy offsets are
 // not looked at: the builder finds boundaries, it does not say whether the
@@ -688,41 +691,6 @@ constexpr int kBiBuilt = 1;     // SNAPMI_INDEX_BUILT: entries as compress write
 constexpr int kBiUnaligned = 2; // ... _UNALIGNED: whole, but an element straddles a boundary
 constexpr int kBiCorrupt = 3;   // ... _CORRUPT: no header, or the chain does not end at (in_len, dlen)
 constexpr int kBiMissized = 4;  // ... _MISSIZED: not the lengths the host's copies said
-
-// hop over the element at p (elem_step of snapmi_decompress.hip, over any
-// source of bytes: at(i) is byte i of the stream); false if it does not fit
-template <class At>
-SNAPMI_BI_HD inline bool bi_elem_step(At &&at, uint64_t in_len, uint64_t &p,
-                                      uint64_t &out)
-{
-    const uint32_t tag = at(p);
-    const uint32_t type = tag & 3;
-    if (type == 0) {
-        const uint32_t n6 = tag >> 2;
-        uint64_t len = n6 + 1, hd = 1;
-        if (n6 >= 60) {
-            const uint32_t nb = n6 - 59;
-            if (p + 1 + nb > in_len)
-                return false;
-            uint32_t v = 0;
-            for (uint32_t k = 0; k < nb; k++)
-                v |= (uint32_t)at(p + 1 + k) << (8 * k);
-            len = (uint64_t)v + 1;
-            hd = 1 + nb;
-        }
-        if (in_len - (p + hd) < len)
-            return false;
-        p += hd + len;
-        out += len;
-    } else {
-        const uint32_t cnb = type == 1 ? 1 : (type == 2 ? 2 : 4);
-        if (p + 1 + cnb > in_len)
-            return false;
-        p += 1 + cnb;
-        out += type == 1 ? 4 + ((tag >> 2) & 7) : 1 + (tag >> 2);
-    }
-    return true;
-}
 
 // The walk of a stream of two blocks and more whose header (hdr bytes) has
 // been read: put(k, p) for every interior k (0 < k < blocks) at which an
@@ -749,7 +717,7 @@ SNAPMI_BI_HD inline int bi_walk(At &&at, uint64_t in_len, uint32_t hdr,
             k++;
         }
         // (out <= dlen < 2^32 here: the sums below cannot wrap)
-        if (!bi_elem_step(at, in_len, p, out) || out > dlen)
+        if (!elem_step(at, in_len, p, out) || out > dlen)
             return kBiCorrupt;
     }
     if (p != in_len || out != dlen)

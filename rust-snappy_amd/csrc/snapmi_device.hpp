@@ -11,6 +11,7 @@
 
 #include "snapmi.h"
 #include "snapmi_block.hpp"
+#include "snapmi_element.hpp"
 #include "snapmi_piecelist.hpp"
 
 namespace snapmi {
@@ -128,14 +129,28 @@ __device__ __forceinline__ void set_error(snapmi_error *errs, uint64_t i,
                                           int kind, uint64_t a, uint64_t b,
                                           uint64_t c)
 {
-    if (errs) {
-        errs[i].kind = kind;
-        errs[i].reserved = 0;
-        errs[i].a = a;
-        errs[i].b = b;
-        errs[i].c = c;
-    }
+    elem_fail(errs, i, kind, a, b, c);
 }
+
+// A stream of the batch decoder is finished: its error (or SNAPMI_OK) and the
+// bytes it produced - none where it failed.
+__device__ __forceinline__ void stream_done(snapmi_error *errs,
+                                            uint64_t *out_lens, uint64_t i,
+                                            int kind, uint64_t a, uint64_t b,
+                                            uint64_t c, uint64_t out_len)
+{
+    set_error(errs, i, kind, a, b, c);
+    out_lens[i] = out_len;
+}
+
+// ... with an error, inside a decoder that has `a` and `st`: `who` writes it
+// (lane 0 of a wavefront; a lane with a stream of its own), all return `ret`.
+#define SNAPMI_FAIL(who, ret, kind, fa, fb, fc)                               \
+    do {                                                                      \
+        if (who)                                                              \
+            stream_done(a.errs, a.out_lens, st, (kind), (fa), (fb), (fc), 0); \
+        return ret;                                                           \
+    } while (0)
 
 // Slot k of a piece-descriptor list (snapmi_piecelist.hpp) as whoever cuts
 // the pieces hands it to the batch decoder: these in_len bytes into this room
@@ -182,46 +197,19 @@ __device__ __forceinline__ bool piece_whole(const PieceList &l, uint64_t k)
            l.c_outlen[k] == l.c_cap[k];
 }
 
-// reference bytes::read_varu64, src/bytes.rs:73-90 (returns header length,
-// 0 = invalid).  Executed redundantly by every lane on uniform data.
+// varint_read / header_read of snapmi_element.hpp over global memory
+// (executed redundantly by every lane on uniform data)
 __device__ __forceinline__ uint32_t read_varint(gcptr p, uint64_t n,
                                                 uint64_t *value)
 {
-    uint64_t acc = 0;
-    uint32_t shift = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint32_t b = p[i];
-        if (shift >= 64)
-            return 0;
-        if (b < 0x80) {
-            *value = acc | ((uint64_t)b << shift);
-            return (uint32_t)i + 1;
-        }
-        acc |= (uint64_t)(b & 0x7F) << shift;
-        shift += 7;
-    }
-    return 0;
+    return varint_read(bytes_at(p), n, value);
 }
 
-// Header::read + the checks of Decoder::decompress, reference
-// src/decompress.rs:75-95,362-374.  Returns kind; on success fills hdr/dlen.
 __device__ __forceinline__ int read_header(gcptr in, uint64_t in_len,
                                            uint32_t *hdr, uint64_t *dlen,
                                            snapmi_error *errs, uint64_t i)
 {
-    uint64_t v = 0;
-    const uint32_t h = read_varint(in, in_len, &v);
-    if (h == 0) {
-        set_error(errs, i, SNAPMI_HEADER, 0, 0, 0);
-        return SNAPMI_HEADER;
-    }
-    if (v > kMaxInput) {
-        set_error(errs, i, SNAPMI_TOO_BIG, v, kMaxInput, 0);
-        return SNAPMI_TOO_BIG;
-    }
-    *hdr = h;
-    *dlen = v;
-    return SNAPMI_OK;
+    return header_read(bytes_at(in), in_len, hdr, dlen, errs, i);
 }
 
 // A 256-byte window of a byte stream held in one VGPR: lane i owns the dword
@@ -260,21 +248,6 @@ struct ByteWindow {
             refill(p);
         uint32_t o = (uint32_t)(p - base);
         return (uint32_t)(pair(o >> 2) >> (8 * (o & 3)));
-    }
-    // u64 at uniform stream offset p
-    __device__ __forceinline__ uint64_t get64(uint64_t p)
-    {
-        if (p < base || p - base > 240)
-            refill(p);
-        uint32_t o = (uint32_t)(p - base);
-        uint32_t i = o >> 2, r = 8 * (o & 3);
-        uint32_t w0 = rdlane(v, i);
-        uint32_t w1 = rdlane(v, i + 1);
-        uint32_t w2 = rdlane(v, i + 2);
-        uint64_t lo = ((uint64_t)w1 << 32) | w0;
-        if (r == 0)
-            return lo;
-        return (lo >> r) | ((uint64_t)w2 << (64 - r));
     }
 };
 

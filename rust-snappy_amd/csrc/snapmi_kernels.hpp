@@ -1,7 +1,8 @@
 // snapmi_kernels.hpp -- the codec's own kernels, as their launchers see them:
 // CompressArgs, the token constants, DecompressArgs and the declarations of
 // the kernels of the compressor's files (snapmi_compress.hip, _window.hip,
-// _lane.hip, _steps.hip) and of snapmi_decompress.hip.  (Every other kernel
+// _lane.hip, _steps.hip) and of the decoder's (snapmi_decompress.hip,
+// snapmi_wide.hip).  (Every other kernel
 // is local to the file that launches it: snapmi_lanetables.hip,
 // snapmi_longstream.hip, snapmi_index.hip, snapmi_update.hip.)  The argument blocks and constants
 // are plain C++ (tests/test_block_cpu.py); the declarations are hipcc's alone.

@@ -32,7 +32,7 @@ namespace snapmi {
 // the same bytes.  Segments -> super-segments (64 segments) -> one short
 // sequential pass over the super-segments -> the exact (src, dst) positions
 // of the element boundaries at every 64 KiB of output -> those pieces are
-// decoded by k_decompress_streams like independent streams.  Anything
+// decoded by k_decompress_streams3 like independent streams.  Anything
 // irregular (an element the scan cannot follow, a piece that fails one of
 // the reference's checks - which includes a copy reaching back into another
 // piece) sets meta[2] and the whole stream is decoded by the sequential
@@ -52,39 +52,6 @@ constexpr unsigned long long kNone = ~0ull;
 constexpr uint32_t kScanOverrun = 8192;
 
 typedef unsigned long long su64x2 __attribute__((ext_vector_type(2)));
-
-// hop over the element at p; false if it does not fit in the stream
-__device__ __forceinline__ bool elem_step(gcptr in, uint64_t in_len,
-                                          uint64_t &p, uint64_t &out)
-{
-    const uint32_t tag = in[p];
-    const uint32_t type = tag & 3;
-    if (type == 0) {
-        const uint32_t n6 = tag >> 2;
-        uint64_t len = n6 + 1, hd = 1;
-        if (n6 >= 60) {
-            const uint32_t nb = n6 - 59;
-            if (p + 1 + nb > in_len)
-                return false;
-            uint32_t v = 0;
-            for (uint32_t k = 0; k < nb; k++)
-                v |= (uint32_t)in[p + 1 + k] << (8 * k);
-            len = (uint64_t)v + 1;
-            hd = 1 + nb;
-        }
-        if (in_len - (p + hd) < len)
-            return false;
-        p += hd + len;
-        out += len;
-    } else {
-        const uint32_t cnb = type == 1 ? 1 : (type == 2 ? 2 : 4);
-        if (p + 1 + cnb > in_len)
-            return false;
-        p += 1 + cnb;
-        out += type == 1 ? 4 + ((tag >> 2) & 7) : 1 + (tag >> 2);
-    }
-    return true;
-}
 
 // level 1 = segments (4 KiB; 1 KiB for short streams: StreamArgs::seg_log2),
 // 2 = 64 of them, 3 = 64 of those
@@ -132,7 +99,7 @@ __device__ __forceinline__ bool reach_end<1>(const StreamArgs &a, uint64_t &p,
     if (end > a.in_len)
         end = a.in_len;
     while (p < end)
-        if (!elem_step((gcptr)a.in, a.in_len, p, out))
+        if (!elem_step(bytes_at((gcptr)a.in), a.in_len, p, out))
             return false;
     return true;
 }
@@ -277,7 +244,7 @@ __device__ __forceinline__ void stream_head(const StreamArgs &a, const uint32_t 
 //     takes the next walk instead of waiting for the longest.
 // Positions are 32-bit offsets from the wavefront's first segment; a chain
 // that a literal of a GiB takes out of that range finishes in the 64-bit
-// loop of the old kernel (elem_step, through HBM).
+// loop of the old kernel (elem_step of snapmi_element.hpp, through HBM).
 // Measured (one 2 GiB stream, profiles/r4_stream_scan_steps.txt): 8.07 ms ->
 // 2.0 ms; a wavefront is bound by the latency of its own dependent chain
 // (alone on the chip or not), the lanes of a round are busy to ~55 %.
@@ -344,23 +311,14 @@ struct Hopper {
     {
         slow = false;
         const uint64_t p = h.wbase + R;
-        const uint32_t tag = h.in[p];
-        const uint32_t nb = (tag >> 2) - 59;
-        if (p + 1 + nb > h.in_len) {
+        uint64_t q = p, qo = out;
+        if (!elem_step(bytes_at(h.in), h.in_len, q, qo)) {
             fail = true;
             return;
         }
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < nb; k++)
-            v |= (uint32_t)h.in[p + 1 + k] << (8 * k);
-        const uint64_t len = (uint64_t)v + 1;
-        if (h.in_len - (p + 1 + nb) < len) {
-            fail = true;
-            return;
-        }
+        const uint64_t len = qo - out;
         if (len + R >= kHopFar) {
             // out of the 32-bit range: the rest of the walk right here
-            uint64_t q = p + 1 + nb + len, qo = (uint64_t)out + len;
             const uint64_t end = h.wbase + endR;
             bool ok = true;
             while (ok && q < h.in_len &&
@@ -369,7 +327,7 @@ struct Hopper {
                     ok = false;
                     break;
                 }
-                ok = elem_step(h.in, h.in_len, q, qo);
+                ok = elem_step(bytes_at(h.in), h.in_len, q, qo);
             }
             punt = true;
             fail = !ok;
@@ -377,7 +335,7 @@ struct Hopper {
             out64 = qo;
             return;
         }
-        R += 1 + nb + (uint32_t)len;
+        R += (uint32_t)(q - p);
         out += (uint32_t)len;
         run = more(h) && R < stopR && out < stopOut;
     }
@@ -537,19 +495,11 @@ __device__ __forceinline__ void hop_pool(const HopShared &h, uint32_t npool,
 }
 
 // the table of tags: encoded bytes | produced bytes << 8, 0 for a literal
-// with length bytes
+// with length bytes (snapmi_element.hpp)
 __device__ __forceinline__ void hop_lut(uint16_t *lutbuf)
 {
     for (uint32_t t = threadIdx.x; t < 256; t += 64) {
-        const uint32_t type = t & 3, n6 = t >> 2;
-        uint32_t enc, prod;
-        if (type == 0) {
-            enc = n6 < 60 ? n6 + 2 : 0;
-            prod = n6 < 60 ? n6 + 1 : 0;
-        } else {
-            enc = type == 1 ? 2 : (type == 2 ? 3 : 5);
-            prod = type == 1 ? 4 + (n6 & 7) : 1 + n6;
-        }
+        const uint32_t enc = tag_encoded(t), prod = tag_produced(t);
         lutbuf[t] = (uint16_t)(enc | (prod << 8));
     }
     __syncthreads();

@@ -1,5 +1,6 @@
 """Lane-level model (numpy, 64-wide arrays) of the windowed wave decoder in
-rust-snappy_amd/csrc/snapmi_decompress.hip (k_decompress_streams, v2).
+rust-snappy_amd/csrc/snapmi_wide2.hpp (decode_windows2, the second
+generation).
 
 TEST INFRASTRUCTURE: the kernel's algorithm restated step by step so that its
 logic - speculative decode per byte, element starts by mask doubling, the

@@ -1,5 +1,5 @@
 """Lane-level model (numpy, 64-wide arrays) of k_decompress_streams3 in
-rust-snappy_amd/csrc/snapmi_decompress.hip: the third-generation wave decoder
+rust-snappy_amd/csrc/snapmi_wide3.hpp: the third-generation wave decoder
 (256 compressed bytes per window, one ELEMENT per lane).
 
 TEST INFRASTRUCTURE: the kernel's algorithm restated step by step so that its

@@ -1,4 +1,4 @@
-"""k_bstream_scan (rust-snappy_amd/csrc/snapmi_decompress.hip) as a model: the
+"""k_bstream_scan (rust-snappy_amd/csrc/snapmi_longstream.hip) as a model: the
 level-1 table of snapmi_decompress_stream - for every segment (SEG: 4 KiB, or
 1 KiB for the streams of a small call - StreamArgs::seg_log2) and every
 entry offset o < 8, where the chain that starts at byte o leaves the segment

@@ -201,6 +201,59 @@ def test_decompress_error_kats_exact_fields(ctx):
             assert (oe.kind, oe.a, oe.b, oe.c) == e, (name, e)
 
 
+def _oracle_error(comp, cap):
+    try:
+        O.decompress(comp, cap)
+    except O.SnapError as oe:
+        return (oe.kind, oe.a, oe.b, oe.c)
+    raise AssertionError("the oracle accepted a variant")
+
+
+@pytest.mark.parametrize("cls", ["lds", "short_wide", "small", "wide", "seq"])
+def test_error_kats_on_every_decoder(ctx, cls):
+    """Every error KAT on every restatement of the reference's loop
+    (tests/error_variants.py: a prefix of valid elements moves the KAT's
+    failing element into the stream class of k_decompress_tiny's staged loop,
+    of k_decompress_small, of the wavefront decoder - whose window loops hand
+    it to decode_sequential - and of k_decompress_sequential, decode_kernel
+    0).  Kind and fields are the oracle's on the very bytes sent; one batch
+    call per class, bad headers and the empty stream unchanged in each.
+    tests/test_element_cpu.py holds every variant to its KAT's kind and to
+    its class, and names the KATs a class cannot hold.
+
+    `short_wide` - under 256 compressed bytes announcing more than 256 of
+    output - is a second shape for the wavefront decoder, not the lane loop
+    on global memory the class was meant for: the seam's single-launch call
+    declines an output over 256 bytes (seam_tiny) and reports a status
+    without fields, and plan_class gives such a stream to the wavefront
+    decoder.  lane_decode on global memory sees headerless pieces and stored
+    chunks only; its element errors are checked by tests/test_element_cpu.py,
+    on the host, on these same bytes."""
+    import error_variants as V
+    import rust_snappy_amd as R
+    comps = [comp for _, _, comp in V.variants(cls)]
+    comps += [data for _, data, _, _ in V.unchanged_kats()]
+    caps = []
+    for c in comps:
+        try:
+            caps.append(O.decompress_len(c))
+        except O.SnapError:
+            caps.append(1024)
+    want = [_oracle_error(c, cap) for c, cap in zip(comps, caps)]
+    c = ctx
+    if cls == "seq":
+        c = R.raw.Context(0)
+        c.set_option("decode_kernel", 0)
+    try:
+        got, errs = gpu_decompress(c, comps, caps)
+    finally:
+        if c is not ctx:
+            c.close()
+    assert len(errs) == len(want)
+    for i, (e, w) in enumerate(zip(errs, want)):
+        assert tuple(e) == w, (cls, i, e, w)
+
+
 def test_decompress_corrupt_never_faults_and_matches_oracle(ctx):
     rng = random.Random(5)
     base = [O.compress(d) for _, d in O.corpus_round()[:4]]

@@ -17,8 +17,11 @@ decode(comp) -> ("ok", bytes) | ("irregular", s, d, prefix)
   complete; the kernel then runs the sequential decoder from there, which
   owns every error report.
 """
+from collections import Counter
+
 import numpy as np
 
+DEEP = 160        # input bytes in front of a window of the uniform fast path
 R = 4096          # ring bytes
 WMAX = 2048       # output bytes per window at most
 WAVE = 64
@@ -40,6 +43,17 @@ class Stats:
     def __init__(self):
         self.windows = self.rounds = self.far = self.wide = self.longlit = 0
         self.flush_partial = self.fence = self.elements = 0
+        # What the streams reached, named as in tests/model_decoder3.py
+        # (counters and sets only: nothing below reads them back).
+        self.events = Counter()     # name -> times; wrap_bytewise by (name, c)
+        self.trace = []             # (s, d, W, elements so far) per window
+        self.late_overlap = set()   # (offset, length) the sweep moved,
+        self.late_apart = set()     # offset < length and offset >= length
+        self.own_lane = set()       # ... copied by their own lane
+
+    def ev(self, name, n=1):
+        if n:
+            self.events[name] += int(n)
 
 
 def decode(comp, stats=None):
@@ -66,6 +80,7 @@ def decode(comp, stats=None):
 
     def ring_read16(pos):
         a = pos & (R - 1)
+        st.ev("ring_read_into_mirror", a > R - 16)
         return ring[a:a + 16].copy()   # may run into the mirror, never past
 
     def flush_chunks():
@@ -117,7 +132,9 @@ def decode(comp, stats=None):
             ~(is_lit & (lnb > 0) & (LANE + 5 > rem))
         # a window with 160 bytes of input in front of it needs none of the
         # per-lane tests (the kernel's uniform fast path)
-        deep = rem >= 160
+        deep = rem >= DEEP
+        st.ev("window_at_tail", rem == DEEP)
+        st.ev("handover_at_tail", rem == DEEP - 1)
         if deep:
             assert (fits == ~long_).all()
         inner = rem >= 64 + 5 + 16      # speculative 16-byte literal loads
@@ -165,6 +182,9 @@ def decode(comp, stats=None):
             # lane 0 is a long literal (> 64 bytes): 256 B per instruction
             st.longlit += 1
             Lq, h0 = int(L[0]), int(hd[0])
+            st.trace.append((s, d, 0, st.elements))
+            if long_[0]:
+                st.ev("longlit_form%d" % (h0 - 1))
             if (not long_[0]) or rem < h0 or src_len - (s + h0) < Lq or \
                     dst_len - d < Lq:
                 return irregular()
@@ -179,6 +199,10 @@ def decode(comp, stats=None):
         last = int(LANE[keep][-1])
         W = int(incl[last])
         cur = last + int(enc[last])
+        st.trace.append((s, d, W, st.elements))
+        st.ev("wmax_cut", (elem & ~keep & (incl > WMAX)
+                           & (LANE < (int(LANE[stop][0]) if stop.any()
+                                      else WAVE))).any())
         st.elements += E
         # ---- the reference's checks (src bounds hold by the TAIL rule) -----
         if d + W > dst_len:
@@ -210,6 +234,12 @@ def decode(comp, stats=None):
             (q + n <= d) & (olen <= off) &
             np.where(ring_ok, True, far_ok & (q + 64 <= dst_len)))
         far = lanewise & ~is_lit & ~ring_ok
+        st.ev("src_straddles_safe_lo", (cpy & (q < safe_lo)
+                                        & (safe_lo < q + n)).sum())
+        st.ev("win_not_whole", ring_lo + R > d + W + 16)
+        st.ev("far_multi_piece", (far & (olen > 16)).sum())
+        for i in LANE[lanewise & ~is_lit]:
+            st.own_lane.add((int(off[i]), int(olen[i])))
 
         def fence_for(limit):
             nonlocal visible, fenced
@@ -253,6 +283,8 @@ def decode(comp, stats=None):
                 m = min(int(olen[i]) - 16 * c, 16)
                 wa = (int(dstp[i]) + 16 * c) & (R - 1)
                 if wa + m > R:
+                    st.ev(("wrap_bytewise", 16 * c))
+                    st.ev("wrap_bytewise")
                     ring_write(int(dstp[i]) + 16 * c, reads[i][:m])
         st.rounds += 1
         for i in LANE[keep & ~lanewise]:     # the sweep, in stream order
@@ -263,6 +295,10 @@ def decode(comp, stats=None):
                 continue
             qi, oi, ni = int(q[i]), int(off[i]), int(olen[i])
             in_ring = qi >= safe_lo
+            (st.late_overlap if oi < ni else st.late_apart).add((oi, ni))
+            st.ev("late_not_ring", not in_ring)
+            st.ev("late_flush_partial",
+                  not in_ring and qi + min(ni, oi) > gflush)
             if not in_ring and qi + min(ni, oi) > gflush:
                 # bytes the ring has lost and that are not stored yet (only
                 # right after a long literal): store them, then read them
@@ -281,6 +317,8 @@ def decode(comp, stats=None):
         # changed: such a source lies below safe_lo.
         a0 = d & (R - 1)
         if a0 < 16 or a0 + W + 16 > R:
+            st.ev("mirror_lo", a0 < 16)
+            st.ev("mirror_hi", a0 + W + 16 > R)
             mirror()
         d += W
         s += cur

@@ -33,6 +33,8 @@ What differs from the second generation (tests/model_decoder.py):
 
 decode(comp) -> ("ok", bytes) | ("irregular", s, d, prefix)
 """
+from collections import Counter
+
 import numpy as np
 
 R = 4096          # ring bytes
@@ -62,6 +64,20 @@ class Stats:
         self.windows = self.runs = self.trips = self.sweeps = 0
         self.far = self.longlit = self.flush_partial = self.fence = 0
         self.elements = self.mirrors = 0
+        # What the streams reached (tests/decoder_shapes.py keeps a stream in
+        # a family by these).  Counters and sets only: nothing below reads
+        # them back.
+        self.events = Counter()     # name -> times; wrap_bytewise by (name, c)
+        self.trace = []             # (s, d, W, elements so far) per window
+        self.late_overlap = set()   # (offset, length), offset < length
+        self.late_apart = set()     # ... moved late, offset >= length
+        self.own_lane = set()       # ... copied by their own lane
+        self.late_general = set()   # pairs moved by the second late loop
+        self.late_ring_loop = set()   # ... by the first (all in the ring)
+
+    def ev(self, name, n=1):
+        if n:
+            self.events[name] += int(n)
 
 
 def top_bit(x):
@@ -93,6 +109,9 @@ def decode(comp, stats=None):
 
     def ring_read16(pos):
         a = pos & (R - 1)
+        if a > R - 16:
+            st.ev("ring_read_into_mirror")
+            st.ev(("ring_read_tail", R - a))
         return ring[a:a + 16].copy()   # may run into the mirror, never past
 
     def flush_chunks():
@@ -124,8 +143,10 @@ def decode(comp, stats=None):
     while s < src_len:
         rem = src_len - s
         if rem < TAIL:
+            st.ev("handover_at_tail", rem == TAIL - 1)
             return irregular()          # the sequential decoder's
         st.windows += 1
+        st.ev("window_at_tail", rem == TAIL)
         # ---- 1. how long is "the element at src[s + 64 g + lane]" ----------
         tagb = [src[s + 64 * g:s + 64 * g + WAVE].astype(np.int64)
                 for g in range(G)]
@@ -179,6 +200,8 @@ def decode(comp, stats=None):
                     postab[rank] = 64 * g + l
             base += bin(S[g]).count("1")
         n_el = min(base, WAVE)
+        st.ev("cap64", base > WAVE)
+        st.ev("starts_64", base == WAVE)
         act = LANE < n_el
         pos = np.where(act, postab[:WAVE], 0)
         # ---- 4. the element, in full, one per lane --------------------------
@@ -202,11 +225,16 @@ def decode(comp, stats=None):
         if (act & lng).any():            # the window ends in front of it
             keep &= LANE < int(LANE[act & lng][0])
         E = int(keep.sum())
+        if E and E < WAVE and act[E] and lng[E]:   # a long literal ends it
+            st.ev("longlit_mid_window")
+            st.ev("longlit_at_255", pos[E] == 255)
         if E == 0:
             # lane 0 is a literal with a length byte: moved by the whole wave
             assert lng[0]
             st.longlit += 1
             lnb = int(n6[0]) - 59
+            st.trace.append((s, d, 0, st.elements))
+            st.ev("longlit_form%d" % lnb)
             Lq = (int(b14[0]) & ((1 << (8 * lnb)) - 1)) + 1
             h0 = 1 + lnb
             if src_len - (s + h0) < Lq or dst_len - d < Lq:
@@ -223,6 +251,22 @@ def decode(comp, stats=None):
         last = E - 1
         W = int(incl[last])
         cur = int(pos[last]) + int(enc[last])
+        st.trace.append((s, d, W, st.elements))
+        st.ev("wmax_cut", E < WAVE and act[E] and not lng[E]
+              and incl[E] > WMAX)
+        st.ev("w_is_wmax", W == WMAX)
+        st.ev("last_is_lit60", is_lit[last] and olen[last] == 60)
+        for p in (31, 32, 63, 64, 255):
+            st.ev("start_at_%d" % p, (keep & (pos == p)).any())
+        st.ev("crosses_window_end", cur > 64 * G)
+        end = pos + enc - 1              # the element's last input byte
+        inside = keep & (end < 64 * G)
+        st.ev("crosses_sub_window", (inside & ((pos >> 5) != (end >> 5))).sum())
+        st.ev("crosses_group", (inside & ((pos >> 6) != (end >> 6))).sum())
+        st.ev("copy_crosses_sub_window",
+              (inside & ~is_lit & ((pos >> 5) != (end >> 5))).sum())
+        st.ev("copy_crosses_group",
+              (inside & ~is_lit & ((pos >> 6) != (end >> 6))).sum())
         st.elements += E
         # ---- the reference's checks --------------------------------------
         if d + W > dst_len:
@@ -250,6 +294,22 @@ def decode(comp, stats=None):
         assert (~(cpy & (off < olen)) | late).all()
         lw = keep & ~late
         far = lw & ~is_lit & ~in_ring
+        st.ev("src_straddles_safe_lo", (cpy & (q < safe_lo)
+                                        & (safe_lo < qe)).sum())
+        if whole:
+            for k in (-1, 0, 1):
+                st.ev(("q_at_safe_lo", k), (cpy & (q - safe_lo == k)).sum())
+                st.ev(("qe_at_safe_lo", k), (cpy & (qe - safe_lo == k)).sum())
+            st.ev("copy4_whole", (keep & (typ == 3)).sum())
+            st.ev("cap64_copy4_whole",
+                  base > WAVE and (keep & (typ == 3)).any())
+            st.ev("off_gt_64k_whole", (cpy & (off > 65535)).sum())
+        else:
+            st.ev("win_not_whole")
+            st.ev("far_own_lane_not_whole", far.sum())
+        st.ev("far_multi_piece", (far & (olen > 16)).sum())
+        for i in LANE[lw & ~is_lit]:
+            st.own_lane.add((int(off[i]), int(olen[i])))
         if far.any():
             st.far += int(far.sum())
             fence_for(int(qe[far].max()))
@@ -259,6 +319,8 @@ def decode(comp, stats=None):
         # instruction, which win, or late elements, written afterwards
         st.runs += 1
         cmax = int(((olen[lw] + 15) // 16).max()) if lw.any() else 0
+        if cmax:
+            st.ev("trips_%d" % cmax)
         for c in range(cmax - 1, -1, -1):
             st.trips += 1
             actc = lw & (16 * c < olen)
@@ -284,12 +346,21 @@ def decode(comp, stats=None):
                 m = min(int(olen[i]) - 16 * c, 16)
                 wa = (int(dstp[i]) + 16 * c) & (R - 1)
                 if wa + m > R:
+                    st.ev(("wrap_bytewise", 16 * c))
+                    st.ev(("wrap_front", 16 * c, R - wa))
+                    st.ev("wrap_bytewise")
                     ring_write(int(dstp[i]) + 16 * c, reads[i][:m])
+        general = bool((late & ~in_ring).any())   # the kernel's second loop
         for i in LANE[late]:                 # in stream order: lane k = byte k
             st.sweeps += 1
             qi, oi, ni = int(q[i]), int(off[i]), int(olen[i])
             inr = qi >= safe_lo
+            (st.late_overlap if oi < ni else st.late_apart).add((oi, ni))
+            (st.late_general if general else st.late_ring_loop).add((oi, ni))
+            st.ev("late_not_ring", not inr)
+            st.ev("late_src_near_end", not inr and qi + 64 > dst_len)
             if not inr and qi + min(ni, oi) > gflush:
+                st.ev("late_flush_partial")
                 flush_partial(int(dstp[i]))
             kk = np.arange(ni)
             srcpos = qi + (kk % oi)
@@ -301,7 +372,13 @@ def decode(comp, stats=None):
             ring_write(int(dstp[i]), data)
         # the mirror for the next window
         a0 = d & (R - 1)
+        if a0 < 16:
+            st.ev(("win_r0", a0))
+        if abs(a0 + W + 16 - R) <= 1:
+            st.ev(("win_end_gap", a0 + W + 16 - R))
         if a0 < 16 or a0 + W + 16 > R:
+            st.ev("mirror_lo", a0 < 16)
+            st.ev("mirror_hi", a0 + W + 16 > R)
             mirror()
         d += W
         s += cur
